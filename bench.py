@@ -1,7 +1,7 @@
 #!/usr/bin/env python
 """bench.py -- depth frames/sec of the SimpleRecon hot path on MI355X (BASELINE.json metric).
 
-    python bench.py --gpus N --steps K --warmup W [--workload NAME]
+    python bench.py --gpus N --steps K --warmup W [--workload NAME] [--dump-outputs DIR]
 
 A "step" is one pass of the hot path over one batch of synthetic keyframes that are already
 resident in HBM.  One process per GPU: under torch.distributed.run the process is one rank; a plain
@@ -19,12 +19,6 @@ import time
 
 ROOT = os.path.dirname(os.path.abspath(__file__))
 sys.path.insert(0, ROOT)
-
-# The step runs on 4 HIP streams (main, image-prior encoder, two decoder branches); an RCCL process group brings its own.  With
-# ROCm's default of 4 hardware queues per process the fifth stream shares a queue with one of ours and the streams serialise
-# against each other: +0.45 ms per step (1.6 %) from nothing but `init_process_group("nccl")` (scripts/pg_probe.py, r04).
-# Must be set before the HIP runtime initialises.
-os.environ.setdefault("GPU_MAX_HW_QUEUES", "8")
 
 import torch  # noqa: E402
 import torch.distributed as dist  # noqa: E402
@@ -135,6 +129,64 @@ def _fenced_experiment(workload, steps, warmup):
         return {"workload": workload, "value": None, "headline": False, "note": f"not measured: {type(e).__name__}: {e}"[:300]}
 
 
+DUMP_BUDGET_BYTES = 64 << 20   # --dump-outputs: all files together
+
+
+def _step_outputs(wl):
+    """name -> tensor: what the timed path handed its caller in the last timed step (the workload's `last` result --
+    a dict, a tuple or one tensor; the fused volume for the TSDF workload), plus the depth maps gathered to rank 0."""
+    out = {}
+
+    def add(name, v):
+        if isinstance(v, torch.Tensor):
+            out[name] = v
+        elif isinstance(v, dict):
+            for k, x in v.items():
+                add(f"{name}.{k}" if name else str(k), x)
+        elif isinstance(v, (list, tuple)):
+            for j, x in enumerate(v):
+                add(f"{name}.{j}" if name else f"out{j}", x)
+
+    add("", getattr(wl, "last", None))
+    fuser = getattr(getattr(wl, "fuser", None), "tsdf_fuser_pred", None)
+    if fuser is not None:
+        add("tsdf_values", fuser.tsdf_values)
+        add("tsdf_weights", fuser.tsdf_weights)
+    if getattr(wl, "gathered", None) is not None:
+        add("gathered", wl.gathered)
+    return out
+
+
+def dump_outputs(outputs, directory, budget=DUMP_BUDGET_BYTES):
+    """Writes every output as `directory/<name>.npy`: float64 stays float64, everything else (fp16, bool masks, integer
+    indices) becomes float32.  When the arrays together exceed `budget` bytes, the budget is shared out smallest array
+    first: an array within its share is written whole, a larger one as a fixed sample of its flattened elements (the same
+    positions in every run: seeded by the name and the shape), kept in index order.  Returns {name: [shape, number of
+    values written]}."""
+    import zlib
+    import numpy as np
+    os.makedirs(directory, exist_ok=True)
+    arrays = {}
+    for name, t in outputs.items():
+        a = t.detach().cpu().numpy()
+        arrays[name] = a.astype(np.float64 if a.dtype == np.float64 else np.float32, copy=False)
+    left = budget - 256 * len(arrays)   # (room for the .npy headers)
+    keep = {}
+    for j, name in enumerate(sorted(arrays, key=lambda n: arrays[n].nbytes)):
+        a = arrays[name]
+        keep[name] = min(a.size, max(1, left // (len(arrays) - j) // a.itemsize))
+        left -= keep[name] * a.itemsize
+    written = {}
+    for name, a in arrays.items():
+        shape = list(a.shape)
+        if keep[name] < a.size:
+            rng = np.random.default_rng(zlib.crc32(f"{name}{shape}".encode()))
+            a = a.reshape(-1)[np.sort(rng.choice(a.size, size=keep[name], replace=False))]
+        np.save(os.path.join(directory, f"{name}.npy"), np.ascontiguousarray(a))
+        written[name] = [shape, int(a.size)]
+    return written
+
+
 def _require_gpus(n):
     have = torch.cuda.device_count() if torch.cuda.is_available() else 0
     if have == 0:
@@ -160,6 +212,9 @@ def main():
     ap.add_argument("--force-collective", action="store_true",
                     help="initialise the process group and run the result gather / all-reduce / barrier collectives even "
                          "with one rank (exercises the RCCL path on a 1-GPU box)")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="after the timed steps, write what the last timed step computed as DIR/<name>.npy (rank 0; "
+                         "float32 / float64, at most 64 MB in all): two builds can be compared output for output")
     args = ap.parse_args()
     if args.gpus < 1:
         raise SystemExit("--gpus must be >= 1")
@@ -208,6 +263,7 @@ def main():
             dist.barrier()
         torch.cuda.synchronize()
 
+    dumped = None
     with torch.inference_mode():
         for _ in range(args.warmup):
             wl.step()
@@ -227,6 +283,8 @@ def main():
         if os.environ.get("SR_BENCH_TRACE"):
             print(f"[rank {rank}] steps issued {t_loop*1e3:.2f} ms, + gather issued {t_fin*1e3:.2f} ms, + barrier/sync {elapsed*1e3:.2f} ms",
                   file=sys.stderr, flush=True)
+        if args.dump_outputs and rank == 0:   # before anything below runs the workload again
+            dumped = dump_outputs(_step_outputs(wl), args.dump_outputs)
     dump = os.environ.get("SR_BENCH_DUMP")   # tests: the gathered result of the job, as rank 0 holds it
     if dump and rank == 0 and getattr(wl, "gathered", None) is not None:
         import numpy as np
@@ -253,6 +311,8 @@ def main():
         "data": "synthetic",
         "config": wl.config(world),
     }
+    if dumped is not None:
+        out["dumped_outputs"] = {"dir": args.dump_outputs, "arrays": dumped}
     if collective:
         out["config"]["backend"] = dist.get_backend()
         out["config"]["rank_pinning"] = pin

@@ -1,6 +1,5 @@
 import sys, os
 sys.path.insert(0, "/root/repo")
-os.environ.setdefault("GPU_MAX_HW_QUEUES", "8")
 import torch, bench_workloads
 from torch.profiler import profile, ProfilerActivity
 wl = bench_workloads.WORKLOADS["hero_cfg3"](torch.device("cuda", 0), 0)

@@ -49,10 +49,11 @@ def test_world_size_mismatch_is_an_error():
 
 
 def test_rank_pinning_gives_local_ranks_disjoint_core_slices():
-    """bench.pin_rank: the local ranks of a node take disjoint, equal slices of the allowed cores (no NUMA information
-    without a GPU: the slice is cut from everything the process may use) and torch's intra-op pool shrinks with it."""
+    """bench.pin_rank: the local ranks of a node take disjoint, equal slices of the allowed cores (no NUMA information:
+    the slice is cut from everything the process may use) and torch's intra-op pool shrinks with it.  Whether sysfs names
+    a GPU's NUMA node depends on the host, so the children run with that lookup answering "unknown"."""
     sys.path.insert(0, ROOT)
-    code = ("import sys, os, json; sys.path.insert(0, %r); import bench; "
+    code = ("import sys, os, json; sys.path.insert(0, %r); import bench; bench._gpu_numa_cpus = lambda dev: None; "
             "r = bench.pin_rank(int(sys.argv[1]), 4, 0); r['set'] = sorted(os.sched_getaffinity(0)); print(json.dumps(r))" % ROOT)
     allowed = sorted(os.sched_getaffinity(0))
     if len(allowed) < 4:
