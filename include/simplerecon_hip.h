@@ -47,7 +47,7 @@ enum {
   SR_OPT_WINO_KSPLIT, SR_OPT_CONV_WINO, SR_OPT_CONV_TILE, SR_OPT_CONV_KSPLIT, SR_OPT_MLP_VEC_STORE, SR_OPT_MLP_XCD,
   SR_OPT_MLP_BWD_VALU, SR_OPT_T16_XCD, SR_OPT_POOL_BW, SR_OPT_POOL_XCD, SR_OPT_PW_NT, SR_OPT_PW_KS, SR_OPT_PT_CFG, SR_OPT_PT_KS,
   SR_OPT_DOT_LDS, SR_OPT_DOT_QUAD, SR_OPT_DOT_LDS_G, SR_OPT_DOT_LDS_CULL, SR_OPT_DOT_LDS_CAP, SR_OPT_GEMM_AUTOTUNE,
-  SR_OPT_UPSAMPLE_QUAD, SR_OPT_POOL_STREAM, SR_OPT_MLP_RESERVE_CUS,
+  SR_OPT_UPSAMPLE_QUAD, SR_OPT_POOL_STREAM,
   SR_OPT_COUNT
 };
 int sr_option_count(void);
@@ -241,7 +241,7 @@ int sr_mlp_pack_weights(const float* W1, const float* b1, const float* W2, const
                         const float* W3, const float* b3, int hidden, int B, int K, int C, int h, int w,
                         void* workspace, size_t workspace_bytes, void* stream);
 
-/* The sweep kernel alone, on a workspace filled by sr_volume_prepare (with T_cur_src) and
+/* The sweep kernel alone (whole chip), on a workspace filled by sr_volume_prepare (with T_cur_src) and
  * sr_mlp_pack_weights for the same sizes. */
 int sr_mlp_volume_sweep(const float* cur, const float* invK_cur, const float* planes, int64_t ps_b,
                         int64_t ps_d, int64_t ps_y, int64_t ps_x, float leaky_slope, int B, int K,
@@ -249,14 +249,17 @@ int sr_mlp_volume_sweep(const float* cur, const float* invK_cur, const float* pl
                         int64_t cv_sp, float* out_lowest, uint8_t* out_mask, void* workspace,
                         size_t workspace_bytes, void* stream);
 
-/* = sr_volume_prepare + sr_mlp_pack_weights + sr_mlp_volume_sweep. */
+/* = sr_volume_prepare + sr_mlp_pack_weights + sr_mlp_volume_sweep, with a CU reserve for this call:
+ * reserve_cus = 0 runs the sweep on the whole chip; n > 0 makes its persistent grid leave n CUs to other streams, with the
+ * plane chunk planned for the CUs that remain (results do not depend on it).  A reserve that would leave fewer than 8 CUs
+ * means the whole chip; a negative one returns SR_ERR_INVALID_ARGUMENT. */
 int sr_mlp_volume_fwd(const float* cur, const float* src, const float* K_src, const float* T_src_cur,
                       const float* T_cur_src, const float* invK_cur, const float* planes, int64_t ps_b,
                       int64_t ps_d, int64_t ps_y, int64_t ps_x, const float* W1, const float* b1,
                       const float* W2, const float* b2, const float* W3, const float* b3, int hidden,
                       float leaky_slope, int B, int K, int C, int h, int w, int D, float* out_cv,
                       int64_t cv_sb, int64_t cv_sd, int64_t cv_sp, float* out_lowest, uint8_t* out_mask,
-                      void* workspace, size_t workspace_bytes, void* stream);
+                      int reserve_cus, void* workspace, size_t workspace_bytes, void* stream);
 
 /* ------------------------------------------------------------- 2-D conv stack -------
  *

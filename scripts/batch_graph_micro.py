@@ -7,4 +7,4 @@ for i in range(4): wl.step(i)
 torch.cuda.synchronize(); t = time.perf_counter()
 n = 20
 for i in range(n): wl.step(i)
-torch.cuda.synchronize(); print(f"B={B} reserve_max_batch={os.environ.get('SR_SWEEP_RESERVE_MAX_POINTS')} {(time.perf_counter()-t)/n*1e3:.3f} ms per step, {(time.perf_counter()-t)/n*1e3/B:.3f} per frame")
+torch.cuda.synchronize(); print(f"B={B} {(time.perf_counter()-t)/n*1e3:.3f} ms per step, {(time.perf_counter()-t)/n*1e3/B:.3f} per frame")

@@ -10,7 +10,7 @@ import torch
 
 _HERE = os.path.dirname(os.path.abspath(__file__))
 LIB_PATH = os.environ.get("SR_HIP_LIBRARY") or os.path.join(_HERE, "libsimplerecon_hip.so")   # override: ablation / trace builds
-ABI_VERSION = 1
+ABI_VERSION = 2
 
 _lib = None
 
@@ -65,7 +65,7 @@ SIGNATURES = {
     "sr_mlp_volume_sweep": (_i, [_p, _p, _p, _i64, _i64, _i64, _i64, _f, _i, _i, _i, _i, _i, _i,
                                  _p, _i64, _i64, _i64, _p, _p, _p, _sz, _p]),
     "sr_mlp_volume_fwd": (_i, [_p, _p, _p, _p, _p, _p, _p, _i64, _i64, _i64, _i64, _p, _p, _p, _p, _p, _p, _i,
-                               _f, _i, _i, _i, _i, _i, _i, _p, _i64, _i64, _i64, _p, _p, _p, _sz, _p]),
+                               _f, _i, _i, _i, _i, _i, _i, _p, _i64, _i64, _i64, _p, _p, _i, _p, _sz, _p]),
     "sr_conv_packed_weight_floats": (_sz, [_i, _i, _i]),
     "sr_conv_pack_weights": (_i, [_p, _i, _i, _i, _p, _p]),
     "sr_conv2d_nhwc_fwd": (_i, [_p, _i64, _i, _p, _p, _p, _i64, _i, _p, _i64, _i, _i, _i, _i, _i, _i, _i, _i, _f, _p]),
@@ -235,14 +235,13 @@ def set_option(name, value):
             raise ValueError(f"option {name} takes an integer, got {value!r}")   # (a typo used to become -1 silently)
         value = SPLIT_MODES.get(value, -1)
     prev = C.c_int(0)
-    if name in SPLIT_OPTION_NAMES:
-        with SPLIT_GUARD:
-            check(lib().sr_option_set(_option_id(name), int(value), C.byref(prev)), "sr_option_set")
-    else:
+    # a split mode's library value, mirror and listeners change together under the guard: a pack + launch in between would
+    # see the library in one mode and key its cache on the other
+    with SPLIT_GUARD if name in SPLIT_OPTION_NAMES else _NULL_CONTEXT:
         check(lib().sr_option_set(_option_id(name), int(value), C.byref(prev)), "sr_option_set")
-    _OPTION_MIRROR[name] = int(value)
-    for fn in OPTION_LISTENERS:
-        fn(name, int(value))
+        _OPTION_MIRROR[name] = int(value)
+        for fn in OPTION_LISTENERS:
+            fn(name, int(value))
     return prev.value
 
 

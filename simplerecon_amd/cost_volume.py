@@ -359,10 +359,6 @@ class FeatureVolumeManager(CostVolumeManager):
     # grad mode with parameters that require grad builds an autograd graph; inference runs under no_grad /
     # inference_mode (reference test.py:210).
     differentiable = True
-    # CUs the NEXT sweep leaves to other streams (0: none).  Set and cleared by DepthModel around its own call, never persistent:
-    # a persistent workgroup of the sweep owns its CU, so work on other streams is parked for the whole sweep otherwise.
-    _reserve_cus = 0
-    _reserve_oid = None
 
     def __init__(self, matching_height, matching_width, num_depth_bins=64, mlp_channels=(202, 128, 128, 1),
                  matching_dim_size=16, num_source_views=7):
@@ -382,8 +378,16 @@ class FeatureVolumeManager(CostVolumeManager):
             raise _lib.HipLibraryError(f"HIP matching MLP supports [Cin, H, H, 1] channel lists, got {self.mlp_channels}")
         return lin
 
+    def forward(self, cur_feats, src_feats, src_extrinsics, src_poses, src_Ks, cur_invK, min_depth, max_depth,
+                depth_planes_bdhw=None, return_mask=False, reserve_cus=0):
+        """As CostVolumeManager.forward.  `reserve_cus` = n > 0: the sweep's persistent grid leaves n CUs to work on other
+        streams for this call (a persistent workgroup owns its CU, so that work is parked for the whole sweep otherwise);
+        an inference-only scheduling hint that does not change the results (include/simplerecon_hip.h)."""
+        return self._sweep(cur_feats, src_feats, src_extrinsics, src_poses, src_Ks, cur_invK, min_depth,
+                           max_depth, depth_planes_bdhw, return_mask, reserve_cus)
+
     def _sweep(self, cur_feats, src_feats, src_extrinsics, src_poses, src_Ks, cur_invK, min_depth, max_depth,
-               depth_planes_bdhw, return_mask):
+               depth_planes_bdhw, return_mask, reserve_cus=0):
         cur_feats, src_feats, src_extrinsics, src_poses, src_Ks, cur_invK = _autocast_to_f32(
             cur_feats, src_feats, src_extrinsics, src_poses, src_Ks, cur_invK)
         b, k, c, h, w = self._check_inputs(cur_feats, src_feats, src_extrinsics, src_poses, src_Ks, cur_invK)
@@ -409,10 +413,10 @@ class FeatureVolumeManager(CostVolumeManager):
                                                          *[t.contiguous() for t in weights])
         else:
             vol, lowest, mask = self._launch_sweep(cur, src, Ks, T, Tp, invK, planes,
-                                                   [t.detach().contiguous() for t in weights], return_mask)
+                                                   [t.detach().contiguous() for t in weights], return_mask, reserve_cus)
         return vol, lowest, planes, (mask.bool() if mask is not None else None)
 
-    def _launch_sweep(self, cur, src, Ks, T, Tp, invK, planes, params, return_mask):
+    def _launch_sweep(self, cur, src, Ks, T, Tp, invK, planes, params, return_mask, reserve_cus=0):
         b, k, c, h, w = src.shape
         dev = src.device
         lib = _lib.lib()
@@ -426,15 +430,7 @@ class FeatureVolumeManager(CostVolumeManager):
         sb, sd, sp = self._volume_strides(vol)
         from . import ops   # (ops.PROFILE: bench.py's in-step kernel table)
         prof = ops.PROFILE
-        reserve = int(getattr(self, "_reserve_cus", 0))
         with _lib.SPLIT_GUARD, _lib.on_device(dev):   # (SR_MLP_SPLIT is read by the packing and by the sweep inside this one call)
-            if reserve > 0:
-                # this call only: the persistent grid leaves `reserve` CUs to other streams (DepthModel: the image-prior encoder on
-                # its side stream).  The option table is process-wide; every sweep launched through this module holds the guard.
-                if FeatureVolumeManager._reserve_oid is None:
-                    FeatureVolumeManager._reserve_oid = _lib._option_id("SR_MLP_RESERVE_CUS")
-                prev_reserve = C.c_int(0)
-                _lib.check(lib.sr_option_set(FeatureVolumeManager._reserve_oid, reserve, C.byref(prev_reserve)), "sr_option_set")
             if prof is not None:
                 ev0, ev1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
                 ev0.record()
@@ -443,9 +439,7 @@ class FeatureVolumeManager(CostVolumeManager):
                 _lib.ptr(planes), *planes.stride(), *[_lib.ptr(t) for t in params], hidden,
                 C.c_float(0.01),  # nn.LeakyReLU default slope (reference networks.py:139)
                 b, k, c, h, w, self.num_depth_bins, _lib.ptr(vol), sb, sd, sp, _lib.ptr(lowest),
-                _lib.ptr(mask), _lib.ptr(ws), ws.numel(), _lib.stream_ptr(dev))
-            if reserve > 0:
-                lib.sr_option_set(FeatureVolumeManager._reserve_oid, prev_reserve.value, C.byref(C.c_int(0)))
+                _lib.ptr(mask), int(reserve_cus), _lib.ptr(ws), ws.numel(), _lib.stream_ptr(dev))
             if prof is not None:
                 ev1.record()
                 cin = c * (k + 1) + 10 * k + 4

@@ -966,11 +966,17 @@ static float* sr_ws_packed(void* workspace, int B, int K, int C, int h, int w) {
   return (float*)sr_align_up((size_t)workspace + sr_volume_workspace_bytes(B, K, C, h, w), 256);
 }
 
-extern "C" int sr_mlp_volume_sweep(const float* cur, const float* invK_cur, const float* planes, int64_t ps_b,
-                                   int64_t ps_d, int64_t ps_y, int64_t ps_x, float leaky_slope, int B, int K,
-                                   int C, int h, int w, int D, float* out_cv, int64_t cv_sb, int64_t cv_sd,
-                                   int64_t cv_sp, float* out_lowest, uint8_t* out_mask, void* workspace,
-                                   size_t workspace_bytes, void* stream_) {
+// reserve_cus = n > 0: the persistent grid leaves n CUs to other streams (one workgroup owns a CU's LDS and registers, so
+// nothing else starts on a CU of the sweep); the plane chunk is planned for the CUs that remain.  DepthModel asks for it at
+// small batch, where the image-prior encoder's chain of small launches on the side stream is the critical path and would be
+// parked for the whole sweep (batch 1, graph replay: 5.72 -> 5.48 ms per frame although the sweep itself takes 14 % longer).
+// At batch 8 it costs what it gains (25.4-25.6 vs 25.2-25.5 ms; 27.2 vs 26.5 on the keyframe stream), at 960x736 / 96
+// planes it loses 2.4 ms of 46: the caller's decision, by batch size.  A reserve that would leave fewer than 8 CUs is ignored.
+static int sr_mlp_volume_sweep_reserved(const float* cur, const float* invK_cur, const float* planes, int64_t ps_b,
+                                        int64_t ps_d, int64_t ps_y, int64_t ps_x, float leaky_slope, int B, int K,
+                                        int C, int h, int w, int D, float* out_cv, int64_t cv_sb, int64_t cv_sd,
+                                        int64_t cv_sp, float* out_lowest, uint8_t* out_mask, int reserve_cus,
+                                        void* workspace, size_t workspace_bytes, void* stream_) {
   if (B < 0 || K <= 0 || C <= 0 || h <= 0 || w <= 0 || D <= 0) return SR_ERR_INVALID_ARGUMENT;
   if (B == 0) return SR_OK;
   if (!cur || !invK_cur || !planes || !out_cv || !workspace) return SR_ERR_INVALID_ARGUMENT;
@@ -998,31 +1004,17 @@ extern "C" int sr_mlp_volume_sweep(const float* cur, const float* invK_cur, cons
 
   // planes per work unit: as many as possible (the hoisted invariant part is paid once per unit) while the
   // units still spread evenly over the 4*CUs persistent waves
-  auto plan = [&](int ncu, int& chunk) {
-    const long waves = 4L * ncu;
-    double best_cost = 1e30;
-    chunk = 1;
-    for (int c = SR_PLANE_CHUNK; c >= 1; c >>= 1) {
-      const long units = (long)B * p.tiles * ((D + c - 1) / c);
-      const long rounds = (units + waves - 1) / waves;
-      const double cost = (double)rounds * (c * 1192.0 + 168.0);  // MFMAs per unit: c planes + invariant part
-      if (cost < best_cost) { best_cost = cost; chunk = c; }
-    }
-    return best_cost;
-  };
-  int cus = sr_device_cus(), best = 1;
-  const double full_cost = plan(cus, best);
-  // SR_MLP_RESERVE_CUS = n: the persistent grid leaves n CUs to other streams (one workgroup owns a CU's LDS and registers, so
-  // nothing else starts on a CU of the sweep); the plane chunk is planned for the CUs that remain.  DepthModel sets it around its
-  // own call at small batch, where the image-prior encoder's chain of small launches on the side stream is the critical path
-  // and would be parked for the whole sweep (batch 1, graph replay: 5.72 -> 5.48 ms per frame although the sweep itself takes
-  // 14 % longer).  At batch 8 it costs what it gains (25.4-25.6 vs 25.2-25.5 ms; 27.2 vs 26.5 on the keyframe stream), at
-  // 960x736 / 96 planes it loses 2.4 ms of 46: the caller's decision, by batch size.
-  {
-    const int r = sr_opt(SR_OPT_MLP_RESERVE_CUS);
-    if (r > 0 && cus - r >= 8) { cus -= r; (void)plan(cus, best); }
+  int cus = sr_device_cus();
+  if (reserve_cus > 0 && cus - reserve_cus >= 8) cus -= reserve_cus;
+  const long waves = 4L * cus;
+  double best_cost = 1e30;
+  int best = 1;
+  for (int c = SR_PLANE_CHUNK; c >= 1; c >>= 1) {
+    const long units = (long)B * p.tiles * ((D + c - 1) / c);
+    const long rounds = (units + waves - 1) / waves;
+    const double cost = (double)rounds * (c * 1192.0 + 168.0);  // MFMAs per unit: c planes + invariant part
+    if (cost < best_cost) { best_cost = cost; best = c; }
   }
-  (void)full_cost;
   p.chunk = best;
   p.chunks = (D + best - 1) / best;
   p.vec_store = (cv_sd == 1) && (p.chunk % 4 == 0) && (cv_sp % 4 == 0) && (cv_sb % 4 == 0) &&
@@ -1067,6 +1059,15 @@ extern "C" int sr_mlp_volume_sweep(const float* cur, const float* invK_cur, cons
   return rc;
 }
 
+extern "C" int sr_mlp_volume_sweep(const float* cur, const float* invK_cur, const float* planes, int64_t ps_b,
+                                   int64_t ps_d, int64_t ps_y, int64_t ps_x, float leaky_slope, int B, int K,
+                                   int C, int h, int w, int D, float* out_cv, int64_t cv_sb, int64_t cv_sd,
+                                   int64_t cv_sp, float* out_lowest, uint8_t* out_mask, void* workspace,
+                                   size_t workspace_bytes, void* stream_) {
+  return sr_mlp_volume_sweep_reserved(cur, invK_cur, planes, ps_b, ps_d, ps_y, ps_x, leaky_slope, B, K, C, h, w, D, out_cv,
+                                      cv_sb, cv_sd, cv_sp, out_lowest, out_mask, 0, workspace, workspace_bytes, stream_);
+}
+
 int sr_launch_argmax_planes(const float* cv, int64_t sb, int64_t sd, int64_t sp, SrPlanes planes, int B, int h, int w,
                             int D, float* lowest, hipStream_t stream) {
   hipLaunchKernelGGL(sr_argmax_planes_kernel, dim3((h * w + 63) / 64, B), dim3(64), 0, stream, cv, sb, sd, sp,
@@ -1095,8 +1096,8 @@ extern "C" int sr_mlp_volume_fwd(const float* cur, const float* src, const float
                                  const float* W2, const float* b2, const float* W3, const float* b3, int hidden,
                                  float leaky_slope, int B, int K, int C, int h, int w, int D, float* out_cv,
                                  int64_t cv_sb, int64_t cv_sd, int64_t cv_sp, float* out_lowest, uint8_t* out_mask,
-                                 void* workspace, size_t workspace_bytes, void* stream_) {
-  if (B < 0 || K <= 0 || C <= 0 || h <= 0 || w <= 0 || D <= 0) return SR_ERR_INVALID_ARGUMENT;
+                                 int reserve_cus, void* workspace, size_t workspace_bytes, void* stream_) {
+  if (B < 0 || K <= 0 || C <= 0 || h <= 0 || w <= 0 || D <= 0 || reserve_cus < 0) return SR_ERR_INVALID_ARGUMENT;
   if (B == 0) return SR_OK;
   if (!T_cur_src) return SR_ERR_INVALID_ARGUMENT;
   if (hidden != SR_HID || C != 16) return SR_ERR_UNSUPPORTED;
@@ -1105,6 +1106,7 @@ extern "C" int sr_mlp_volume_fwd(const float* cur, const float* src, const float
   if (rc) return rc;
   rc = sr_mlp_pack_weights(W1, b1, W2, b2, W3, b3, hidden, B, K, C, h, w, workspace, workspace_bytes, stream_);
   if (rc) return rc;
-  return sr_mlp_volume_sweep(cur, invK_cur, planes, ps_b, ps_d, ps_y, ps_x, leaky_slope, B, K, C, h, w, D, out_cv,
-                             cv_sb, cv_sd, cv_sp, out_lowest, out_mask, workspace, workspace_bytes, stream_);
+  return sr_mlp_volume_sweep_reserved(cur, invK_cur, planes, ps_b, ps_d, ps_y, ps_x, leaky_slope, B, K, C, h, w, D, out_cv,
+                                      cv_sb, cv_sd, cv_sp, out_lowest, out_mask, reserve_cus, workspace, workspace_bytes,
+                                      stream_);
 }

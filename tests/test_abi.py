@@ -146,3 +146,28 @@ def test_option_table_is_explicit_and_seeded_once_from_the_environment():
     assert _lib.set_option("SR_MLP_SPLIT", "int8") in (0, 1, 2, -1) and _lib.get_option("SR_MLP_SPLIT") == -1
     _lib.set_option("SR_MLP_SPLIT", 0)
     assert lib.sr_option_set(n, 0, None) == 1 and lib.sr_option_get(-1, C.byref(d)) == 1   # SR_ERR_INVALID_ARGUMENT
+
+
+def test_split_option_listeners_run_under_the_split_guard():
+    """A split mode's library value, Python mirror and listeners change together under SPLIT_GUARD: no pack + launch on
+    another thread sees them disagree (a listener probes the guard from a second thread)."""
+    import threading
+    from simplerecon_amd import _lib
+    seen = {}
+
+    def probe(name, value):
+        def try_guard():
+            got = _lib.SPLIT_GUARD.acquire(blocking=False)
+            if got:
+                _lib.SPLIT_GUARD.release()
+            seen[name] = got
+        t = threading.Thread(target=try_guard)
+        t.start()
+        t.join()
+    _lib.OPTION_LISTENERS.append(probe)
+    try:
+        for name in ("SR_MLP_SPLIT", "SR_WINO_SPLIT", "SR_PW_NT"):
+            _lib.set_option(name, _lib.get_option(name))
+    finally:
+        _lib.OPTION_LISTENERS.remove(probe)
+    assert seen == {"SR_MLP_SPLIT": False, "SR_WINO_SPLIT": False, "SR_PW_NT": True}

@@ -177,3 +177,29 @@ def test_cfg5_full_size_stress_config():
                                         planes_np[:1])
     assert_close(dv, dv_o, tol=2e-6, what="cfg5 dot sweep vs oracle")
     assert_lowest_cost(dlow, dv, planes_np[:1], dlow_o, "cfg5 dot sweep")
+
+
+def test_cu_reserve_changes_nothing_but_the_grid():
+    """`reserve_cus` (include/simplerecon_hip.h, sr_mlp_volume_fwd) at the batch-1 hero shape: the full chip, the 32 CUs
+    DepthModel leaves to the image-prior encoder, the smallest grid allowed (8 CUs) and a reserve too large to honour
+    (ignored) give bit-identical volumes, lowest costs and masks -- results do not depend on the plane chunking.  A negative
+    reserve is refused."""
+    from simplerecon_amd._lib import HipLibraryError
+    case = dict(B=1, K=7, C=16, D=64, h=120, w=160, seed=61)
+    inp = {k: v.to(DEV) for k, v in synthetic.cost_volume_inputs(1, 7, 16, 120, 160, seed=case["seed"]).items()}
+    mgr = _manager(case)
+    mgr.volume_memory_format = torch.channels_last
+    cus = torch.cuda.get_device_properties(DEV).multi_processor_count
+    outs = []
+    for reserve in (0, 32, cus - 8, cus - 7):
+        with torch.inference_mode():
+            vol, lowest, _, mask = mgr(return_mask=True, reserve_cus=reserve, **inp)
+        torch.cuda.synchronize()
+        outs.append((reserve, vol, lowest, mask))
+    _, vol0, low0, mask0 = outs[0]
+    for reserve, vol, lowest, mask in outs[1:]:
+        assert torch.equal(vol.view(torch.int32), vol0.view(torch.int32)), f"volume with reserve_cus={reserve}"
+        assert torch.equal(lowest.view(torch.int32), low0.view(torch.int32)), f"lowest cost with reserve_cus={reserve}"
+        assert torch.equal(mask, mask0), f"mask with reserve_cus={reserve}"
+    with pytest.raises(HipLibraryError), torch.inference_mode():
+        mgr(return_mask=True, reserve_cus=-1, **inp)

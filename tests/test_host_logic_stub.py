@@ -20,6 +20,8 @@ def stub(monkeypatch):
     class Calls(list):
         prefer_wino = False
     calls = Calls()
+    calls.args = []          # (name, arguments) of every stubbed call
+    calls.option_sets = []   # (id, value) of every sr_option_set, forwarded to the real library
 
     class Stream:
         cuda_stream = 0
@@ -39,6 +41,7 @@ def stub(monkeypatch):
                 else:
                     assert isinstance(v, int), (self.name, type(v), v)
             calls.append(self.name)
+            calls.args.append((self.name, args))
             if self.name == "sr_conv_prefers_wino":
                 return int(calls.prefer_wino)
             if res is ctypes.c_char_p:
@@ -47,8 +50,14 @@ def stub(monkeypatch):
 
     real = _lib.lib()   # (the option table is host-only code: those calls go to the real library, GPU or not)
 
+    def option_set(oid, value, previous):
+        calls.option_sets.append((oid, value))
+        return real.sr_option_set(oid, value, previous)
+
     class Lib:
         def __getattr__(self, name):
+            if name == "sr_option_set":
+                return option_set
             return getattr(real, name) if name.startswith("sr_option_") else Fn(name)
 
     from simplerecon_amd import ops
@@ -89,6 +98,28 @@ def test_inference_paths(stub, cls, kw, fwd):
     with torch.inference_mode():
         vol = mgr(**empty)[0]
     assert vol.shape == (0, D, H, W) and not [c for c in stub if c.endswith("_fwd")]
+
+
+def _reserve_arg(stub):
+    name, args = [c for c in stub.args if c[0] == "sr_mlp_volume_fwd"][-1]
+    argtypes = _lib.SIGNATURES[name][1]
+    assert argtypes[-4:] == [ctypes.c_int, ctypes.c_void_p, ctypes.c_size_t, ctypes.c_void_p]
+    return args[-4]   # reserve_cus, just before workspace, workspace_bytes, stream
+
+
+@pytest.mark.parametrize("cls", [cv.FeatureVolumeManager, cv.FastFeatureVolumeManager])
+def test_cu_reserve_is_an_argument_of_the_call(stub, cls):
+    """The MLP sweep's CU reserve reaches sr_mlp_volume_fwd as a call argument (0 by default) and touches no library option."""
+    inp = synthetic.cost_volume_inputs(B, K, C, H, W, seed=1)
+    mgr = cls(H, W, num_depth_bins=D, num_source_views=K)
+    with torch.inference_mode():
+        mgr(**inp)
+        assert _reserve_arg(stub) == 0
+        mgr(reserve_cus=32, **inp)
+        assert _reserve_arg(stub) == 32
+        mgr(**inp)
+        assert _reserve_arg(stub) == 0
+    assert stub.option_sets == []
 
 
 def test_autograd_seams(stub):
@@ -139,6 +170,7 @@ def test_whole_model_control_flow(stub, prefer_wino, fvt):
            "cam_T_world_b44": inp["src_extrinsics"], "world_T_cam_b44": inp["src_poses"]}
     with torch.inference_mode():
         out = model("test", cur, src, return_mask=True)
+    assert stub.option_sets == []   # the forward changes no process-wide library option
     for i in range(4):
         assert out[f"log_depth_pred_s{i}_b1hw"].shape == (b, 1, (h // 2) >> i, (w // 2) >> i)
         assert out[f"depth_pred_s{i}_b1hw"].shape == (b, 1, (h // 2) >> i, (w // 2) >> i)
@@ -152,6 +184,23 @@ def test_whole_model_control_flow(stub, prefer_wino, fvt):
                  "sr_conv3x3_wino_splitk_nhwc_fwd" if prefer_wino else "sr_conv2d_splitk_nhwc_fwd"):
         assert name in seen, name
     assert stub.count("sr_dwconv3x3_nhwc_fwd") == 30 and stub.count("sr_upsample2x_nhwc_fwd") == 16
+
+
+def test_sweep_reserve_rule():
+    """DepthModel leaves `sweep_reserved_cus` CUs to the image-prior encoder while that still runs on its side stream (a
+    pending pyramid), for metadata-MLP sweeps of up to `sweep_reserve_max_points` (pixel, plane) points; otherwise none."""
+    from simplerecon_amd import depth_model as dm
+    model = dm.DepthModel(dm.default_options(image_width=640, image_height=480, matching_num_depth_bins=64))
+    assert isinstance(model.cost_volume, cv.FeatureVolumeManager) and model.cost_volume.num_depth_bins == 64
+    feats = [torch.empty(0)] * 5
+    pending = dm.PendingPyramid(None, feats)
+    one, eight = torch.empty(1, 16, 120, 160), torch.empty(8, 16, 120, 160)
+    assert model.sweep_reserved_cus == 32 and model.sweep_reserve_max_points == 5_000_000
+    assert model._sweep_reserve(pending, one) == 32
+    assert model._sweep_reserve(pending, eight) == 0
+    assert model._sweep_reserve(feats, one) == 0
+    model.cost_volume = cv.CostVolumeManager(120, 160, num_depth_bins=64)
+    assert model._sweep_reserve(pending, one) == 0
 
 
 def test_autocast_region_upcasts_half_features(stub):
