@@ -46,8 +46,8 @@ enum {
   SR_OPT_MLP_SPLIT = 0, SR_OPT_WINO_SPLIT, SR_OPT_WINO_XCD, SR_OPT_WINO_STAGGER, SR_OPT_WINO_WG_PER_CU, SR_OPT_WINO_NT,
   SR_OPT_WINO_KSPLIT, SR_OPT_CONV_WINO, SR_OPT_CONV_TILE, SR_OPT_CONV_KSPLIT, SR_OPT_MLP_VEC_STORE, SR_OPT_MLP_XCD,
   SR_OPT_MLP_BWD_VALU, SR_OPT_T16_XCD, SR_OPT_POOL_BW, SR_OPT_POOL_XCD, SR_OPT_PW_NT, SR_OPT_PW_KS, SR_OPT_PT_CFG, SR_OPT_PT_KS,
-  SR_OPT_DOT_LDS, SR_OPT_DOT_QUAD, SR_OPT_DOT_LDS_G, SR_OPT_DOT_LDS_CULL, SR_OPT_DOT_LDS_CAP, SR_OPT_GEMM_AUTOTUNE,
-  SR_OPT_UPSAMPLE_QUAD, SR_OPT_POOL_STREAM,
+  SR_OPT_DOT_LDS, SR_OPT_DOT_QUAD, SR_OPT_DOT_LDS_G, SR_OPT_DOT_LDS_CULL, SR_OPT_DOT_LDS_CAP, SR_OPT_UPSAMPLE_QUAD,
+  SR_OPT_POOL_STREAM,
   SR_OPT_COUNT
 };
 int sr_option_count(void);
@@ -93,19 +93,6 @@ int sr_dot_volume_sweep(const float* cur, const float* invK_cur, const float* pl
                         int D, float* out_cv, int64_t cv_sb, int64_t cv_sd, int64_t cv_sp,
                         float* out_lowest, uint8_t* out_mask, void* workspace,
                         size_t workspace_bytes, void* stream);
-
-/* 1x1 convolution over a dense channels-last map as a plain library GEMM (hipBLASLt, fp32 in / out / accumulate):
- * out[m][co] = act( sum_ci in[m][ci] * weight[co][ci] + bias[co] [+ residual[m][co]] ) for the M = B*H*W pixels of a map
- * whose pixels are `*_pix_stride` floats apart (channel slices of wider buffers are fine).  `weight` is the UNPACKED
- * [Cout][Cin] nn.Conv2d weight (eval-mode BatchNorm folded by the caller); act 0 none, 1 SiLU, 2 ReLU (a residual is added
- * BEFORE the activation).  Replaces nn.Conv2d(k=1) + BatchNorm + SiLU of the image-prior encoder's MBConv blocks
- * (reference depth_model.py:110-116) and the 1x1 skip convs of BasicBlock (layers.py:58-65) where this is faster than
- * sr_conv2d_nhwc_fwd.  `workspace`: sr_gemm1x1_workspace_bytes(), 256-byte aligned.  SR_ERR_UNSUPPORTED when hipBLASLt
- * offers no algorithm for the shape (use sr_conv2d_nhwc_fwd then). */
-size_t sr_gemm1x1_workspace_bytes(void);
-int sr_gemm1x1_nhwc_fwd(const float* in, int in_pix_stride, const float* weight, const float* bias, const float* residual,
-                        int res_pix_stride, float* out, int out_pix_stride, int M, int Cin, int Cout, int act,
-                        void* workspace, size_t workspace_bytes, void* stream);
 
 /* Pointwise (1x1, stride 1) convolution as a hand-written fp32-MFMA GEMM (csrc/sr_pw.hip), deterministic:
  *   out[b,p,co] = act( sum_ci gate[b,ci] * in[b,p,ci] * W[co,ci] + bias[co] + residual[b,p,co] ),  p = 0 .. HW-1
@@ -578,22 +565,6 @@ int sr_se_gate_fwd(const float* pool_partial, int bands, int pixels, const float
 int sr_rgb_stem3x3s2_fwd(const float* image, int64_t sb, int64_t sc, int64_t sy, int64_t sx, const float* weight27c,
                          const float* bias, float* out, int64_t out_batch_stride, int out_pix_stride, int B, int H, int W,
                          int Cout, int pad_top, int pad_left, int Ho, int Wo, float act_code, void* stream);
-
-/* The front half of a stride-1 MBConv block in ONE launch (csrc/sr_mbconv_fused.hip, r05): 1x1 expansion (BatchNorm folded,
- * SiLU) -> depthwise 3x3 / pad 1 (BatchNorm folded, SiLU) -> squeeze-excite average pool -> squeeze-excite gates
- * sigmoid(W2 silu(W1 mean + b1) + b2) -- timm's InvertedResidual up to the projection (reference
- * experiment_modules/depth_model.py:110-116 builds the encoder from timm), which stays sr_pw_conv_nhwc_fwd with `gate`.
- * `w_expand` [mid][Cin], `w_dw9c` [9][mid] tap-major, `w_reduce` [rd][mid], `w_excite` [mid][rd]; `out` [B][H*W][mid]
- * channels-last view, `pool` [B][mid] (channel sums, by-product), `gate` [B][mid]; `counters`: B zeroed 32-bit words that the
- * call leaves zeroed (one arrival counter per image: the last workgroup of an image computes its gates).  `counters` must not be
- * shared by launches that may be in flight at the same time (different streams): one buffer per stream.  Deterministic.
- * sr_mbconv_fused_supported(): Cin in {128, 160, 256}, mid % 16 == 0, rd <= 64, H*W*64 bytes within the LDS budget. */
-int sr_mbconv_fused_supported(int H, int W, int Cin, int mid, int rd);
-int sr_mbconv_expand_dw_se_fwd(const float* in, int64_t in_batch_stride, int in_pix_stride, const float* w_expand,
-                               const float* b_expand, const float* w_dw9c, const float* b_dw, const float* w_reduce,
-                               const float* b_reduce, const float* w_excite, const float* b_excite, float* out,
-                               int64_t out_batch_stride, int out_pix_stride, float* pool, float* gate, unsigned* counters,
-                               int B, int H, int W, int Cin, int mid, int rd, void* stream);
 
 /* The squeeze-excite gates alone, gate[b][c] = sigmoid(W2 silu(W1 mean_b + b1) + b2)[c], from sr_dwconv3x3_nhwc_fwd's partial
  * sums (timm SqueezeExcite of the MBConv blocks, reference depth_model.py:110-116) for a consumer that applies them itself:

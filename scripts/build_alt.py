@@ -37,8 +37,7 @@ def main():
     with concurrent.futures.ThreadPoolExecutor(max_workers=8) as ex:
         objs = list(ex.map(comp, B.sources()))
     lib = os.path.join(out_dir, f"libsr_{name}.so")
-    subprocess.check_call([B.HIPCC, "--offload-arch=" + B.ARCH, "-shared", "-fPIC", "-o", lib] + objs +
-                          ["-L/opt/rocm/lib", "-lhipblaslt"])
+    subprocess.check_call([B.HIPCC, "--offload-arch=" + B.ARCH, "-shared", "-fPIC", "-o", lib] + objs)
     print(lib)
 
 

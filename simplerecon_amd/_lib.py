@@ -10,7 +10,7 @@ import torch
 
 _HERE = os.path.dirname(os.path.abspath(__file__))
 LIB_PATH = os.environ.get("SR_HIP_LIBRARY") or os.path.join(_HERE, "libsimplerecon_hip.so")   # override: ablation / trace builds
-ABI_VERSION = 2
+ABI_VERSION = 3
 
 _lib = None
 
@@ -36,11 +36,6 @@ SIGNATURES = {
                                  _p, _i64, _i64, _i64, _p, _p, _p, _sz, _p]),
     "sr_dot_volume_fwd": (_i, [_p, _p, _p, _p, _p, _p, _i64, _i64, _i64, _i64, _i, _i, _i, _i, _i, _i,
                                _p, _i64, _i64, _i64, _p, _p, _p, _sz, _p]),
-    "sr_gemm1x1_workspace_bytes": (_sz, []),
-    "sr_gemm1x1_nhwc_fwd": (_i, [_p, _i, _p, _p, _p, _i, _p, _i, _i, _i, _i, _i, _p, _sz, _p]),
-    "sr_mbconv_fused_supported": (_i, [_i, _i, _i, _i, _i]),
-    "sr_mbconv_expand_dw_se_fwd": (_i, [_p, _i64, _i, _p, _p, _p, _p, _p, _p, _p, _p, _p, _i64, _i, _p, _p, _p, _i, _i, _i, _i, _i,
-                                        _i, _p]),
     "sr_rgb_stem3x3s2_fwd": (_i, [_p, _i64, _i64, _i64, _i64, _p, _p, _p, _i64, _i, _i, _i, _i, _i, _i, _i, _i, _i, _f, _p]),
     "sr_se_gate2_fwd": (_i, [_p, _i, _i, _p, _p, _p, _p, _p, _p, _i, _i, _i, _p]),
     "sr_conv3x3_wino_io_nhwc_fwd": (_i, [_p, _i64, _i, _p, _p, _p, _i64, _i, _p, _i64, _i, _i, _i, _i, _i, _i, _f, _i, _p]),
@@ -179,7 +174,8 @@ def lib():
     return _lib
 
 
-_ERRORS = {1: "invalid argument", 2: "unsupported configuration", 3: "workspace too small"}
+ERR_UNSUPPORTED = 2   # SR_ERR_UNSUPPORTED: the entry point does not serve this configuration (callers may fall back)
+_ERRORS = {1: "invalid argument", ERR_UNSUPPORTED: "unsupported configuration", 3: "workspace too small"}
 
 
 def check(rc, what):

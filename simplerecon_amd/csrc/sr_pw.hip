@@ -6,9 +6,9 @@
 // expand / project convolutions of the image-prior encoder (reference experiment_modules/depth_model.py:110-116: timm
 // tf_efficientnetv2_s), where `gate` is the squeeze-excite gate of the block (sigmoid(W2 silu(W1 mean)), one value per
 // image and INPUT channel of the projection) -- applied while the A operand is loaded, so the gated activation tensor is
-// never written.  r02 / r03 handed these GEMMs to hipBLASLt (sr_gemm1x1.hip), which picked its algorithm by timing, per
-// process: fast, but two processes were not bit-identical.  This kernel is deterministic (fixed reduction order), serves the
-// short-K / short-N / small-M shapes of the encoder with a launch plan of its own, and keeps the library behind a switch.
+// never written.  r02 / r03 handed these GEMMs to hipBLASLt (since removed), which picked its algorithm by timing, per
+// process: fast, but two processes were not bit-identical.  This kernel is deterministic (fixed reduction order) and serves
+// the short-K / short-N / small-M shapes of the encoder with a launch plan of its own.
 //
 // GEMM view: M = pixels (a 32-row MFMA tile never straddles two images: ceil(HW / 32) tiles per image), N = output
 // channels, K = input channels, v_mfma_f32_32x32x2_f32 (fp32 products, fp32 accumulation).  A wave owns a 32 x (32 NT)

@@ -184,37 +184,15 @@ def packed_weight(conv: nn.Conv2d, bn=None):
     return packed, bias
 
 
-_GEMM_W = weakref.WeakKeyDictionary()  # nn.Conv2d (1x1) -> (state key, [Cout, Cin] weight with BN folded, bias)
-# 1x1 / stride-1 convolutions: "pw" (default) = the hand-written pointwise MFMA GEMM of csrc/sr_pw.hip (deterministic, r04);
-# "lib" = hipBLASLt where the caller allows it (library_gemm=True; r02 / r03 behaviour: the algorithm is picked by timing,
-# per process); "0" = the implicit-GEMM conv kernel for everything.
-_MODE_1X1 = os.environ.get("SR_CONV1X1_GEMM", "pw")
-USE_PW_1X1 = _MODE_1X1 not in ("0", "lib", "1")
+# 1x1 / stride-1 convolutions run on the hand-written pointwise MFMA GEMM of csrc/sr_pw.hip (deterministic, r04); False sends
+# the ungated ones to the implicit-GEMM conv kernel (the reference path of the tests)
+USE_PW_1X1 = True
 # which of the two pointwise kernels: "auto" = the LDS-tiled one for batch-dense maps of at least PW_TILED_MIN_ROWS pixels
 # (the HBM-bound full-resolution skips: 168 vs 182 us for 192 -> 64 @ 8x240x320), the direct one below that -- on the small-M
 # encoder GEMMs the tiled kernel's one or two workgroups per CU cannot hide their load latency and it measured no faster
 # (38 vs 36 us for 1536 -> 256 @ 8x15x20, profiles/r04_pw_plan_sweep.txt); "1" / "0" force one of them
 PW_TILED = os.environ.get("SR_PW_TILED", "auto")
 PW_TILED_MIN_ROWS = 100000
-USE_GEMM_1X1 = _MODE_1X1 in ("lib", "1")
-GEMM_1X1_MIN_PIXELS = 1024
-SHORTCUT_GEMM = os.environ.get("SR_SHORTCUT_GEMM", "1") != "0"   # BasicBlock's 1x1 skip conv as a library GEMM
-
-
-def gemm_weight(conv: nn.Conv2d, bn=None):
-    """([Cout, Cin] weight, bias) of a 1x1 conv with the eval-mode BatchNorm folded in, for sr_gemm1x1_nhwc_fwd."""
-    _lib.require_device_f32("conv weight", conv.weight)
-    key = _state_key(conv, bn)
-    hit = _GEMM_W.get(conv)
-    if hit is not None and hit[0] == key:
-        _await_packed(conv, "gemm", conv.weight.device)   # folded on another stream's first call?  wait for it
-        return hit[1], hit[2]
-    w, bias = _effective_weight(conv, bn)
-    w2d = w.reshape(w.shape[0], w.shape[1]).contiguous()
-    bias = bias.contiguous() if bias is not None else None
-    _packed_here(conv, "gemm", conv.weight.device)
-    _GEMM_W[conv] = (key, w2d, bias)
-    return w2d, bias
 
 
 _PACKED_LIN = weakref.WeakKeyDictionary()  # nn.Linear -> (weight version, data_ptr, packed tensor)
@@ -335,21 +313,19 @@ def _shape_query(lib, name, *shape, dev=None):
     return v
 
 
-def conv2d(x, conv: nn.Conv2d, residual=None, leaky=None, out=None, bn=None, act=None, tf_same=False, library_gemm=False,
-           gate=None):
-    """act(bn(conv(x) + bias) [+ residual]) with nn.Conv2d semantics (zero or replicate padding); `bn` is an
-    eval-mode BatchNorm2d folded into weight and bias.  `leaky` = LeakyReLU slope, or act="silu".  tf_same=True
-    replaces the module's symmetric padding by TensorFlow-"SAME" padding (tf_same_pads).  library_gemm=True lets a 1x1
-    conv over a dense map run as a hipBLASLt GEMM (faster on the MBConv shapes; its algorithm choice depends on the number
-    of pixels; only with SR_CONV1X1_GEMM=lib since r04).  Batch-size invariance: every kernel on the default path is run-to-run
-    deterministic, but the RESULT OF A FRAME MAY DEPEND ON THE BATCH IT IS IN (and on the CU count of the device) in its low-order
-    bits: the launch plans are chosen from the total number of work items, B included -- a 3x3 / stride-1 layer runs F(4x4)
-    Winograd at one batch size and F(2x2) at another (sr_conv_prefers_wino4: 64 -> 64 at 240x320 is F(2x2) at B = 1, F(4x4) at
-    B = 8; error constants 3e-7 vs 1.3e-6 of the output range), and the Winograd / direct / pointwise plans split K on small
-    maps.  Within ONE plan the per-pixel arithmetic does not depend on B.  tests/test_gpu_determinism.py pins the run-to-run
-    statement and the 1x1 cases, tests/test_gpu_e2e_full_size.py::test_batch_1_and_batch_8_agree_frame_by_frame the model-level
-    agreement (to the element-wise tolerance each holds against the oracle, not bitwise).  `gate` ([B, Cin], 1x1 / stride-1 convs only): the input is scaled
-    per image and input channel while it is loaded (the squeeze-excite gate of an MBConv block).  Returns a channels-last view."""
+def conv2d(x, conv: nn.Conv2d, residual=None, leaky=None, out=None, bn=None, act=None, tf_same=False, gate=None):
+    """act(bn(conv(x) + bias) [+ residual]) with nn.Conv2d semantics (zero or replicate padding); `bn` is an eval-mode
+    BatchNorm2d folded into weight and bias.  `leaky` = LeakyReLU slope, or act="silu".  tf_same=True replaces the module's
+    symmetric padding by TensorFlow-"SAME" padding (tf_same_pads).  Batch-size invariance: every kernel on the default path is
+    run-to-run deterministic, but the RESULT OF A FRAME MAY DEPEND ON THE BATCH IT IS IN (and on the CU count of the device) in
+    its low-order bits: the launch plans are chosen from the total number of work items, B included -- a 3x3 / stride-1 layer
+    runs F(4x4) Winograd at one batch size and F(2x2) at another (sr_conv_prefers_wino4: 64 -> 64 at 240x320 is F(2x2) at B = 1,
+    F(4x4) at B = 8; error constants 3e-7 vs 1.3e-6 of the output range), and the Winograd / direct / pointwise plans split K on
+    small maps.  Within ONE plan the per-pixel arithmetic does not depend on B.  tests/test_gpu_determinism.py pins the
+    run-to-run statement and the 1x1 cases, tests/test_gpu_e2e_full_size.py::test_batch_1_and_batch_8_agree_frame_by_frame the
+    model-level agreement (to the element-wise tolerance each holds against the oracle, not bitwise).  `gate` ([B, Cin], 1x1 /
+    stride-1 convs only): the input is scaled per image and input channel while it is loaded (the squeeze-excite gate of an
+    MBConv block).  Returns a channels-last view."""
     _lib.refuse_autograd(x, conv.weight)
     x = as_nhwc(x, "conv input")
     b, ci, h, w = x.shape
@@ -382,67 +358,24 @@ def conv2d(x, conv: nn.Conv2d, residual=None, leaky=None, out=None, bn=None, act
     isb, isp = _strides(x)
     osb, osp = _strides(out)
     rsb, rsp = _strides(residual) if residual is not None else (0, 0)
-    prof = PROFILE
-    if use_wino and wino_split_mode():
-        # fenced split-precision Winograd (SR_WINO_SPLIT, csrc/sr_wino_split.hip): the vector instantiation only -- layers with
-        # unaligned tensors or channel counts that are no multiple of 4 take the direct fp32 kernel instead
-        al = lambda t, sb_, sp_: t is None or (t.data_ptr() % 16 == 0 and sp_ % 4 == 0 and sb_ % 4 == 0)
-        if not (ci % 4 == 0 and co % 4 == 0 and al(x, isb, isp) and al(out, osb, osp) and al(residual, rsb, rsp)):
-            use_wino = False
+    split = use_wino and wino_split_mode()
+    if split and not (ci % 4 == 0 and co % 4 == 0 and _aligned16(x, isb, isp) and _aligned16(out, osb, osp)
+                      and _aligned16(residual, rsb, rsp)):
+        # the fenced split-precision Winograd (SR_WINO_SPLIT, csrc/sr_wino_split.hip) has the vector instantiation only:
+        # unaligned tensors and channel counts that are no multiple of 4 take the direct fp32 kernel instead
+        use_wino = split = False
     if gate is not None:
         _lib.require_device_f32("gate", gate)
         if k != 1 or s != 1 or tuple(gate.shape) != (b, ci) or not gate.is_contiguous():
             raise ValueError(f"`gate` needs a 1x1 / stride-1 conv and a contiguous [{b}, {ci}] tensor")
+    slope = C.c_float(_act_code(leaky, act))
+    strides = (isb, isp, osb, osp, rsb, rsp)
     if k == 1 and s == 1 and not padded and not replicate and (USE_PW_1X1 or gate is not None) and ci % 4 == 0 \
-            and x.data_ptr() % 16 == 0 and isp % 4 == 0 and isb % 4 == 0:
-        wp, bias = packed_weight(conv, bn)
-        m = b * h * w
-        dense = (b == 1 or (isb == h * w * isp and osb == h * w * osp and (residual is None or rsb == h * w * rsp)))
-        tiled = dense and (PW_TILED == "1" or (PW_TILED == "auto" and m >= PW_TILED_MIN_ROWS))
-        gflag = 'true' if gate is not None else 'false'
-        with _lib.on_device(x.device):
-            if tiled:
-                nbytes = _shape_query(lib, "sr_pw_conv_tiled_workspace_bytes", m, ci, co, dev=x.device.index)
-                ws = _workspace(x.device, "pw_splitk", nbytes) if nbytes else None
-            if prof is not None:
-                ev0, ev1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
-                ev0.record()
-            if tiled:
-                rc = lib.sr_pw_conv_tiled_nhwc_fwd(_lib.ptr(x), isp, _lib.ptr(wp), _lib.ptr(bias), _lib.ptr(gate),
-                                                   _lib.ptr(residual), rsp, _lib.ptr(out), osp, m, h * w, ci, co,
-                                                   C.c_float(_act_code(leaky, act)), _lib.ptr(ws), nbytes,
-                                                   _lib.stream_ptr(x.device))
-            else:
-                rc = lib.sr_pw_conv_nhwc_fwd(_lib.ptr(x), isb, isp, _lib.ptr(wp), _lib.ptr(bias), _lib.ptr(gate),
-                                             _lib.ptr(residual), rsb, rsp, _lib.ptr(out), osb, osp, b, h * w, ci, co,
-                                             C.c_float(_act_code(leaky, act)), _lib.stream_ptr(x.device))
-            if prof is not None:
-                ev1.record()
-                a_, b_ = C.c_int(0), C.c_int(0)
-                if tiled:
-                    # the plan the LAUNCHER took: it splits K only with a usable workspace AND 16-byte aligned out / residual /
-                    # bias rows (sr_pw_conv_tiled_nhwc_fwd's `can_split`), so ask with the same answer
-                    al16 = lambda t, sp_: t is None or (t.data_ptr() % 16 == 0 and sp_ % 4 == 0)
-                    can_split = ws is not None and ws.data_ptr() % 16 == 0 and co % 4 == 0 and al16(out, osp) and \
-                        al16(residual, rsp) and (bias is None or bias.data_ptr() % 16 == 0)
-                    lib.sr_pw_conv_tiled_plan(m, ci, co, int(can_split), C.byref(a_), C.byref(b_))
-                    if b_.value > 1 and nbytes < b_.value * m * co * 4:
-                        lib.sr_pw_conv_tiled_plan(m, ci, co, 0, C.byref(a_), C.byref(b_))
-                    tile_m, tile_n = ((64, 128), (128, 160), (128, 64), (64, 64))[a_.value]
-                    executed = 2.0 * (-(-m // tile_m) * tile_m) * (-(-co // tile_n) * tile_n) * (-(-ci // 32) * 32)
-                    name = f"sr_pw_tiled_kernel<{tile_m}x{tile_n}, ks {b_.value}, {gflag}>"
-                else:
-                    lib.sr_pw_conv_plan(b, h * w, ci, co, C.byref(a_), C.byref(b_))
-                    mt = b * ((h * w + 31) // 32)
-                    executed = 2.0 * mt * 32 * ((co + 32 * a_.value - 1) // (32 * a_.value) * 32 * a_.value) * ((ci + 7) // 8 * 8)
-                    name = f"sr_pw_kernel<{a_.value}, {b_.value}, {gflag}>"
-                prof.append((name, 2.0 * b * h * w * co * ci, ev0, ev1, (b, ci, h, w, co, k, s, ho, wo, residual is not None),
-                             executed))
-        if rc != 2 or gate is not None:   # SR_ERR_UNSUPPORTED (a per-image byte range past 2^31): the implicit-GEMM kernel below,
-            _lib.check(rc, "sr_pw_conv_tiled_nhwc_fwd" if tiled else "sr_pw_conv_nhwc_fwd")   # whose addressing is 64-bit
+            and _aligned16(x, isb, isp):
+        shape = (b, ci, h, w, co, k, s, ho, wo, residual is not None)
+        if _conv_pointwise(lib, x, conv, bn, residual, out, gate, strides, shape, slope) == 0:
             return out
-        if prof is not None:
-            prof.pop()
+        # SR_ERR_UNSUPPORTED (a per-image byte range past 2^31): the implicit-GEMM kernel below, whose addressing is 64-bit
     if gate is not None:
         raise _lib.HipLibraryError("a gated 1x1 convolution needs Cin % 4 == 0 and 16-byte aligned input rows")
     if k == 1 and s == 1 and (w % 32 != 0 or h % 4 != 0) and (isp, isb) == (ci, h * w * ci) \
@@ -454,124 +387,161 @@ def conv2d(x, conv: nn.Conv2d, residual=None, leaky=None, out=None, bn=None, act
         fw = 32 if m % 32 == 0 else 8 if m % 8 == 0 else 0
         if fw:
             b, h, w, ho, wo = 1, m // fw, fw, m // fw, fw
-            isb, osb, rsb = m * ci, m * co, (m * co if residual is not None else 0)
-    # 1x1 convs over dense maps are plain GEMMs: hipBLASLt (north star: "rocBLAS/MFMA only where it is a dense im2col
-    # GEMM") is 1.25-1.75x faster than the implicit-GEMM kernel on the MBConv shapes (scripts/gemm_probe.py)
-    if library_gemm and k == 1 and s == 1 and not padded and not replicate and USE_GEMM_1X1 and \
-            b * h * w >= GEMM_1X1_MIN_PIXELS:
-        gact = 0 if (leaky is None and act is None) else 1 if act == "silu" else 2 if (act is None and leaky == 0.0) else -1
-        dense = (isb == h * w * isp or b == 1) and (osb == ho * wo * osp or b == 1) and \
-            (residual is None or rsb == ho * wo * rsp or b == 1)
-        if gact >= 0 and dense:
-            w2d, gbias = gemm_weight(conv, bn)
-            ws = _workspace(x.device, "gemm1x1", lib.sr_gemm1x1_workspace_bytes())
-            with _lib.on_device(x.device):
-                if prof is not None:
-                    ev0, ev1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
-                    ev0.record()
-                rc = lib.sr_gemm1x1_nhwc_fwd(_lib.ptr(x), isp, _lib.ptr(w2d), _lib.ptr(gbias), _lib.ptr(residual), rsp,
-                                             _lib.ptr(out), osp, b * h * w, ci, co, gact, _lib.ptr(ws), ws.numel() * 4,
-                                             _lib.stream_ptr(x.device))
-                if prof is not None and rc == 0:
-                    ev1.record()
-                    prof.append(("hipBLASLt fp32 GEMM (1x1 conv)", 2.0 * b * ho * wo * co * ci, ev0, ev1,
-                                 (b, ci, h, w, co, k, s, ho, wo, residual is not None), None))
-            if rc == 0:
-                return out
-            if rc != 2:   # SR_ERR_UNSUPPORTED: no library algorithm for this shape -> the HIP kernel below
-                _lib.check(rc, "sr_gemm1x1_nhwc_fwd")
+            strides = (m * ci, isp, m * co, osp, m * co if residual is not None else 0, rsp)
+    shape = (b, ci, h, w, co, k, s, ho, wo, residual is not None)
     w4_form = _shape_query(lib, "sr_conv_prefers_wino4", b, h, w, ci, co, WINO4_MODE, dev=x.device.index) \
-        if (use_wino and WINO4_MODE and not wino_split_mode()) else 0   # 0: F(2x2); 1 / 3: the kernel form the rule picks
-    if w4_form:
-        al = lambda t, sb_, sp_: t is None or (t.data_ptr() % 16 == 0 and sp_ % 4 == 0 and sb_ % 4 == 0)
-        wp4, bias4 = packed_wino4_weight(conv, bn)
-        if al(x, isb, isp) and al(out, osb, osp) and al(residual, rsb, rsp) and (bias4 is None or bias4.data_ptr() % 16 == 0):
-            with _lib.on_device(x.device):
-                if prof is not None:
-                    ev0, ev1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
-                    ev0.record()
-                rc = lib.sr_conv3x3_wino4_variant_nhwc_fwd(_lib.ptr(x), isb, isp, _lib.ptr(wp4), _lib.ptr(bias4),
-                                                           _lib.ptr(residual), rsb, rsp, _lib.ptr(out), osb, osp, b, h, w, ci, co,
-                                                           C.c_float(_act_code(leaky, act)), WINO4_VARIANT or w4_form,
-                                                           _lib.stream_ptr(x.device))
-                if prof is not None and rc == 0:
-                    ev1.record()
-                    regions = ((h + 15) // 16) * ((w + 15) // 16)   # multiplies issued: 36 per 4x4 tile and (ci, co) pair, padded
-                    executed = 2.0 * b * regions * 16 * 36 * ((ci + 15) // 16 * 16) * ((co + 63) // 64 * 64)
-                    prof.append(("sr_wino4ws_kernel" if (WINO4_VARIANT or w4_form) == 3 else "sr_wino4_kernel",
-                                 2.0 * b * ho * wo * co * ci * 9, ev0, ev1,
-                                 (b, ci, h, w, co, k, s, ho, wo, residual is not None), executed))
-            if rc == 0:
-                return out
-            if rc != 2:   # SR_ERR_UNSUPPORTED (per-image byte range): the F(2x2) kernel below
-                _lib.check(rc, "sr_conv3x3_wino4_nhwc_fwd")
-    # (pack and launch must see ONE split mode: ADVICE r05.  A plain acquire / release -- a context manager object per call costs
-    # a microsecond on a launch path that is host-bound at batch 1)
-    if use_wino:
-        _lib.SPLIT_GUARD.acquire()
-    try:
-        wp, bias = packed_wino_weight(conv, bn) if use_wino else packed_weight(conv, bn)
-        slope = C.c_float(_act_code(leaky, act))
-        with _lib.on_device(x.device):
-            if prof is not None:
-                ev0, ev1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
-                ev0.record()
-            if padded:
-                rc = lib.sr_conv2d_padded_nhwc_fwd(_lib.ptr(x), isb, isp, _lib.ptr(wp), _lib.ptr(bias), _lib.ptr(residual),
-                                                   rsb, rsp, _lib.ptr(out), osb, osp, b, h, w, ci, co, k, s, *pads, slope,
-                                                   _lib.stream_ptr(x.device))
-            elif use_wino:
-                nbytes = _shape_query(lib, "sr_wino_splitk_workspace_bytes", b, h, w, ci, co, dev=x.device.index)   # 0 unless the plan splits K
-                ws = _workspace(x.device, "wino_splitk", nbytes) if nbytes else None
-                rc = lib.sr_conv3x3_wino_splitk_nhwc_fwd(_lib.ptr(x), isb, isp, _lib.ptr(wp), _lib.ptr(bias),
-                                                         _lib.ptr(residual), rsb, rsp, _lib.ptr(out), osb, osp, b, h, w, ci,
-                                                         co, slope, _lib.ptr(ws), nbytes, _lib.stream_ptr(x.device))
-            elif replicate:
-                rc = lib.sr_conv2d_replicate_nhwc_fwd(_lib.ptr(x), isb, isp, _lib.ptr(wp), _lib.ptr(bias),
-                                                      _lib.ptr(residual), rsb, rsp, _lib.ptr(out), osb, osp, b, h, w, ci,
-                                                      co, k, s, slope, _lib.stream_ptr(x.device))
-            else:
-                nbytes = _shape_query(lib, "sr_conv_splitk_workspace_bytes", b, h, w, ci, co, k, s, dev=x.device.index)   # 0 unless it may split K
-                ws = _workspace(x.device, "conv_splitk", nbytes) if nbytes else None
-                rc = lib.sr_conv2d_splitk_nhwc_fwd(_lib.ptr(x), isb, isp, _lib.ptr(wp), _lib.ptr(bias), _lib.ptr(residual),
-                                                   rsb, rsp, _lib.ptr(out), osb, osp, b, h, w, ci, co, k, s, slope,
-                                                   _lib.ptr(ws), nbytes, _lib.stream_ptr(x.device))
-            if prof is not None:
-                ev1.record()
-                v4 = int(x.data_ptr() % 16 == 0 and isp % 4 == 0 and isb % 4 == 0)
-                if use_wino:
-                    vin = bool(v4 and ci % 4 == 0)
-                    al = lambda t, sb_, sp_: t is None or (t.data_ptr() % 16 == 0 and sp_ % 4 == 0 and sb_ % 4 == 0)
-                    vout = vin and co % 4 == 0 and al(out, osb, osp) and al(residual, rsb, rsp) and \
-                        (bias is None or bias.data_ptr() % 16 == 0)
-                    name = lib.sr_wino_kernel_name(b, h, w, ci, co, int(vin), int(vout)).decode()
-                    if wino_split_mode():   # (the fenced variant: sr_wino_split_kernel<NT, FMT>)
-                        name = name.replace("sr_wino_kernel<", "sr_wino_split_kernel<").replace(
-                            ", true, true>", f", {1 if wino_split_mode() == 'bf16' else 2}>")
-                else:
-                    name = lib.sr_conv_kernel_name(b, h, w, ci, co, k, s, v4).decode()
-                executed = None
-                if use_wino:  # multiplies actually issued: 16 per 2x2 tile and (ci, co) pair, on padded regions / channels
-                    regions = ((h + 7) // 8) * ((w + 15) // 16)
-                    executed = 2.0 * b * regions * 32 * 16 * ((ci + 15) // 16 * 16) * ((co + 31) // 32 * 32)
-                prof.append((name, 2.0 * b * ho * wo * co * ci * k * k, ev0, ev1,
-                             (b, ci, h, w, co, k, s, ho, wo, residual is not None), executed))
-        if use_wino and rc == 2 and not wino_split_mode():
-            # SR_ERR_UNSUPPORTED from the Winograd entry point (a per-image byte range past 2^31: its buffer descriptors carry 32-bit
-            # offsets): the implicit-GEMM kernel serves the shape with 64-bit addressing, as it did before r04
-            if prof is not None:
-                prof.pop()
-            wp, bias = packed_weight(conv, bn)
-            with _lib.on_device(x.device):
-                rc = lib.sr_conv2d_nhwc_fwd(_lib.ptr(x), isb, isp, _lib.ptr(wp), _lib.ptr(bias), _lib.ptr(residual), rsb, rsp,
-                                            _lib.ptr(out), osb, osp, b, h, w, ci, co, k, s, slope, _lib.stream_ptr(x.device))
-            _lib.check(rc, "sr_conv2d_nhwc_fwd")
-            return out
-        _lib.check(rc, "sr_conv3x3_wino_nhwc_fwd" if use_wino else "sr_conv2d_nhwc_fwd")
+        if (use_wino and WINO4_MODE and not split) else 0   # 0: F(2x2); 1 / 3: the kernel form the rule picks
+    if w4_form and _conv_wino4(lib, x, conv, bn, residual, out, strides, shape, slope, WINO4_VARIANT or w4_form) == 0:
         return out
-    finally:
-        if use_wino:
+    if use_wino:
+        # pack and launch must see ONE split mode.  A plain acquire / release -- a context manager object per call
+        # costs a microsecond on a launch path that is host-bound at batch 1
+        _lib.SPLIT_GUARD.acquire()
+        try:
+            if _conv_wino(lib, x, conv, bn, residual, out, strides, shape, slope) == 0:
+                return out
+        finally:
             _lib.SPLIT_GUARD.release()
+        # SR_ERR_UNSUPPORTED from the Winograd entry point (a per-image byte range past 2^31: its buffer descriptors carry 32-bit
+        # offsets): the implicit-GEMM kernel serves the shape with 64-bit addressing, as it did before r04
+        wp, bias = packed_weight(conv, bn)
+        isb, isp, osb, osp, rsb, rsp = strides
+        with _lib.on_device(x.device):
+            rc = lib.sr_conv2d_nhwc_fwd(_lib.ptr(x), isb, isp, _lib.ptr(wp), _lib.ptr(bias), _lib.ptr(residual), rsb, rsp,
+                                        _lib.ptr(out), osb, osp, b, h, w, ci, co, k, s, slope, _lib.stream_ptr(x.device))
+        _lib.check(rc, "sr_conv2d_nhwc_fwd")
+        return out
+    _conv_direct(lib, x, conv, bn, residual, out, strides, shape, slope, pads if padded else None, replicate)
+    return out
+
+
+def _aligned16(t, sb, sp):
+    """None, or a channels-last view whose pixel rows all start 16-byte aligned (the kernels' vector instantiations)."""
+    return t is None or (t.data_ptr() % 16 == 0 and sp % 4 == 0 and sb % 4 == 0)
+
+
+def _launch(x, shape, entry, fallback, describe, fn, *args):
+    """fn(*args) on x's device -> the library's rc; raises for any error but SR_ERR_UNSUPPORTED with a `fallback` behind it
+    (`entry`: the call's name in the message).  With PROFILE on, two timing events bracket the launch and a launch that
+    succeeded appends (kernel name, algorithmic FLOPs, start event, end event, shape, executed FLOPs); describe() -> (kernel
+    name, executed FLOPs or None) is only asked then."""
+    prof = PROFILE
+    with _lib.on_device(x.device):
+        if prof is None:
+            rc = fn(*args)
+        else:
+            ev0, ev1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+            ev0.record()
+            rc = fn(*args)
+            ev1.record()
+            if rc == 0:
+                b, ci, h, w, co, k, s, ho, wo, _ = shape
+                name, executed = describe()
+                prof.append((name, 2.0 * b * ho * wo * co * ci * k * k, ev0, ev1, shape, executed))
+    if rc != 0 and (rc != _lib.ERR_UNSUPPORTED or not fallback):
+        _lib.check(rc, entry)
+    return rc
+
+
+def _conv_pointwise(lib, x, conv, bn, residual, out, gate, strides, shape, slope):
+    """1x1 / stride-1: the pointwise GEMM kernels of csrc/sr_pw.hip (the LDS-tiled one on large batch-dense maps)."""
+    isb, isp, osb, osp, rsb, rsp = strides
+    b, ci, h, w, co = shape[:5]
+    wp, bias = packed_weight(conv, bn)
+    m = b * h * w
+    dense = b == 1 or (isb == h * w * isp and osb == h * w * osp and (residual is None or rsb == h * w * rsp))
+    gflag = "true" if gate is not None else "false"
+    if dense and (PW_TILED == "1" or (PW_TILED == "auto" and m >= PW_TILED_MIN_ROWS)):
+        nbytes = _shape_query(lib, "sr_pw_conv_tiled_workspace_bytes", m, ci, co, dev=x.device.index)
+        ws = _workspace(x.device, "pw_splitk", nbytes) if nbytes else None
+
+        def describe():
+            # the plan the LAUNCHER took: it splits K only with a usable workspace AND 16-byte aligned out / residual / bias
+            # rows (sr_pw_conv_tiled_nhwc_fwd's `can_split`), so ask with the same answer
+            a_, b_ = C.c_int(0), C.c_int(0)
+            can_split = ws is not None and ws.data_ptr() % 16 == 0 and co % 4 == 0 and _aligned16(out, 0, osp) and \
+                _aligned16(residual, 0, rsp) and (bias is None or bias.data_ptr() % 16 == 0)
+            lib.sr_pw_conv_tiled_plan(m, ci, co, int(can_split), C.byref(a_), C.byref(b_))
+            if b_.value > 1 and nbytes < b_.value * m * co * 4:
+                lib.sr_pw_conv_tiled_plan(m, ci, co, 0, C.byref(a_), C.byref(b_))
+            tile_m, tile_n = ((64, 128), (128, 160), (128, 64), (64, 64))[a_.value]
+            executed = 2.0 * (-(-m // tile_m) * tile_m) * (-(-co // tile_n) * tile_n) * (-(-ci // 32) * 32)
+            return f"sr_pw_tiled_kernel<{tile_m}x{tile_n}, ks {b_.value}, {gflag}>", executed
+        return _launch(x, shape, "sr_pw_conv_tiled_nhwc_fwd", gate is None, describe, lib.sr_pw_conv_tiled_nhwc_fwd,
+                       _lib.ptr(x), isp, _lib.ptr(wp), _lib.ptr(bias), _lib.ptr(gate), _lib.ptr(residual), rsp, _lib.ptr(out),
+                       osp, m, h * w, ci, co, slope, _lib.ptr(ws), nbytes, _lib.stream_ptr(x.device))
+
+    def describe():
+        a_, b_ = C.c_int(0), C.c_int(0)
+        lib.sr_pw_conv_plan(b, h * w, ci, co, C.byref(a_), C.byref(b_))
+        mt = b * ((h * w + 31) // 32)
+        executed = 2.0 * mt * 32 * ((co + 32 * a_.value - 1) // (32 * a_.value) * 32 * a_.value) * ((ci + 7) // 8 * 8)
+        return f"sr_pw_kernel<{a_.value}, {b_.value}, {gflag}>", executed
+    return _launch(x, shape, "sr_pw_conv_nhwc_fwd", gate is None, describe, lib.sr_pw_conv_nhwc_fwd, _lib.ptr(x), isb, isp,
+                   _lib.ptr(wp), _lib.ptr(bias), _lib.ptr(gate), _lib.ptr(residual), rsb, rsp, _lib.ptr(out), osb, osp, b,
+                   h * w, ci, co, slope, _lib.stream_ptr(x.device))
+
+
+def _conv_wino4(lib, x, conv, bn, residual, out, strides, shape, slope, variant):
+    """3x3 / stride 1: F(4x4, 3x3) Winograd (csrc/sr_wino4.hip) in kernel form `variant`; SR_ERR_UNSUPPORTED without
+    launching when a tensor or the bias is not 16-byte aligned."""
+    isb, isp, osb, osp, rsb, rsp = strides
+    b, ci, h, w, co = shape[:5]
+    wp, bias = packed_wino4_weight(conv, bn)
+    if not (_aligned16(x, isb, isp) and _aligned16(out, osb, osp) and _aligned16(residual, rsb, rsp)
+            and (bias is None or bias.data_ptr() % 16 == 0)):
+        return _lib.ERR_UNSUPPORTED
+
+    def describe():
+        regions = ((h + 15) // 16) * ((w + 15) // 16)   # multiplies issued: 36 per 4x4 tile and (ci, co) pair, padded
+        executed = 2.0 * b * regions * 16 * 36 * ((ci + 15) // 16 * 16) * ((co + 63) // 64 * 64)
+        return "sr_wino4ws_kernel" if variant == 3 else "sr_wino4_kernel", executed
+    return _launch(x, shape, "sr_conv3x3_wino4_nhwc_fwd", True, describe, lib.sr_conv3x3_wino4_variant_nhwc_fwd, _lib.ptr(x),
+                   isb, isp, _lib.ptr(wp), _lib.ptr(bias), _lib.ptr(residual), rsb, rsp, _lib.ptr(out), osb, osp, b, h, w, ci,
+                   co, slope, variant, _lib.stream_ptr(x.device))
+
+
+def _conv_wino(lib, x, conv, bn, residual, out, strides, shape, slope):
+    """3x3 / stride 1: F(2x2, 3x3) Winograd (csrc/sr_wino.hip, or the fenced split-precision variant of SR_WINO_SPLIT)."""
+    isb, isp, osb, osp, rsb, rsp = strides
+    b, ci, h, w, co = shape[:5]
+    split = wino_split_mode()
+    wp, bias = packed_wino_weight(conv, bn)
+    nbytes = _shape_query(lib, "sr_wino_splitk_workspace_bytes", b, h, w, ci, co, dev=x.device.index)   # 0 unless it splits K
+    ws = _workspace(x.device, "wino_splitk", nbytes) if nbytes else None
+
+    def describe():
+        vin = bool(_aligned16(x, isb, isp) and ci % 4 == 0)
+        vout = vin and co % 4 == 0 and _aligned16(out, osb, osp) and _aligned16(residual, rsb, rsp) and \
+            (bias is None or bias.data_ptr() % 16 == 0)
+        name = lib.sr_wino_kernel_name(b, h, w, ci, co, int(vin), int(vout)).decode()
+        if split:   # (the fenced variant: sr_wino_split_kernel<NT, FMT>)
+            name = name.replace("sr_wino_kernel<", "sr_wino_split_kernel<").replace(
+                ", true, true>", f", {1 if split == 'bf16' else 2}>")
+        regions = ((h + 7) // 8) * ((w + 15) // 16)   # multiplies issued: 16 per 2x2 tile and (ci, co) pair, padded
+        return name, 2.0 * b * regions * 32 * 16 * ((ci + 15) // 16 * 16) * ((co + 31) // 32 * 32)
+    return _launch(x, shape, "sr_conv3x3_wino_nhwc_fwd", not split, describe, lib.sr_conv3x3_wino_splitk_nhwc_fwd,
+                   _lib.ptr(x), isb, isp, _lib.ptr(wp), _lib.ptr(bias), _lib.ptr(residual), rsb, rsp, _lib.ptr(out), osb, osp,
+                   b, h, w, ci, co, slope, _lib.ptr(ws), nbytes, _lib.stream_ptr(x.device))
+
+
+def _conv_direct(lib, x, conv, bn, residual, out, strides, shape, slope, pads, replicate):
+    """Implicit-GEMM direct convolution (csrc/sr_conv.hip): explicit zero `pads`, replicate or symmetric zero padding."""
+    isb, isp, osb, osp, rsb, rsp = strides
+    b, ci, h, w, co, k, s = shape[:7]
+    wp, bias = packed_weight(conv, bn)
+    args = (_lib.ptr(x), isb, isp, _lib.ptr(wp), _lib.ptr(bias), _lib.ptr(residual), rsb, rsp, _lib.ptr(out), osb, osp,
+            b, h, w, ci, co, k, s)
+    describe = lambda: (lib.sr_conv_kernel_name(b, h, w, ci, co, k, s, int(_aligned16(x, isb, isp))).decode(), None)
+    launch = lambda fn, *tail: _launch(x, shape, "sr_conv2d_nhwc_fwd", False, describe, fn, *args, *tail,
+                                       _lib.stream_ptr(x.device))
+    if pads is not None:
+        return launch(lib.sr_conv2d_padded_nhwc_fwd, *pads, slope)
+    if replicate:
+        return launch(lib.sr_conv2d_replicate_nhwc_fwd, slope)
+    nbytes = _shape_query(lib, "sr_conv_splitk_workspace_bytes", b, h, w, ci, co, k, s, dev=x.device.index)   # 0 unless it may split K
+    ws = _workspace(x.device, "conv_splitk", nbytes) if nbytes else None
+    return launch(lib.sr_conv2d_splitk_nhwc_fwd, slope, _lib.ptr(ws), nbytes)
 
 
 def basic_block(block, x, out=None):
@@ -581,7 +551,7 @@ def basic_block(block, x, out=None):
     slope = block.relu.negative_slope
     x = as_nhwc(x, "BasicBlock input")
     t = conv2d(x, block.conv1, leaky=slope)
-    identity = x if block.downsample is None else conv2d(x, block.downsample[0], library_gemm=SHORTCUT_GEMM)
+    identity = x if block.downsample is None else conv2d(x, block.downsample[0])
     return conv2d(t, block.conv2, residual=identity, leaky=slope, out=out)
 
 
@@ -997,54 +967,6 @@ def se_gates(pool_partial, pixels, conv_reduce: nn.Conv2d, conv_expand: nn.Conv2
                                         _lib.stream_ptr(gate.device))
     _lib.check(rc, "sr_se_gate2_fwd")
     return gate
-
-
-# (device, stream) -> zeroed int32 arrival counters of sr_mbconv_expand_dw_se_fwd (the call leaves them zeroed).  Per STREAM: two
-# fused launches in flight on different streams must not interleave their atomicAdds on one buffer -- launches on one
-# stream are ordered.  A captured graph keeps the buffer of the stream it was captured on.
-_MBX_COUNTERS = {}
-
-
-def mbconv_fused_supported(x, conv_pw: nn.Conv2d, conv_dw: nn.Conv2d, se):
-    """True when the one-launch front half (csrc/sr_mbconv_fused.hip) serves this MBConv block on this input."""
-    if conv_dw.stride != (1, 1) or tuple(conv_dw.padding) != (1, 1) or conv_pw.kernel_size != (1, 1):
-        return False
-    return bool(_shape_query(_lib.lib(), "sr_mbconv_fused_supported", x.shape[2], x.shape[3], conv_pw.in_channels,
-                             conv_pw.out_channels, se.conv_reduce.out_channels))
-
-
-def mbconv_expand_dw_se(x, conv_pw: nn.Conv2d, bn1, conv_dw: nn.Conv2d, bn2, se):
-    """MBConv front half in one launch: silu(bn1(conv_pw(x))) -> silu(bn2(conv_dw(.))) -> squeeze-excite gates.  Returns
-    (the depthwise output as a channels-last view, gates [B, mid]); the projection applies the gates (conv2d(..., gate=))."""
-    _lib.refuse_autograd(x, conv_pw.weight)
-    x = as_nhwc(x, "MBConv input")
-    b, ci, h, w = x.shape
-    mid, rd = conv_pw.out_channels, se.conv_reduce.out_channels
-    w_exp, b_exp = gemm_weight(conv_pw, bn1)
-    w9c, b_dw = packed_dw_weight(conv_dw, bn2)
-    w1, w2 = se.conv_reduce.weight.detach(), se.conv_expand.weight.detach()
-    if not (w1.is_contiguous() and w2.is_contiguous()):
-        w1, w2 = w1.contiguous(), w2.contiguous()
-    b1 = se.conv_reduce.bias.detach() if se.conv_reduce.bias is not None else None
-    b2 = se.conv_expand.bias.detach() if se.conv_expand.bias is not None else None
-    out = empty_nhwc(b, mid, h, w, x.device)
-    pool = torch.empty((b, mid), dtype=torch.float32, device=x.device)
-    gate = torch.empty((b, mid), dtype=torch.float32, device=x.device)
-    if b == 0:
-        return out, gate
-    ckey = (x.device, torch.cuda.current_stream(x.device).cuda_stream)
-    cnt = _MBX_COUNTERS.get(ckey)
-    if cnt is None or cnt.numel() < b:
-        cnt = _MBX_COUNTERS[ckey] = torch.zeros(max(b, 64), dtype=torch.int32, device=x.device)
-    isb, isp = _strides(x)
-    osb, osp = _strides(out)
-    with _lib.on_device(x.device):
-        rc = _lib.lib().sr_mbconv_expand_dw_se_fwd(_lib.ptr(x), isb, isp, _lib.ptr(w_exp), _lib.ptr(b_exp), _lib.ptr(w9c),
-                                                   _lib.ptr(b_dw), _lib.ptr(w1), _lib.ptr(b1), _lib.ptr(w2), _lib.ptr(b2),
-                                                   _lib.ptr(out), osb, osp, _lib.ptr(pool), _lib.ptr(gate), _lib.ptr(cnt), b, h, w,
-                                                   ci, mid, rd, _lib.stream_ptr(x.device))
-    _lib.check(rc, "sr_mbconv_expand_dw_se_fwd")
-    return out, gate
 
 
 def se_scale_(x, pool_partial, conv_reduce: nn.Conv2d, conv_expand: nn.Conv2d, want_gate=False):

@@ -244,9 +244,9 @@ def test_winograd_pipeline_cases_and_work_order(shape, monkeypatch, sr_option):
 @pytest.mark.parametrize("shape", [(8, 160, 960, 30, 40, "silu", False), (8, 960, 160, 30, 40, None, True),
                                    (2, 64, 128, 120, 160, None, False), (1, 192, 64, 48, 64, "relu", True),
                                    (3, 24, 1, 33, 47, None, False)])
-def test_conv1x1_library_gemm_path(shape, monkeypatch):
-    """1x1 convs over dense maps through hipBLASLt (sr_gemm1x1_nhwc_fwd: bias, BatchNorm fold, residual before the
-    activation, SiLU / ReLU epilogues, channel-slice outputs) against F.conv2d and against the implicit-GEMM HIP kernel."""
+def test_conv1x1_implicit_gemm_path(shape, monkeypatch):
+    """1x1 convs over dense maps through the implicit-GEMM conv kernel (the reference path of the pointwise GEMM: bias,
+    BatchNorm fold, residual before the activation, SiLU / ReLU epilogues, channel-slice outputs) against F.conv2d."""
     B, ci, co, h, w, act, with_res = shape
     g = torch.Generator().manual_seed(ci * 3 + co)
     conv = torch.nn.Conv2d(ci, co, 1).to(DEV)
@@ -260,21 +260,12 @@ def test_conv1x1_library_gemm_path(shape, monkeypatch):
     if res is not None:
         ref = ref + res
     ref = torch.nn.functional.silu(ref) if act == "silu" else torch.relu(ref) if act == "relu" else ref
-    outs = {}
-    monkeypatch.setattr(ops, "USE_PW_1X1", False)   # (r04 default: the hand-written pointwise GEMM, tested below)
-    for use in (True, False):
-        monkeypatch.setattr(ops, "USE_GEMM_1X1", use)
-        with torch.inference_mode():
-            ops.PROFILE = []
-            buf = ops.empty_nhwc(B, co + 8, h, w, DEV).fill_(3.0)      # write into a channel slice of a wider buffer
-            ops.conv2d(x, conv, bn=bn, residual=res, out=buf[:, 4:4 + co], library_gemm=True, **kw)
-            names = [r[0] for r in ops.PROFILE]
-            ops.PROFILE = None
-        assert ("hipBLASLt" in names[0]) == (use and B * h * w >= ops.GEMM_1X1_MIN_PIXELS), names
-        assert bool((buf[:, :4] == 3).all()) and bool((buf[:, 4 + co:] == 3).all())
-        outs[use] = buf[:, 4:4 + co].clone()
-        assert rel_err(outs[use], ref.detach()) < 1e-5, use
-    assert rel_err(outs[True], outs[False]) < 1e-5
+    monkeypatch.setattr(ops, "USE_PW_1X1", False)   # (default: the hand-written pointwise GEMM, tested below)
+    with torch.inference_mode():
+        buf = ops.empty_nhwc(B, co + 8, h, w, DEV).fill_(3.0)      # write into a channel slice of a wider buffer
+        ops.conv2d(x, conv, bn=bn, residual=res, out=buf[:, 4:4 + co], **kw)
+    assert bool((buf[:, :4] == 3).all()) and bool((buf[:, 4 + co:] == 3).all())
+    assert rel_err(buf[:, 4:4 + co], ref.detach()) < 1e-5
 
 
 PW_SHAPES = [  # (B, Cin, Cout, h, w, act, residual, gate)

@@ -1,6 +1,6 @@
 """Run-to-run determinism of the whole hot path with DEFAULT settings: two fresh processes
 build the same seeded hero model and push the same batch through `DepthModel.forward_tensors`; `depth_pred_s0`, the cost
-volume's `lowest_cost` and the mask must be bit-identical.  r03 could only promise this with SR_GEMM_AUTOTUNE=0 (the
+volume's `lowest_cost` and the mask must be bit-identical.  r03 could only promise this with hipBLASLt's autotuning off (the
 library GEMMs picked their algorithm by timing, per process); since r04 every 1x1 convolution runs the hand-written
 pointwise GEMM (fixed reduction order), the Winograd / direct convolutions and the sweeps never used atomics on the
 forward path, so no switch is involved."""

@@ -3,8 +3,7 @@
 with SR_BENCH_SHARED_GPU=1 (both ranks on cuda:0, rendezvous + result gather over gloo because RCCL refuses two ranks
 on one device).  The stream of 32 keyframes is sharded round-robin (keyframe i -> rank i mod 2), every depth map is
 gathered to rank 0; the gathered [32,1,240,320] tensor must equal, bit for bit and in keyframe order, what ONE rank
-computes for the same stream.  SR_GEMM_AUTOTUNE=0 in all processes: the image-prior encoder's library GEMMs otherwise
-pick their algorithm by timing, per process."""
+computes for the same stream."""
 import json
 import os
 import subprocess
@@ -19,7 +18,7 @@ ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 
 def _run(n, steps, dump, shared):
     env = {k: v for k, v in os.environ.items() if k not in ("WORLD_SIZE", "RANK", "LOCAL_RANK", "MASTER_PORT")}
-    env.update(SR_GEMM_AUTOTUNE="0", SR_BENCH_DUMP=dump, HSA_ENABLE_IPC_MODE_LEGACY="0")
+    env.update(SR_BENCH_DUMP=dump, HSA_ENABLE_IPC_MODE_LEGACY="0")
     if shared:
         env["SR_BENCH_SHARED_GPU"] = "1"
     else:

@@ -3,6 +3,8 @@ against the ctypes signature table (argument count and kinds) and returns succes
 argument packing, output allocation, mask handling, the autograd seams and their bookkeeping -- runs without a GPU.
 No numerics here: the kernels themselves are covered by the `-m gpu` tests."""
 import contextlib
+import gzip
+import json
 import os
 import ctypes
 
@@ -15,13 +17,18 @@ from simplerecon_amd import cost_volume as cv
 B, K, C, H, W, D = 2, 3, 16, 8, 12, 4
 
 
+_BYREF = type(ctypes.byref(ctypes.c_int()))
+
+
 @pytest.fixture
 def stub(monkeypatch):
     class Calls(list):
         prefer_wino = False
+        prefer_wino4 = 0     # the F(4x4) kernel form sr_conv_prefers_wino4 answers
     calls = Calls()
     calls.args = []          # (name, arguments) of every stubbed call
     calls.option_sets = []   # (id, value) of every sr_option_set, forwarded to the real library
+    calls.rc = {}            # entry point -> the code it returns (default 0: success)
 
     class Stream:
         cuda_stream = 0
@@ -35,7 +42,7 @@ def stub(monkeypatch):
             assert len(args) == len(argtypes), (self.name, len(args), len(argtypes))
             for v, t in zip(args, argtypes):
                 if t is ctypes.c_void_p:
-                    assert v is None or isinstance(v, (ctypes.c_void_p, int)), (self.name, type(v))
+                    assert v is None or isinstance(v, (ctypes.c_void_p, int, _BYREF)), (self.name, type(v))
                 elif t is ctypes.c_float:
                     assert isinstance(v, (float, ctypes.c_float)), (self.name, type(v))
                 else:
@@ -44,9 +51,19 @@ def stub(monkeypatch):
             calls.args.append((self.name, args))
             if self.name == "sr_conv_prefers_wino":
                 return int(calls.prefer_wino)
+            if self.name == "sr_conv_prefers_wino4":
+                return calls.prefer_wino4
+            if self.name in ("sr_pw_conv_plan", "sr_pw_conv_tiled_plan"):
+                # (tile variant, K split) through the two out-pointers; the tiled plan splits K only when it may
+                plan = (2, 1) if self.name == "sr_pw_conv_plan" else (1, 4) if args[3] else (3, 1)
+                args[-2]._obj.value, args[-1]._obj.value = plan
+            if self.name == "sr_wino_kernel_name":
+                return ("sr_wino_kernel<%d, %s, %s>" % (args[3], *("true" if a else "false" for a in args[5:]))).encode()
+            if self.name == "sr_conv_kernel_name":
+                return ("sr_conv_kernel<%s>" % ", ".join(map(str, args))).encode()
             if res is ctypes.c_char_p:
                 return b"stub_kernel"
-            return 4096 if res is ctypes.c_size_t else 0
+            return 4096 if res is ctypes.c_size_t else calls.rc.get(self.name, 0)
 
     real = _lib.lib()   # (the option table is host-only code: those calls go to the real library, GPU or not)
 
@@ -350,3 +367,111 @@ def test_batchnorm_layer_cache_sees_direct_mutations_of_modules():
     bn = nn.BatchNorm2d(2)                           # a batch-norm layer as the root of the query
     assert A.any_batchnorm_training(bn)
     assert not A.any_batchnorm_training(bn.eval())
+
+
+# ---- ops.conv2d dispatch, pinned --------------------------------------------------------------------------------------
+# Which library entry points ops.conv2d calls (in order, with every non-pointer argument), and the ops.PROFILE records it
+# appends, over a grid of layer shapes, tensor layouts and library answers -- including SR_ERR_UNSUPPORTED (2) injected on
+# each entry point a case falls back from, and a hard error (1) on the first one.  Recorded in
+# tests/golden/conv2d_dispatch.json.gz; a case that raises pins its exception instead of its records.
+_GOLDEN_DISPATCH = os.path.join(os.path.dirname(os.path.abspath(__file__)), "golden", "conv2d_dispatch.json.gz")
+
+
+def _dispatch_cases():
+    answers = [(False, 0, ""), (True, 0, ""), (True, 1, ""), (True, 3, ""), (True, 0, "f16"), (True, 0, "bf16")]
+    for k in (1, 3):
+        for s in (1, 2):
+            for pad in ("zeros", "replicate", "tf_same"):
+                pw = k == 1 and s == 1 and pad != "replicate"   # cases the pointwise kernels may take
+                for aligned in (True, False):
+                    for out_slice in (False, True):
+                        for res in (False, True):
+                            for gate in ((False, True) if k == 1 else (False,)):
+                                for wino, w4, split in (answers if (k, s) == (3, 1) else answers[:1]):
+                                    for tiled in ((False, True) if pw else (False,)):
+                                        for pw1x1 in ((True, False) if pw else (True,)):
+                                            yield (k, s, pad, aligned, out_slice, res, gate, wino, w4, split, tiled, pw1x1)
+
+
+def _dispatch_trace(stub, monkeypatch, case, rc):
+    """(calls, records or the exception) of one ops.conv2d call, with and without ops.PROFILE."""
+    from torch import nn
+
+    from simplerecon_amd import ops
+    k, s, pad, aligned, out_slice, res, gate, wino, w4, split, tiled, pw1x1 = case
+    b, ci, co, h, w = 2, 8, 12, 8, 12
+    stub.prefer_wino, stub.prefer_wino4, stub.rc = wino, w4, rc
+    _lib.set_option("SR_WINO_SPLIT", split)
+    monkeypatch.setattr(ops, "PW_TILED_MIN_ROWS", 1 if tiled else 100000)
+    monkeypatch.setattr(ops, "USE_PW_1X1", pw1x1)
+    trace = {}
+    for profiled in (False, True):
+        ops._SHAPE_QUERIES.clear()
+        conv = nn.Conv2d(ci, co, k, stride=s, padding=k // 2, padding_mode="zeros" if pad == "tf_same" else pad)
+        bn = nn.BatchNorm2d(co).eval()
+        x = torch.zeros(b, h, w, ci + 3)[..., 1:1 + ci].permute(0, 3, 1, 2) if not aligned else \
+            torch.zeros(b, ci, h, w).contiguous(memory_format=torch.channels_last)
+        ho, wo = -(-h // s), -(-w // s)
+        out = torch.zeros(b, ho, wo, co + 8)[..., 4:4 + co].permute(0, 3, 1, 2) if out_slice else None
+        kw = dict(residual=torch.zeros(b, co, ho, wo).contiguous(memory_format=torch.channels_last), act="silu") if res \
+            else dict(leaky=0.1)
+        if gate:
+            kw["gate"] = torch.ones(b, ci)
+        prof = [] if profiled else None
+        monkeypatch.setattr(ops, "PROFILE", prof)
+        del stub[:], stub.args[:]
+        try:
+            with torch.no_grad():
+                ops.conv2d(x, conv, out=out, bn=bn, tf_same=pad == "tf_same", **kw)
+            if profiled:
+                trace["records"] = [[n, f, list(shape), ex] for n, f, _, _, shape, ex in prof]
+        except (ValueError, _lib.HipLibraryError) as e:
+            trace["raises"] = f"{type(e).__name__}: {e}"
+        argtypes = lambda n: _lib.SIGNATURES[n][1]
+        # (profiled: without the queries behind a record's name and executed FLOPs -- the records pin what they answered)
+        trace["calls_profiled" if profiled else "calls"] = [
+            [n] + [("p" if v is not None else None) if t is ctypes.c_void_p else
+                   round(v.value if isinstance(v, ctypes.c_float) else v, 6) for v, t in zip(a, argtypes(n))]
+            for n, a in stub.args if not (profiled and n.endswith(("_kernel_name", "_plan")))]
+    return trace
+
+
+def _dispatch_traces(stub, monkeypatch):
+    class Event:   # (torch.cuda.Event without a GPU: PROFILE only keeps them)
+        def __init__(self, **kw):
+            pass
+
+        def record(self, *a):
+            pass
+    from simplerecon_amd import ops
+    monkeypatch.setattr(torch.cuda, "Event", Event)
+    monkeypatch.setattr(ops, "_PACK_EVENTS", {})
+    traces = {}
+    saved = _lib.get_option("SR_WINO_SPLIT")
+    try:
+        for case in _dispatch_cases():
+            cid = "-".join(map(str, case))
+            rc = {}
+            for step in range(6):
+                t = _dispatch_trace(stub, monkeypatch, case, dict(rc))
+                traces[f"{cid}/rc2x{step}"] = t
+                launched = [c[0] for c in t["calls"] if c[0].endswith("_fwd")]
+                if step == 0 and launched:
+                    traces[f"{cid}/rc1"] = _dispatch_trace(stub, monkeypatch, case, {launched[0]: 1})
+                if "raises" in t or not launched or launched[-1] in rc:
+                    break
+                rc[launched[-1]] = 2   # the entry point that served the call now answers SR_ERR_UNSUPPORTED
+    finally:
+        _lib.set_option("SR_WINO_SPLIT", saved)
+    return json.loads(json.dumps(traces))
+
+
+def test_conv2d_dispatch_is_pinned(stub, monkeypatch):
+    """ops.conv2d picks the same kernels, falls back in the same order and writes the same PROFILE records (name, algorithmic
+    and executed FLOPs, shape) as recorded in tests/golden/conv2d_dispatch.json.gz."""
+    got = _dispatch_traces(stub, monkeypatch)
+    with gzip.open(_GOLDEN_DISPATCH, "rt") as f:
+        want = json.load(f)
+    assert sorted(got) == sorted(want)
+    for cid in want:
+        assert got[cid] == want[cid], cid
