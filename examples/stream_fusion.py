@@ -1,9 +1,10 @@
 """End-to-end streaming example on synthetic data: posed frames -> online keyframe / source selection
 (simplerecon_amd.keyframes) -> DepthModel.forward (image-prior + matching encoders, plane-sweep cost volume, cost-volume
-encoder and UNet++ decoder, all on HIP kernels) -> TSDF fusion of the predicted depth (simplerecon_amd.tsdf).  It mirrors
-what the reference's test.py does per scan (test.py:210-410) without datasets, checkpoints or mesh export.
+encoder and UNet++ decoder, all on HIP kernels) -> TSDF fusion of the predicted depth (simplerecon_amd.tsdf) -> with
+--mesh, marching cubes on the GPU and a PLY file.  It mirrors what the reference's test.py does per scan
+(test.py:210-410) without datasets or checkpoints.
 
-    python examples/stream_fusion.py [--frames 120] [--height 192] [--width 256]
+    python examples/stream_fusion.py [--frames 120] [--height 192] [--width 256] [--mesh out.ply]
 
 Weights are random, so the depth maps are meaningless -- the point is the data flow and the API.
 """
@@ -44,7 +45,7 @@ def camera_path(n, seed=0):
     return out
 
 
-def run(frames=120, height=192, width=256, views=8, device="cuda:0", verbose=True):
+def run(frames=120, height=192, width=256, views=8, device="cuda:0", verbose=True, mesh_path=None):
     opts = dm.default_options(image_width=width, image_height=height, model_num_views=views)
     model = dm.DepthModel(opts)
     for i, m in enumerate((model.encoder, model.matching_model, model.cost_volume_net, model.depth_decoder,
@@ -88,6 +89,11 @@ def run(frames=120, height=192, width=256, views=8, device="cuda:0", verbose=Tru
     touched = int((vol.tsdf_weights > 0).sum())
     if verbose:
         print(f"{frames} frames -> {predicted} keyframes predicted and fused; TSDF {tuple(vol.shape)}: {touched} voxels touched")
+    if mesh_path:
+        fuser.export_mesh(mesh_path)   # test.py:405-410
+        if verbose:
+            mesh = fuser.get_mesh()
+            print(f"mesh: {mesh.vertices.shape[0]} vertices, {mesh.faces.shape[0]} triangles -> {mesh_path}")
     return predicted, touched
 
 
@@ -96,5 +102,6 @@ if __name__ == "__main__":
     ap.add_argument("--frames", type=int, default=120)
     ap.add_argument("--height", type=int, default=192)
     ap.add_argument("--width", type=int, default=256)
+    ap.add_argument("--mesh", default=None, help="write the fused surface to this .ply file")
     a = ap.parse_args()
-    run(a.frames, a.height, a.width)
+    run(a.frames, a.height, a.width, mesh_path=a.mesh)

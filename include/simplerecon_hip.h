@@ -468,6 +468,44 @@ int sr_tsdf_integrate_fwd(void* tsdf_values, void* tsdf_weights, const void* vox
                           float min_depth, float max_depth, float depth_range, float truncation, float maxW,
                           void* stream);
 
+/* ------------------------------------------------------------- mesh extraction -------
+ *
+ * Marching cubes on a fused TSDF volume (the reference's TSDF.to_mesh, tools/tsdf.py:128-156, runs skimage on the host
+ * with level = 0, values clamped to [-1, 1] and allow_degenerate = False).  Output: an indexed mesh with shared vertices.
+ *
+ *  tsdf_values : [X,Y,Z] fp16, contiguous (z fastest), X, Y, Z >= 2.  Z % 8 == 0 with 16-byte alignment takes 16-byte
+ *                loads; other shapes a scalar path with the same results.
+ *
+ * Rules (tests/mesh_oracle.py implements them in numpy):
+ *  - Corners: fp16 -> fp32, clamped to [-1, 1]; a corner is below if v < level, else above.  An edge with a NaN endpoint
+ *    has no vertex; a cube with a NaN corner emits nothing.
+ *  - Vertices: voxel (i,j,k) owns its edges toward +x, +y, +z.  An edge with endpoints on different sides has one vertex
+ *    at p0 + t along its axis, t = (level - v0) / (v1 - v0), v0 the lower-index endpoint.  Vertices are numbered in
+ *    linear voxel order, then x, y, z edge order (independent of the schedule).
+ *  - Faces of a cube: 2 or 4 crossing edges.  With 4 (above corners a, c on one diagonal, below b, d on the other, all
+ *    minus level) the above corners are joined across the face iff a*c >= b*d (fp32, no FMA): the asymptotic decider.
+ *    It depends on the face's own values only, so neighbouring cubes agree and the mesh has no cracks.
+ *  - Loops: the face segments chain into closed loops, oriented so that triangles wind counter-clockwise seen from the
+ *    above side (face normals point toward increasing TSDF).  Each loop is a fan from its vertex with the smallest global
+ *    index; a triangle is dropped if two of its three voxel-unit positions are bitwise equal.
+ *  - Coordinates: origin + p * scale in fp32 (scale_to_world: the fp16 origin as fp32 and the voxel size; else 0 and 1).
+ *    normals (optional): central-difference gradients of the clamped values at both endpoints (one-sided at the border),
+ *    g0 + t * (g1 - g0), normalised; a zero gradient gives a zero normal.
+ *
+ * Use: sr_mesh_count writes {active voxels, vertices, triangles} as int64 to the device array `totals`[3] and brick
+ * offsets to `count_scratch` (sr_mesh_count_scratch_bytes, 16-byte aligned).  After the host has read the totals,
+ * sr_mesh_emit with the same volume, level and count_scratch, a `list_scratch` of sr_mesh_list_scratch_bytes(active)
+ * bytes (16-byte aligned) writes vertices [V,3] fp32, normals [V,3] fp32 (NULL: none) and faces [F,3] int32.
+ * V or F >= 2^31: SR_ERR_UNSUPPORTED.  The library allocates nothing; no host synchronisation inside either call. */
+size_t sr_mesh_count_scratch_bytes(int X, int Y, int Z);
+size_t sr_mesh_list_scratch_bytes(int64_t active);
+int sr_mesh_count(const void* tsdf_values, int X, int Y, int Z, float level, void* count_scratch,
+                  size_t count_scratch_bytes, int64_t* totals, void* stream);
+int sr_mesh_emit(const void* tsdf_values, int X, int Y, int Z, float level, float origin_x, float origin_y, float origin_z,
+                 float scale, const void* count_scratch, size_t count_scratch_bytes, void* list_scratch,
+                 size_t list_scratch_bytes, int64_t active, int64_t num_vertices, int64_t num_faces, float* vertices,
+                 float* normals, int* faces, void* stream);
+
 /* ------------------------------------------------------ backward (training) -------------
  *
  * Backward of sr_dot_volume_sweep (reference: autograd through CostVolumeManager.build_cost_volume,

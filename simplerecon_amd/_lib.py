@@ -149,6 +149,10 @@ SIGNATURES = {
     "sr_conv3x3_c16_nhwc_fwd": (_i, [_p, _i64, _i, _p, _f, _p, _p, _p, _i64, _i, _i, _i, _i, _i, _i, _i, _f, _p]),
     "sr_tsdf_integrate_fwd": (_i, [_p, _p, _p, _i, _i, _i, _f, _f, _f, _f, _p, _p, _p, _p, _i, _i, _i,
                                    _f, _f, _f, _f, _f, _p]),
+    "sr_mesh_count_scratch_bytes": (_sz, [_i, _i, _i]),
+    "sr_mesh_list_scratch_bytes": (_sz, [_i64]),
+    "sr_mesh_count": (_i, [_p, _i, _i, _i, _f, _p, _sz, _p, _p]),
+    "sr_mesh_emit": (_i, [_p, _i, _i, _i, _f, _f, _f, _f, _f, _p, _sz, _p, _sz, _i64, _i64, _i64, _p, _p, _p, _p]),
 }
 
 

@@ -7,16 +7,98 @@ csrc/sr_tsdf.hip): the fp16 volume is streamed once, every voxel applies the fra
 registers.  The reference instead materialises ~10 [B, N]-sized fp16 temporaries per call (N = voxels) and does a
 masked gather / scatter per frame.  Results are bit-identical to the reference executed on CPU (tests/golden/tsdf_*).
 
-Not provided: mesh extraction (`to_mesh` / `save` need scikit-image marching cubes + trimesh; out of scope) and the
-open3d fuser.  There is no CPU fallback: tensors must live on the GPU.
+Mesh export (`TSDF.extract_mesh` / `TSDF.save`, `OurFuser.export_mesh` / `get_mesh`) runs marching cubes on the GPU
+(`sr_mesh_count` + `sr_mesh_emit`, csrc/sr_mesh.hip) and returns a `TriangleMesh`; the reference copies the volume to the
+host and runs skimage + trimesh there (tools/tsdf.py:128-168).  The surface rules are in include/simplerecon_hip.h.
+
+Not provided: `to_mesh` (its contract is a trimesh.Trimesh) and the open3d fuser.  There is no CPU fallback: tensors
+must live on the GPU.
 """
 import ctypes as C
-from typing import Tuple
+import os
+from typing import Optional, Tuple
 
 import numpy as np
 import torch
 
 from . import _lib
+
+
+class TriangleMesh:
+    """An indexed triangle mesh: `vertices` [V,3] fp32, `faces` [F,3] int32 (counter-clockwise seen from the side of
+    increasing TSDF, i.e. from free space), `normals` [V,3] fp32 unit vectors or None."""
+
+    def __init__(self, vertices: torch.Tensor, faces: torch.Tensor, normals: Optional[torch.Tensor] = None):
+        self.vertices = vertices
+        self.faces = faces
+        self.normals = normals
+
+    def cpu(self):
+        return TriangleMesh(self.vertices.cpu(), self.faces.cpu(), None if self.normals is None else self.normals.cpu())
+
+    def write_ply(self, path):
+        """Binary little-endian PLY: `float x,y,z` (+ `nx,ny,nz`) per vertex and a `list uchar int vertex_indices` face
+        element -- the layout trimesh writes."""
+        v = self.vertices.detach().cpu().numpy().astype("<f4", copy=False).reshape(-1, 3)
+        f = self.faces.detach().cpu().numpy().astype("<i4", copy=False).reshape(-1, 3)
+        names = ["x", "y", "z"]
+        cols = [v]
+        if self.normals is not None:
+            names += ["nx", "ny", "nz"]
+            cols.append(self.normals.detach().cpu().numpy().astype("<f4", copy=False).reshape(-1, 3))
+        vrec = np.empty(len(v), dtype=[(n, "<f4") for n in names])
+        for idx, n in enumerate(names):
+            vrec[n] = cols[idx // 3][:, idx % 3]
+        frec = np.empty(len(f), dtype=[("n", "u1"), ("i", "<i4", (3,))])
+        frec["n"] = 3
+        frec["i"] = f
+        header = ["ply", "format binary_little_endian 1.0", f"element vertex {len(v)}"]
+        header += [f"property float {n}" for n in names]
+        header += [f"element face {len(f)}", "property list uchar int vertex_indices", "end_header"]
+        with open(path, "wb") as fh:
+            fh.write(("\n".join(header) + "\n").encode("ascii"))
+            fh.write(vrec.tobytes())
+            fh.write(frec.tobytes())
+
+
+def marching_cubes(tsdf_values: torch.Tensor, level=0.0, origin=(0.0, 0.0, 0.0), scale=1.0,
+                   compute_normals=True) -> TriangleMesh:
+    """Marching cubes on an fp16 [X,Y,Z] device volume (sr_mesh_count + sr_mesh_emit; rules: include/simplerecon_hip.h,
+    "mesh extraction").  Vertices are origin + voxel index * scale in fp32.  One host synchronisation (the totals)."""
+    vals = tsdf_values
+    if not isinstance(vals, torch.Tensor) or vals.dtype != torch.float16 or vals.dim() != 3:
+        raise TypeError("tsdf_values must be an fp16 [X,Y,Z] tensor")
+    if not vals.is_cuda:
+        raise _lib.HipLibraryError("the TSDF volume lives on the host: call tsdf.cuda() (no CPU fallback)")
+    X, Y, Z = vals.shape
+    if min(X, Y, Z) < 2:
+        raise ValueError(f"marching cubes needs every volume dimension >= 2, got {tuple(vals.shape)}")
+    vals = vals.contiguous()
+    dev = vals.device
+    lib = _lib.lib()
+    f = C.c_float
+    with torch.cuda.device(dev):
+        stream = _lib.stream_ptr(dev)
+        cbytes = lib.sr_mesh_count_scratch_bytes(X, Y, Z)
+        cscratch = torch.empty(cbytes, dtype=torch.uint8, device=dev)
+        totals = torch.empty(3, dtype=torch.int64, device=dev)
+        _lib.check(lib.sr_mesh_count(_lib.ptr(vals), X, Y, Z, f(level), _lib.ptr(cscratch), cbytes, _lib.ptr(totals),
+                                     stream), "sr_mesh_count")
+        active, nv, nf = (int(x) for x in totals.tolist())
+        if nv >= 2 ** 31 or nf >= 2 ** 31:
+            raise _lib.HipLibraryError(f"mesh of {nv} vertices / {nf} faces: int32 face indices cannot address it")
+        lbytes = lib.sr_mesh_list_scratch_bytes(active)
+        lscratch = torch.empty(max(lbytes, 1), dtype=torch.uint8, device=dev)
+        verts = torch.empty((nv, 3), dtype=torch.float32, device=dev)
+        normals = torch.empty((nv, 3), dtype=torch.float32, device=dev) if compute_normals else None
+        faces = torch.empty((nf, 3), dtype=torch.int32, device=dev)
+        ox, oy, oz = (float(o) for o in origin)
+        rc = lib.sr_mesh_emit(_lib.ptr(vals), X, Y, Z, f(level), f(ox), f(oy), f(oz), f(scale), _lib.ptr(cscratch), cbytes,
+                              _lib.ptr(lscratch), lbytes, active, nv, nf, _lib.ptr(verts), _lib.ptr(normals),
+                              _lib.ptr(faces), stream)
+        _lib.check(rc, "sr_mesh_emit")
+        # the scratch buffers go back to torch's caching allocator, which orders their reuse on this stream
+    return TriangleMesh(verts, faces, normals)
 
 
 class TSDF:
@@ -80,12 +162,35 @@ class TSDF:
             self._voxel_coords = self._voxel_coords.cpu()
 
     def to_mesh(self, scale_to_world=True, export_single_mesh=False):
-        raise NotImplementedError("mesh extraction (skimage marching cubes + trimesh, reference tsdf.py:128-160) is "
-                                  "outside this path: take `tsdf_values` / `origin` / `voxel_size` to the reference's "
-                                  "TSDF.to_mesh")
+        raise NotImplementedError("to_mesh returns a trimesh.Trimesh in the reference (tsdf.py:128-156), which is not "
+                                  "available here: use TSDF.extract_mesh (a TriangleMesh on the GPU) or TSDF.save (PLY)")
+
+    def extract_mesh(self, level=0.0, scale_to_world=True, compute_normals=True) -> TriangleMesh:
+        """Marching cubes on the GPU (the reference's to_mesh settings: level 0, values clamped to [-1, 1], no
+        degenerate triangles).  scale_to_world: vertices in world coordinates, float(fp16 origin) + index * voxel_size
+        (as the reference adds its fp16 origin, tsdf.py:147-148); else in voxel units."""
+        if scale_to_world:
+            origin, scale = [float(o) for o in self.origin.float()], float(self.voxel_size)
+        else:
+            origin, scale = (0.0, 0.0, 0.0), 1.0
+        return marching_cubes(self.tsdf_values, level=level, origin=origin, scale=scale, compute_normals=compute_normals)
 
     def save(self, savepath, filename, save_mesh=True):
-        raise NotImplementedError("see to_mesh")
+        """Saves the mesh as `filename` with .bin replaced by .ply under `savepath` (reference tsdf.py:158-168).  Like
+        the reference, the volume is on the host afterwards; a volume already on the host is meshed from a copy on the
+        current GPU."""
+        mesh = None
+        if save_mesh:
+            if self.tsdf_values.is_cuda:
+                mesh = self.extract_mesh()
+            else:
+                dev = torch.device("cuda", torch.cuda.current_device())
+                copy = TSDF(None, self.tsdf_values.to(dev), self.tsdf_weights, self.voxel_size, self.origin)
+                mesh = copy.extract_mesh()
+        self.cpu()
+        os.makedirs(savepath, exist_ok=True)
+        if mesh is not None:
+            mesh.write_ply(os.path.join(savepath, filename).replace(".bin", ".ply"))
 
 
 class TSDFFuser:
@@ -176,8 +281,8 @@ class TSDFFuser:
 
 
 class OurFuser:
-    """The fuser behind `--depth_fuser ours` (reference tools/fusers_helper.py:25-83) without mesh I/O: a dense TSDF
-    over the given bounds (default: the reference's +-10 m cube when no ground-truth mesh limits the extent)."""
+    """The fuser behind `--depth_fuser ours` (reference tools/fusers_helper.py:25-83): a dense TSDF over the given bounds
+    (default: the reference's +-10 m cube when no ground-truth mesh limits the extent)."""
 
     def __init__(self, gt_path=None, fusion_resolution=0.04, max_fusion_depth=3, fuse_color=False, bounds=None,
                  device="cuda"):
@@ -193,3 +298,16 @@ class OurFuser:
     def fuse_frames(self, depths_b1hw, K_b44, cam_T_world_b44, color_b3hw=None):
         self.tsdf_fuser_pred.integrate_depth(depth_b1hw=depths_b1hw.half(), cam_T_world_T_b44=cam_T_world_b44.half(),
                                              K_b44=K_b44.half())
+
+    def get_mesh(self, export_single_mesh=True, convert_to_trimesh=True) -> TriangleMesh:
+        """The fused surface as a `TriangleMesh` on the GPU (not a trimesh object: trimesh is not a dependency).  The
+        output is always one mesh, so `export_single_mesh` changes nothing; `convert_to_trimesh` is accepted for the
+        reference's signature (fusers_helper.py:79-81) and ignored."""
+        return self.tsdf_fuser_pred.tsdf.extract_mesh()
+
+    def export_mesh(self, path, export_single_mesh=True):
+        """Writes the fused surface to `path` as binary PLY (reference fusers_helper.py:72-77, which lets trimesh pick
+        the format from the extension: only .ply is written here).  `export_single_mesh` changes nothing."""
+        if not str(path).lower().endswith(".ply"):
+            raise ValueError(f"export_mesh writes PLY only, got {path!r}")
+        self.get_mesh(export_single_mesh=export_single_mesh).write_ply(path)
