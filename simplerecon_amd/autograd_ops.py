@@ -16,7 +16,7 @@ import torch
 from torch import nn
 
 from . import _lib
-from .ops import _is_nhwc_view, _strides, _workspace, as_nhwc, empty_nhwc
+from .ops import _is_nhwc_view, _pack, _strides, _workspace, as_nhwc, empty_nhwc
 
 
 # torch.autocast compatibility (the reference trains under 16-bit autocast, options.py:100-101, train.py:132): every
@@ -234,13 +234,11 @@ def _conv_raw_io(x, weight, bias, stride, residual, slope, pads):
     sl = C.c_float(-1.0 if slope is None else float(slope))
     with _lib.on_device(x.device):
         if wino:
-            wp = torch.empty(lib.sr_wino_packed_weight_floats(co, ci), dtype=torch.float32, device=x.device)
-            _lib.check(lib.sr_wino_pack_weights(_lib.ptr(wd), co, ci, _lib.ptr(wp), st), "sr_wino_pack_weights")
+            wp = _pack("wino", wd)
             rc = lib.sr_conv3x3_wino_io_nhwc_fwd(_lib.ptr(x), isb, isp, _lib.ptr(wp), _lib.ptr(bd), _lib.ptr(residual), rsb, rsp,
                                                  _lib.ptr(out), osb, osp, b, h, w, ci, co, sl, _IO_CODE[dt], st)
         else:
-            wp = torch.empty(lib.sr_conv_packed_weight_floats(co, ci, 1), dtype=torch.float32, device=x.device)
-            _lib.check(lib.sr_conv_pack_weights(_lib.ptr(wd), co, ci, 1, _lib.ptr(wp), st), "sr_conv_pack_weights")
+            wp = _pack("conv", wd)
             rc = lib.sr_pw_conv_io_nhwc_fwd(_lib.ptr(x), isb, isp, _lib.ptr(wp), _lib.ptr(bd), _lib.ptr(residual), rsb, rsp,
                                             _lib.ptr(out), osb, osp, b, h * w, ci, co, sl, _IO_CODE[dt], st)
     _lib.check(rc, "conv forward (16-bit I/O)")
@@ -267,12 +265,7 @@ def _conv_raw(x, weight, bias, stride, residual=None, slope=None, pads=None):
     use_wino = pads is None and stride == 1 and k == 3 and bool(lib.sr_conv_prefers_wino(b, h, w, ci, co, k, stride))
     st = _lib.stream_ptr(x.device)
     with _lib.on_device(x.device):
-        if use_wino:
-            wp = torch.empty(lib.sr_wino_packed_weight_floats(co, ci), dtype=torch.float32, device=x.device)
-            _lib.check(lib.sr_wino_pack_weights(_lib.ptr(wd), co, ci, _lib.ptr(wp), st), "sr_wino_pack_weights")
-        else:
-            wp = torch.empty(lib.sr_conv_packed_weight_floats(co, ci, k), dtype=torch.float32, device=x.device)
-            _lib.check(lib.sr_conv_pack_weights(_lib.ptr(wd), co, ci, k, _lib.ptr(wp), st), "sr_conv_pack_weights")
+        wp = _pack("wino" if use_wino else "conv", wd)
         isb, isp = _strides(x)
         osb, osp = _strides(out)
         if residual is not None:

@@ -14,44 +14,64 @@ from torch import nn
 
 from . import _lib
 
-# When set to a list, every conv launch appends (kernel symbol, algorithmic FLOPs, start event, end event):
-# bench.py uses it to time the dominant kernel with HIP events on the launch stream.
+# When set to a list, every timed launch (_timed) appends (kernel symbol, algorithmic FLOPs, start event, end event, shape,
+# executed FLOPs): bench.py uses it to time the dominant kernel with HIP events on the launch stream.
 PROFILE = None
 
-_PACKED = weakref.WeakKeyDictionary()  # nn.Conv2d -> (weight version, data_ptr, packed tensor)
+# Packed weights (and the other tensors derived from a module's parameters), per module: {cache tag: [state key, payload,
+# pack fence]}.  They are produced on whichever stream made the first call; a consumer on ANOTHER stream (the sub-batch
+# streams of DepthModel.hot_path, the image-prior side stream) must not start before that work finished.  The fence is
+# (event recorded behind the pack, its stream handle, device), or None once the event has completed.
+_PACKED = weakref.WeakKeyDictionary()
+_NO_ENTRIES = {}   # (read only: what a module without entries looks up)
 
-# Packed weights are produced by a kernel on whichever stream made the first call; a consumer on ANOTHER stream (the
-# sub-batch streams of DepthModel.hot_path, the image-prior side stream) must not start before that kernel finished.
-# (module, cache tag) -> (event recorded behind the pack kernel, its stream); the entry is dropped once the event completed.
-_PACK_EVENTS = {}
+
+def _cached(mod, tag, key, build, *args):
+    """build(*args), cached as `mod`'s `tag` entry until `key` (its _state_key and anything else the payload depends on)
+    changes.  Runs once per launch: a hit is one lookup and one key comparison."""
+    e = _PACKED.get(mod, _NO_ENTRIES).get(tag)
+    if e is not None and e[0] == key:
+        if e[2] is not None:
+            _await_pack(e)
+        return e[1]
+    payload = build(*args)
+    fence = None
+    # weights are packed during warm-up, never inside a capture (graph.GraphedCallable warms up first)
+    if _lib.cuda_available() and not _lib.capturing():
+        device = mod.weight.device
+        st = torch.cuda.current_stream(device)
+        ev = torch.cuda.Event()
+        ev.record(st)
+        fence = (ev, st.cuda_stream, device)
+    _PACKED.setdefault(mod, {})[tag] = [key, payload, fence]
+    return payload
 
 
-def _packed_here(mod, tag, device):
-    if device.type != "cuda" or not _lib.cuda_available():
-        return
-    st = torch.cuda.current_stream(device)
+def _await_pack(e):
     if _lib.capturing():
-        return  # weights are packed during warm-up, never inside a capture (graph.GraphedCallable warms up first)
-    ev = torch.cuda.Event()
-    ev.record(st)
-    _PACK_EVENTS[(id(mod), tag)] = (ev, st.cuda_stream, weakref.ref(mod))
-
-
-def _await_packed(mod, tag, device):
-    if not _PACK_EVENTS:
         return
-    hit = _PACK_EVENTS.get((id(mod), tag))
-    if hit is None or hit[2]() is not mod:
-        return
-    if _lib.capturing():
-        return
-    ev, stream_ptr, _ = hit
+    ev, stream, device = e[2]
     if ev.query():
-        del _PACK_EVENTS[(id(mod), tag)]
+        e[2] = None
         return
     st = torch.cuda.current_stream(device)
-    if st.cuda_stream != stream_ptr:
+    if st.cuda_stream != stream:
         st.wait_event(ev)
+
+
+# the leading weight dimensions the library's sr_<kind>_packed_weight_floats / sr_<kind>_pack_weights take
+_PACK_DIMS = {"conv": 3, "wino": 2, "wino4": 2, "stem": 1, "conv3x3_c16": 2}
+
+
+def _pack(kind, w):
+    """The library's `kind` packing of the contiguous fp32 weight `w` ([Co, Ci, k, k]) into a new tensor (uncached)."""
+    lib = _lib.lib()
+    dims = w.shape[:_PACK_DIMS[kind]]
+    packed = torch.empty(getattr(lib, f"sr_{kind}_packed_weight_floats")(*dims), dtype=torch.float32, device=w.device)
+    with _lib.on_device(w.device):
+        rc = getattr(lib, f"sr_{kind}_pack_weights")(_lib.ptr(w), *dims, _lib.ptr(packed), _lib.stream_ptr(w.device))
+    _lib.check(rc, f"sr_{kind}_pack_weights")
+    return packed
 
 
 def empty_nhwc(b, c, h, w, device):
@@ -163,25 +183,17 @@ def _check_conv(conv):
         raise _lib.HipLibraryError(f"unsupported Conv2d configuration for the HIP path: {conv}")
 
 
-def packed_weight(conv: nn.Conv2d, bn=None):
-    """(packed weight, bias) for the direct kernel; cached until a parameter changes."""
-    key = _state_key(conv, bn)
-    hit = _PACKED.get(conv)
-    if hit is not None and hit[0] == key:
-        _await_packed(conv, "direct", hit[1].device)
-        return hit[1], hit[2]
+def _pack_folded(kind, conv, bn):
+    """(the `kind` packing of conv's weight with `bn` folded in, bias)."""
     _lib.require_device_f32("conv weight", conv.weight)
     _check_conv(conv)
-    lib = _lib.lib()
     w, bias = _effective_weight(conv, bn)
-    co, ci, k, _ = w.shape
-    packed = torch.empty(lib.sr_conv_packed_weight_floats(co, ci, k), dtype=torch.float32, device=w.device)
-    with _lib.on_device(w.device):
-        rc = lib.sr_conv_pack_weights(_lib.ptr(w), co, ci, k, _lib.ptr(packed), _lib.stream_ptr(w.device))
-    _lib.check(rc, "sr_conv_pack_weights")
-    _packed_here(conv, "direct", w.device)
-    _PACKED[conv] = (key, packed, bias)
-    return packed, bias
+    return _pack(kind, w), bias
+
+
+def packed_weight(conv: nn.Conv2d, bn=None):
+    """(packed weight, bias) for the direct kernel; cached until a parameter changes."""
+    return _cached(conv, "direct", _state_key(conv, bn), _pack_folded, "conv", conv, bn)
 
 
 # 1x1 / stride-1 convolutions run on the hand-written pointwise MFMA GEMM of csrc/sr_pw.hip (deterministic, r04); False sends
@@ -195,7 +207,8 @@ PW_TILED = os.environ.get("SR_PW_TILED", "auto")
 PW_TILED_MIN_ROWS = 100000
 
 
-_PACKED_LIN = weakref.WeakKeyDictionary()  # nn.Linear -> (weight version, data_ptr, packed tensor)
+def _pack_linear(lin):
+    return _pack("conv", lin.weight.detach().reshape(lin.out_features, lin.in_features, 1, 1).contiguous())
 
 
 def linear(x, lin: nn.Linear, leaky=None):
@@ -211,29 +224,15 @@ def linear(x, lin: nn.Linear, leaky=None):
     out = torch.empty((m, cout), dtype=torch.float32, device=x.device)
     if m == 0:
         return out.view(*x.shape[:-1], cout)
-    w = lin.weight
-    hit = _PACKED_LIN.get(lin)
-    lib = _lib.lib()
-    if hit is not None and hit[0] == w._version and hit[1] == w.data_ptr():
-        wp = hit[2]
-        _await_packed(lin, "linear", w.device)
-    else:
-        wp = torch.empty(lib.sr_conv_packed_weight_floats(cout, cin, 1), dtype=torch.float32, device=w.device)
-        with _lib.on_device(w.device):
-            _lib.check(lib.sr_conv_pack_weights(_lib.ptr(w.detach().contiguous()), cout, cin, 1, _lib.ptr(wp),
-                                                _lib.stream_ptr(w.device)), "sr_conv_pack_weights")
-        _packed_here(lin, "linear", w.device)
-        _PACKED_LIN[lin] = (w._version, w.data_ptr(), wp)
+    wp = _cached(lin, "linear", _state_key(lin, None), _pack_linear, lin)
     bias = lin.bias.detach() if lin.bias is not None else None
+    lib = _lib.lib()
     with _lib.on_device(x.device):
         rc = lib.sr_conv2d_nhwc_fwd(_lib.ptr(x2), m * cin, cin, _lib.ptr(wp), _lib.ptr(bias), None, 0, 0,
                                     _lib.ptr(out), m * cout, cout, 1, 1, m, cin, cout, 1, 1,
                                     C.c_float(-1.0 if leaky is None else float(leaky)), _lib.stream_ptr(x.device))
     _lib.check(rc, "sr_conv2d_nhwc_fwd (linear)")
     return out.view(*x.shape[:-1], cout)
-
-
-_PACKED_WINO = weakref.WeakKeyDictionary()  # nn.Conv2d -> (weight version, data_ptr, Winograd-packed tensor)
 
 
 def wino_split_mode():
@@ -245,24 +244,9 @@ def wino_split_mode():
 def packed_wino_weight(conv: nn.Conv2d, bn=None):
     """(Winograd-packed weight U = G g G^T, bias); cached until a parameter changes."""
     key = (_state_key(conv, bn), wino_split_mode())   # (the fenced split-precision variant packs 16-bit pieces)
-    hit = _PACKED_WINO.get(conv)
-    if hit is not None and hit[0] == key:
-        _await_packed(conv, "wino", hit[1].device)
-        return hit[1], hit[2]
-    _check_conv(conv)
-    lib = _lib.lib()
-    w, bias = _effective_weight(conv, bn)
-    co, ci = w.shape[:2]
-    packed = torch.empty(lib.sr_wino_packed_weight_floats(co, ci), dtype=torch.float32, device=w.device)
-    with _lib.on_device(w.device):
-        rc = lib.sr_wino_pack_weights(_lib.ptr(w), co, ci, _lib.ptr(packed), _lib.stream_ptr(w.device))
-    _lib.check(rc, "sr_wino_pack_weights")
-    _packed_here(conv, "wino", w.device)
-    _PACKED_WINO[conv] = (key, packed, bias)
-    return packed, bias
+    return _cached(conv, "wino", key, _pack_folded, "wino", conv, bn)
 
 
-_PACKED_WINO4 = weakref.WeakKeyDictionary()  # nn.Conv2d -> (state key, F(4x4, 3x3)-packed tensor, bias)
 # Which 3x3 / stride-1 layers take the F(4x4, 3x3) kernel (csrc/sr_wino4.hip): "1" (default) = the library's rule
 # (sr_conv_prefers_wino4: the full-resolution layers at batch 8), "0" = none, "2" = every layer it applies to (tests).
 # Read once, handed to the library as an argument.
@@ -274,22 +258,7 @@ WINO4_VARIANT = int(os.environ.get("SR_WINO4_VARIANT", "0"))
 
 def packed_wino4_weight(conv: nn.Conv2d, bn=None):
     """(F(4x4, 3x3)-packed weight U = G g G^T, bias); cached until a parameter changes."""
-    key = _state_key(conv, bn)
-    hit = _PACKED_WINO4.get(conv)
-    if hit is not None and hit[0] == key:
-        _await_packed(conv, "wino4", hit[1].device)
-        return hit[1], hit[2]
-    _check_conv(conv)
-    lib = _lib.lib()
-    w, bias = _effective_weight(conv, bn)
-    co, ci = w.shape[:2]
-    packed = torch.empty(lib.sr_wino4_packed_weight_floats(co, ci), dtype=torch.float32, device=w.device)
-    with _lib.on_device(w.device):
-        rc = lib.sr_wino4_pack_weights(_lib.ptr(w), co, ci, _lib.ptr(packed), _lib.stream_ptr(w.device))
-    _lib.check(rc, "sr_wino4_pack_weights")
-    _packed_here(conv, "wino4", w.device)
-    _PACKED_WINO4[conv] = (key, packed, bias)
-    return packed, bias
+    return _cached(conv, "wino4", _state_key(conv, bn), _pack_folded, "wino4", conv, bn)
 
 
 # Pure functions of the layer shape inside the C library (launch-plan choices): asked once per shape, not once per launch.
@@ -420,24 +389,36 @@ def _aligned16(t, sb, sp):
     return t is None or (t.data_ptr() % 16 == 0 and sp % 4 == 0 and sb % 4 == 0)
 
 
-def _launch(x, shape, entry, fallback, describe, fn, *args):
-    """fn(*args) on x's device -> the library's rc; raises for any error but SR_ERR_UNSUPPORTED with a `fallback` behind it
-    (`entry`: the call's name in the message).  With PROFILE on, two timing events bracket the launch and a launch that
-    succeeded appends (kernel name, algorithmic FLOPs, start event, end event, shape, executed FLOPs); describe() -> (kernel
-    name, executed FLOPs or None) is only asked then."""
+def _timed(device, record, fn, *args):
+    """fn(*args) on `device` -> the library's rc.  With PROFILE on, two timing events bracket the launch and a launch that
+    succeeded appends (kernel name, algorithmic FLOPs, start event, end event, shape, executed FLOPs); record() -> (kernel
+    name, algorithmic FLOPs, shape, executed FLOPs or None) is only asked then."""
     prof = PROFILE
-    with _lib.on_device(x.device):
+    with _lib.on_device(device):
         if prof is None:
+            return fn(*args)
+        ev0, ev1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+        ev0.record()
+        rc = fn(*args)
+        ev1.record()
+        if rc == 0:
+            name, flops, shape, executed = record()
+            prof.append((name, flops, ev0, ev1, shape, executed))
+    return rc
+
+
+def _launch(x, shape, entry, fallback, describe, fn, *args):
+    """A conv launch through _timed; raises for any error but SR_ERR_UNSUPPORTED with a `fallback` behind it (`entry`: the
+    call's name in the message).  describe() -> (kernel name, executed FLOPs or None) completes the PROFILE record."""
+    if PROFILE is None:   # (skips _timed's call frame: a quarter microsecond per launch on a host-bound batch-1 path)
+        with _lib.on_device(x.device):
             rc = fn(*args)
-        else:
-            ev0, ev1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
-            ev0.record()
-            rc = fn(*args)
-            ev1.record()
-            if rc == 0:
-                b, ci, h, w, co, k, s, ho, wo, _ = shape
-                name, executed = describe()
-                prof.append((name, 2.0 * b * ho * wo * co * ci * k * k, ev0, ev1, shape, executed))
+    else:
+        def record():
+            b, ci, h, w, co, k, s, ho, wo, _ = shape
+            name, executed = describe()
+            return name, 2.0 * b * ho * wo * co * ci * k * k, shape, executed
+        rc = _timed(x.device, record, fn, *args)
     if rc != 0 and (rc != _lib.ERR_UNSUPPORTED or not fallback):
         _lib.check(rc, entry)
     return rc
@@ -596,8 +577,7 @@ def copy_into(dst_view, src):
 
 # ---------------------------------------------------------------- matching encoder ops --
 
-_PACKED_STEM = weakref.WeakKeyDictionary()  # nn.Conv2d -> (state key, packed weight, scale, shift)
-_WORKSPACES = {}                            # (device, tag) -> scratch tensor (grown on demand)
+_WORKSPACES = {}   # (device, tag) -> scratch tensor (grown on demand)
 
 
 def _workspace(device, tag, nbytes):
@@ -614,6 +594,20 @@ def _workspace(device, tag, nbytes):
     return ws
 
 
+def _pack_stem(conv, bn):
+    """(packed weight, per-channel scale or None, shift or None) of the stem with `bn` and conv's bias folded into the
+    epilogue."""
+    wp = _pack("stem", conv.weight.detach().contiguous())
+    scale = shift = None
+    if bn is not None:
+        scale, shift = bn_affine(bn)
+    if conv.bias is not None:
+        cb = conv.bias.detach()
+        shift = (cb if scale is None else cb * scale) + (0 if shift is None else shift)
+        shift = shift.contiguous()
+    return wp, scale, shift
+
+
 def stem7x7(image, conv: nn.Conv2d, bn=None, leaky=0.0, out=None):
     """act(bn(conv7x7_s2_p3(image))): encoder.conv1 + bn1 + relu of the ResNet stem (reference networks.py:176-179).
     image [B,3,H,W], any strides; returns channels-last [B,64,H/2,W/2] (or writes it into `out`, e.g. a batch slice
@@ -627,27 +621,7 @@ def stem7x7(image, conv: nn.Conv2d, bn=None, leaky=0.0, out=None):
     if image.dim() != 4 or image.shape[1] != 3:
         raise ValueError(f"stem expects [B,3,H,W], got {tuple(image.shape)}")
     _lib.require_device_f32("stem weight", conv.weight)
-    lib = _lib.lib()
-    key = _state_key(conv, bn)
-    hit = _PACKED_STEM.get(conv)
-    if hit is None or hit[0] != key:
-        wp = torch.empty(lib.sr_stem_packed_weight_floats(64), dtype=torch.float32, device=conv.weight.device)
-        with _lib.on_device(conv.weight.device):
-            _lib.check(lib.sr_stem_pack_weights(_lib.ptr(conv.weight.detach().contiguous()), 64, _lib.ptr(wp),
-                                                _lib.stream_ptr(conv.weight.device)), "sr_stem_pack_weights")
-        scale = shift = None
-        if bn is not None:
-            scale, shift = bn_affine(bn)
-        if conv.bias is not None:
-            cb = conv.bias.detach()
-            shift = (cb if scale is None else cb * scale) + (0 if shift is None else shift)
-            shift = shift.contiguous()
-        hit = (key, wp, scale, shift)
-        _packed_here(conv, "stem", conv.weight.device)
-        _PACKED_STEM[conv] = hit
-    else:
-        _await_packed(conv, "stem", conv.weight.device)
-    _, wp, scale, shift = hit
+    wp, scale, shift = _cached(conv, "stem", _state_key(conv, bn), _pack_stem, conv, bn)
     b, _, h, w = image.shape
     ho, wo = (h - 1) // 2 + 1, (w - 1) // 2 + 1
     if out is None:
@@ -658,18 +632,11 @@ def stem7x7(image, conv: nn.Conv2d, bn=None, leaky=0.0, out=None):
         return out
     sb, sc, sy, sx = image.stride()
     osb, osp = _strides(out)
-    prof = PROFILE
-    with _lib.on_device(image.device):
-        if prof is not None:
-            ev0, ev1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
-            ev0.record()
-        rc = lib.sr_stem7x7_fwd(_lib.ptr(image), sb, sc, sy, sx, _lib.ptr(wp), _lib.ptr(scale), _lib.ptr(shift),
-                                C.c_float(-1.0 if leaky is None else float(leaky)), _lib.ptr(out), osb, osp, b, h, w,
-                                64, _lib.stream_ptr(image.device))
-        if prof is not None:
-            ev1.record()
-            prof.append(("sr_stem_kernel", 2.0 * b * ho * wo * 64 * 147, ev0, ev1, (b, 3, h, w, 64, 7, 2),
-                         2.0 * b * ((ho + 15) // 16) * ((wo + 15) // 16) * 256 * 64 * 148))
+    record = lambda: ("sr_stem_kernel", 2.0 * b * ho * wo * 64 * 147, (b, 3, h, w, 64, 7, 2),
+                      2.0 * b * ((ho + 15) // 16) * ((wo + 15) // 16) * 256 * 64 * 148)
+    rc = _timed(image.device, record, _lib.lib().sr_stem7x7_fwd, _lib.ptr(image), sb, sc, sy, sx, _lib.ptr(wp),
+                _lib.ptr(scale), _lib.ptr(shift), C.c_float(-1.0 if leaky is None else float(leaky)), _lib.ptr(out), osb,
+                osp, b, h, w, 64, _lib.stream_ptr(image.device))
     _lib.check(rc, "sr_stem7x7_fwd")
     return out
 
@@ -717,9 +684,6 @@ def instance_norm(x, eps=1e-5, leaky=None, inplace=False):
     return out
 
 
-_PACKED_C16 = weakref.WeakKeyDictionary()  # nn.Conv2d -> (state key, packed weight, bias)
-
-
 def instance_norm_stats(x, eps=1e-5):
     """Per-(image, channel) InstanceNorm statistics of a channels-last tensor: [B,2,C] = (mean, 1/sqrt(var + eps))."""
     x = as_nhwc(x, "instance_norm_stats input")
@@ -757,20 +721,17 @@ def conv1x1_stats(x, conv: nn.Conv2d, eps=1e-5):
     bias = conv.bias.detach() if conv.bias is not None else None
     isb, isp = _strides(x)
     osb, osp = _strides(out)
-    prof = PROFILE
-    with _lib.on_device(x.device):
-        if prof is not None:
-            ev0, ev1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
-            ev0.record()
-        rc = lib.sr_conv1x1_stats_nhwc_fwd(_lib.ptr(x), isb, isp, _lib.ptr(weight), _lib.ptr(bias), _lib.ptr(out), osb,
-                                           osp, b, h, w, ci, co, C.c_float(eps), _lib.ptr(stats), _lib.ptr(ws),
-                                           ws.numel() * 4, _lib.stream_ptr(x.device))
-        if prof is not None:
-            ev1.record()
-            prof.append(("sr_conv1x1_stats_kernel", 2.0 * b * h * w * co * ci, ev0, ev1, (b, ci, h, w, co, 1, 1),
-                         2.0 * b * ((h * w + 63) // 64) * 64 * co * ci))
+    record = lambda: ("sr_conv1x1_stats_kernel", 2.0 * b * h * w * co * ci, (b, ci, h, w, co, 1, 1),
+                      2.0 * b * ((h * w + 63) // 64) * 64 * co * ci)
+    rc = _timed(x.device, record, lib.sr_conv1x1_stats_nhwc_fwd, _lib.ptr(x), isb, isp, _lib.ptr(weight), _lib.ptr(bias),
+                _lib.ptr(out), osb, osp, b, h, w, ci, co, C.c_float(eps), _lib.ptr(stats), _lib.ptr(ws), ws.numel() * 4,
+                _lib.stream_ptr(x.device))
     _lib.check(rc, "sr_conv1x1_stats_nhwc_fwd")
     return out, stats
+
+
+def _pack_c16(conv):
+    return _pack("conv3x3_c16", conv.weight.detach().contiguous()), (conv.bias.detach() if conv.bias is not None else None)
 
 
 def conv3x3_c16(x, conv: nn.Conv2d, in_stats=None, in_leaky=None, leaky=None):
@@ -784,20 +745,7 @@ def conv3x3_c16(x, conv: nn.Conv2d, in_stats=None, in_leaky=None, leaky=None):
             or conv.dilation != (1, 1) or conv.padding_mode not in ("zeros", "replicate") or co > 16 or ci % 32 \
             or ci != conv.in_channels:
         raise _lib.HipLibraryError(f"conv3x3_c16 needs Conv2d(32k, <=16, 3, padding=1), got {conv} for {ci} channels")
-    lib = _lib.lib()
-    key = _state_key(conv, None)
-    hit = _PACKED_C16.get(conv)
-    if hit is None or hit[0] != key:
-        wp = torch.empty(lib.sr_conv3x3_c16_packed_weight_floats(co, ci), dtype=torch.float32, device=conv.weight.device)
-        with _lib.on_device(conv.weight.device):
-            _lib.check(lib.sr_conv3x3_c16_pack_weights(_lib.ptr(conv.weight.detach().contiguous()), co, ci, _lib.ptr(wp),
-                                                       _lib.stream_ptr(conv.weight.device)), "sr_conv3x3_c16_pack_weights")
-        hit = (key, wp, conv.bias.detach() if conv.bias is not None else None)
-        _packed_here(conv, "c16", conv.weight.device)
-        _PACKED_C16[conv] = hit
-    else:
-        _await_packed(conv, "c16", conv.weight.device)
-    _, wp, bias = hit
+    wp, bias = _cached(conv, "c16", _state_key(conv, None), _pack_c16, conv)
     if in_stats is not None and (tuple(in_stats.shape) != (b, 2, ci) or not in_stats.is_contiguous()):
         raise ValueError(f"in_stats must be a contiguous [{b}, 2, {ci}] tensor")
     out = empty_nhwc(b, co, h, w, x.device)
@@ -805,27 +753,21 @@ def conv3x3_c16(x, conv: nn.Conv2d, in_stats=None, in_leaky=None, leaky=None):
         return out
     isb, isp = _strides(x)
     osb, osp = _strides(out)
-    prof = PROFILE
-    with _lib.on_device(x.device):
-        if prof is not None:
-            ev0, ev1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
-            ev0.record()
-        rc = lib.sr_conv3x3_c16_nhwc_fwd(_lib.ptr(x), isb, isp, _lib.ptr(in_stats),
-                                         C.c_float(-1.0 if in_leaky is None else float(in_leaky)), _lib.ptr(wp),
-                                         _lib.ptr(bias), _lib.ptr(out), osb, osp, b, h, w, ci, co,
-                                         int(conv.padding_mode == "replicate"),
-                                         C.c_float(-1.0 if leaky is None else float(leaky)), _lib.stream_ptr(x.device))
-        if prof is not None:
-            ev1.record()
-            prof.append(("sr_t16_kernel", 2.0 * b * h * w * co * ci * 9, ev0, ev1, (b, ci, h, w, co, 3, 1),
-                         2.0 * b * ((h + 7) // 8) * ((w + 15) // 16) * 128 * 16 * ci * 9))
+    record = lambda: ("sr_t16_kernel", 2.0 * b * h * w * co * ci * 9, (b, ci, h, w, co, 3, 1),
+                      2.0 * b * ((h + 7) // 8) * ((w + 15) // 16) * 128 * 16 * ci * 9)
+    rc = _timed(x.device, record, _lib.lib().sr_conv3x3_c16_nhwc_fwd, _lib.ptr(x), isb, isp, _lib.ptr(in_stats),
+                C.c_float(-1.0 if in_leaky is None else float(in_leaky)), _lib.ptr(wp), _lib.ptr(bias), _lib.ptr(out), osb,
+                osp, b, h, w, ci, co, int(conv.padding_mode == "replicate"),
+                C.c_float(-1.0 if leaky is None else float(leaky)), _lib.stream_ptr(x.device))
     _lib.check(rc, "sr_conv3x3_c16_nhwc_fwd")
     return out
 
 
 # ---- MBConv pieces of the image-prior encoder (csrc/sr_mbconv.hip) -----------------------------------------------
 
-_PACKED_DW = weakref.WeakKeyDictionary()  # depthwise nn.Conv2d -> (state key, [9, C] weight, bias)
+def _pack_dw(conv, bn):
+    w, bias = _effective_weight(conv, bn)                      # [C, 1, 3, 3]
+    return w.reshape(conv.in_channels, 9).t().contiguous(), (bias.contiguous() if bias is not None else None)
 
 
 def packed_dw_weight(conv: nn.Conv2d, bn=None):
@@ -835,15 +777,7 @@ def packed_dw_weight(conv: nn.Conv2d, bn=None):
     if conv.kernel_size != (3, 3) or conv.groups != c or conv.out_channels != c or conv.dilation != (1, 1) \
             or conv.padding_mode != "zeros":
         raise _lib.HipLibraryError(f"unsupported depthwise Conv2d configuration for the HIP path: {conv}")
-    key = _state_key(conv, bn)
-    hit = _PACKED_DW.get(conv)
-    if hit is not None and hit[0] == key:
-        return hit[1], hit[2]
-    w, bias = _effective_weight(conv, bn)                      # [C, 1, 3, 3]
-    w9c = w.reshape(c, 9).t().contiguous()
-    bias = bias.contiguous() if bias is not None else None
-    _PACKED_DW[conv] = (key, w9c, bias)
-    return w9c, bias
+    return _cached(conv, "dw", _state_key(conv, bn), _pack_dw, conv, bn)
 
 
 def dwconv3x3(x, conv: nn.Conv2d, bn=None, leaky=None, act=None, tf_same=False, want_pool=False, pads=None):
@@ -904,7 +838,11 @@ def se_gate(pool_partial, pixels, conv_reduce: nn.Conv2d, conv_expand: nn.Conv2d
     return gate
 
 
-_PACKED_RGB = weakref.WeakKeyDictionary()  # stem nn.Conv2d -> (state key, [27, Cout] weight with BN folded, bias)
+def _pack_rgb(conv, bn):
+    """([27, Cout] weight with `bn` folded in, bias)."""
+    wt, bias = _effective_weight(conv, bn)                                     # [Cout, 3, 3, 3]
+    w27 = wt.permute(2, 3, 1, 0).reshape(27, conv.out_channels).contiguous()   # [ky][kx][ci][Cout]
+    return w27, (bias.contiguous() if bias is not None else None)
 
 
 def rgb_stem3x3s2(image, conv: nn.Conv2d, bn=None, act=None, leaky=None, tf_same=True):
@@ -918,18 +856,8 @@ def rgb_stem3x3s2(image, conv: nn.Conv2d, bn=None, act=None, leaky=None, tf_same
     b, _, h, w = image.shape
     pads = tf_same_pads(h, w, 3, 2) if tf_same else (1, 1, 1, 1)
     ho, wo = (h + pads[0] + pads[2] - 3) // 2 + 1, (w + pads[1] + pads[3] - 3) // 2 + 1
-    key = _state_key(conv, bn)
-    hit = _PACKED_RGB.get(conv)
-    if hit is None or hit[0] != key:
-        wt, bias = _effective_weight(conv, bn)                          # [Cout, 3, 3, 3]
-        w27 = wt.permute(2, 3, 1, 0).reshape(27, conv.out_channels).contiguous()   # [ky][kx][ci][Cout]
-        hit = (key, w27, bias.contiguous() if bias is not None else None)
-        _packed_here(conv, "rgb", conv.weight.device)
-        _PACKED_RGB[conv] = hit
-    else:
-        _await_packed(conv, "rgb", conv.weight.device)
-    _, w27, bias = hit
-    out = empty_nhwc(b, conv.out_channels, ho, wo, image.device)
+    w27, bias = _cached(conv, "rgb", _state_key(conv, bn), _pack_rgb, conv, bn)
+    out =empty_nhwc(b, conv.out_channels, ho, wo, image.device)
     if b == 0:
         return out
     sb, sc, sy, sx = image.stride()

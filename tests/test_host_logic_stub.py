@@ -7,6 +7,7 @@ import gzip
 import json
 import os
 import ctypes
+import weakref
 
 import pytest
 import torch
@@ -32,6 +33,16 @@ def stub(monkeypatch):
 
     class Stream:
         cuda_stream = 0
+
+    class Event:   # (torch.cuda.Event without a GPU: the PROFILE records and the pack fences only keep them)
+        def __init__(self, **kw):
+            pass
+
+        def record(self, *a):
+            pass
+
+        def query(self):
+            return True
 
     class Fn:
         def __init__(self, name):
@@ -84,6 +95,7 @@ def stub(monkeypatch):
     monkeypatch.setattr(_lib, "stream_ptr", lambda dev=None: ctypes.c_void_p(0))
     monkeypatch.setattr(torch.cuda, "device", lambda d: contextlib.nullcontext())
     monkeypatch.setattr(torch.cuda, "current_stream", lambda d=None: Stream())
+    monkeypatch.setattr(torch.cuda, "Event", Event)
     return calls
 
 
@@ -274,14 +286,13 @@ def test_per_shape_library_answers_are_asked_once(stub):
     assert ops._shape_query(lib, "sr_conv_prefers_wino", 2, 8, 16, 16, 32, 3, 1) == 1 and len(stub) == n + 1
 
 
-def test_split_precision_switch_repacks_the_winograd_weight(stub, monkeypatch, sr_option):
+def test_split_precision_switch_repacks_the_cached_winograd_weight(stub, monkeypatch, sr_option):
     """SR_WINO_SPLIT (the fenced split-precision Winograd variant) changes what a packed weight CONTAINS (16-bit pieces in the
     fp32 layout's buffer): the cache must re-pack when the switch changes and hit otherwise; off-values mean the fp32 path."""
     from torch import nn
 
     from simplerecon_amd import ops
-    monkeypatch.setattr(ops, "_await_packed", lambda *a, **k: None)
-    monkeypatch.setattr(ops, "_packed_here", lambda *a, **k: None)
+    monkeypatch.setattr(ops, "_PACKED", weakref.WeakKeyDictionary())
     conv = nn.Conv2d(16, 32, 3, padding=1)
     for off in ("", "0", "off", "fp32"):
         sr_option("SR_WINO_SPLIT", off)
@@ -302,6 +313,120 @@ def test_split_precision_switch_repacks_the_winograd_weight(stub, monkeypatch, s
     sr_option("SR_WINO_SPLIT", "0")
     ops.packed_wino_weight(conv)
     assert stub.count("sr_wino_pack_weights") == n + 3        # and back to fp32 fragments
+
+
+def _cached_entry_points():
+    """name -> (module, eval-mode BatchNorm folded into it or None, one call that uses the cached payload) for each ops entry
+    point with a packed-weight cache entry."""
+    from torch import nn
+
+    from simplerecon_amd import ops
+    nhwc = lambda *shape: torch.zeros(*shape).contiguous(memory_format=torch.channels_last)
+    bn = lambda c: nn.BatchNorm2d(c).eval()
+    conv3 = lambda: nn.Conv2d(8, 16, 3, padding=1)
+    return {
+        "direct": (conv3(), bn(16), lambda m, n: ops.packed_weight(m, n)),
+        "wino": (conv3(), bn(16), lambda m, n: ops.packed_wino_weight(m, n)),
+        "wino4": (conv3(), bn(16), lambda m, n: ops.packed_wino4_weight(m, n)),
+        "linear": (nn.Linear(8, 16), None, lambda m, n: ops.linear(torch.zeros(4, 8), m)),
+        "stem": (nn.Conv2d(3, 64, 7, stride=2, padding=3, bias=False), bn(64),
+                 lambda m, n: ops.stem7x7(torch.zeros(1, 3, 16, 16), m, n)),
+        "c16": (nn.Conv2d(32, 16, 3, padding=1), None, lambda m, n: ops.conv3x3_c16(nhwc(1, 32, 8, 8), m)),
+        "dw": (nn.Conv2d(16, 16, 3, padding=1, groups=16, bias=False), bn(16),
+               lambda m, n: ops.dwconv3x3(nhwc(1, 16, 8, 8), m, n)),
+        "rgb": (nn.Conv2d(3, 24, 3, stride=2, bias=False), bn(24),
+                lambda m, n: ops.rgb_stem3x3s2(torch.zeros(1, 3, 16, 16), m, n)),
+    }
+
+
+_CACHED = sorted(_cached_entry_points())
+
+
+@pytest.mark.parametrize("name", _CACHED)
+def test_packed_weights_are_cached_until_a_parameter_changes(stub, monkeypatch, name):
+    """Each cached entry point packs once, hits afterwards, and re-packs after an in-place parameter update, a new
+    nn.Parameter and a change of a folded BatchNorm's running statistics."""
+    from torch import nn
+
+    from simplerecon_amd import ops
+    mod, bn, use = _cached_entry_points()[name]
+    builds, cached = [], ops._cached
+    monkeypatch.setattr(ops, "_cached", lambda m, tag, key, build, *args: cached(
+        m, tag, key, lambda *a: (builds.append(tag), build(*a))[1], *args))
+
+    def packs():
+        with torch.no_grad():
+            use(mod, bn)
+            use(mod, bn)
+        return len(builds)
+    assert packs() == 1
+    with torch.no_grad():
+        mod.weight.mul_(2.0)
+    assert packs() == 2
+    mod.weight = nn.Parameter(mod.weight.detach().clone())
+    assert packs() == 3
+    if bn is not None:
+        bn.running_mean.add_(1.0)
+        assert packs() == 4
+
+
+@pytest.mark.parametrize("name", _CACHED)
+def test_packed_weights_are_fenced_for_other_streams(stub, monkeypatch, name):
+    """A payload packed on stream A is waited for once by a use on stream B while the pack has not completed, never by a use
+    on A; a completed pack is not waited for again; while a graph is captured nothing is recorded or awaited."""
+    class Stream:
+        def __init__(self, handle):
+            self.cuda_stream, self.waits = handle, []
+
+        def wait_event(self, ev):
+            self.waits.append(ev)
+
+    events = []
+
+    class Event:
+        def __init__(self, **kw):
+            self.stream, self.done, self.queries = None, False, 0
+            events.append(self)
+
+        def record(self, stream=None):
+            self.stream = stream
+
+        def query(self):
+            self.queries += 1
+            return self.done
+
+    a, b = Stream(1), Stream(2)
+    now = {"stream": a, "capturing": False}
+    monkeypatch.setattr(torch.cuda, "current_stream", lambda d=None: now["stream"])
+    monkeypatch.setattr(torch.cuda, "Event", Event)
+    monkeypatch.setattr(_lib, "cuda_available", lambda: True)
+    monkeypatch.setattr(_lib, "capturing", lambda: now["capturing"])
+    mod, bn, use = _cached_entry_points()[name]
+
+    def run(stream, capturing=False):
+        now["stream"], now["capturing"] = stream, capturing
+        with torch.no_grad():
+            use(mod, bn)
+    run(a)
+    assert len(events) == 1 and events[0].stream is a
+    ev = events[0]
+    run(a)
+    assert a.waits == []
+    queries = ev.queries
+    run(b, capturing=True)
+    assert b.waits == [] and ev.queries == queries and len(events) == 1
+    run(b)
+    assert b.waits == [ev]
+    ev.done = True
+    run(b)
+    queries = ev.queries
+    run(b)
+    assert b.waits == [ev] and ev.queries == queries
+    with torch.no_grad():
+        mod.weight.mul_(2.0)
+    run(a, capturing=True)   # a re-pack inside a capture
+    run(b)
+    assert len(events) == 1 and b.waits == [ev] and a.waits == []
 
 
 def test_fenced_workloads_label_their_arithmetic():
@@ -437,15 +562,8 @@ def _dispatch_trace(stub, monkeypatch, case, rc):
 
 
 def _dispatch_traces(stub, monkeypatch):
-    class Event:   # (torch.cuda.Event without a GPU: PROFILE only keeps them)
-        def __init__(self, **kw):
-            pass
-
-        def record(self, *a):
-            pass
     from simplerecon_amd import ops
-    monkeypatch.setattr(torch.cuda, "Event", Event)
-    monkeypatch.setattr(ops, "_PACK_EVENTS", {})
+    monkeypatch.setattr(ops, "_PACKED", weakref.WeakKeyDictionary())
     traces = {}
     saved = _lib.get_option("SR_WINO_SPLIT")
     try:
@@ -466,7 +584,7 @@ def _dispatch_traces(stub, monkeypatch):
     return json.loads(json.dumps(traces))
 
 
-def test_conv2d_dispatch_is_pinned(stub, monkeypatch):
+def test_conv2d_dispatch_matches_the_golden(stub, monkeypatch):
     """ops.conv2d picks the same kernels, falls back in the same order and writes the same PROFILE records (name, algorithmic
     and executed FLOPs, shape) as recorded in tests/golden/conv2d_dispatch.json.gz."""
     got = _dispatch_traces(stub, monkeypatch)
