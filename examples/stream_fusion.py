@@ -1,10 +1,11 @@
 """End-to-end streaming example on synthetic data: posed frames -> online keyframe / source selection
 (simplerecon_amd.keyframes) -> DepthModel.forward (image-prior + matching encoders, plane-sweep cost volume, cost-volume
 encoder and UNet++ decoder, all on HIP kernels) -> TSDF fusion of the predicted depth (simplerecon_amd.tsdf) -> with
---mesh, marching cubes on the GPU and a PLY file.  It mirrors what the reference's test.py does per scan
+--mesh, marching cubes on the GPU and a PLY file; with --point-cloud, multi-view consistency fusion of the same depth maps
+into a coloured point cloud (simplerecon_amd.point_cloud, the reference's pc_fusion.py).  It mirrors what the reference's test.py does per scan
 (test.py:210-410) without datasets or checkpoints.
 
-    python examples/stream_fusion.py [--frames 120] [--height 192] [--width 256] [--mesh out.ply]
+    python examples/stream_fusion.py [--frames 120] [--height 192] [--width 256] [--mesh out.ply] [--point-cloud out.ply]
 
 Weights are random, so the depth maps are meaningless -- the point is the data flow and the API.
 """
@@ -19,6 +20,7 @@ sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
 from simplerecon_amd import depth_model as dm  # noqa: E402
 from simplerecon_amd import keyframes as kf  # noqa: E402
 from simplerecon_amd import synthetic  # noqa: E402
+from simplerecon_amd.point_cloud import PointCloudFuser  # noqa: E402
 from simplerecon_amd.tsdf import OurFuser  # noqa: E402
 
 
@@ -45,7 +47,8 @@ def camera_path(n, seed=0):
     return out
 
 
-def run(frames=120, height=192, width=256, views=8, device="cuda:0", verbose=True, mesh_path=None):
+def run(frames=120, height=192, width=256, views=8, device="cuda:0", verbose=True, mesh_path=None,
+        point_cloud_path=None):
     opts = dm.default_options(image_width=width, image_height=height, model_num_views=views)
     model = dm.DepthModel(opts)
     for i, m in enumerate((model.encoder, model.matching_model, model.cost_volume_net, model.depth_decoder,
@@ -54,6 +57,7 @@ def run(frames=120, height=192, width=256, views=8, device="cuda:0", verbose=Tru
     model = model.to(device).eval()
     fuser = OurFuser(bounds=dict(xmin=-2.0, xmax=6.0, ymin=-2.0, ymax=2.0, zmin=-1.0, zmax=7.0), max_fusion_depth=3.0,
                      device=device)
+    pc_fuser = PointCloudFuser(fusion_size=(height, width)) if point_cloud_path else None   # pc_fusion.py:122-150
     cfg = kf.DVMVS_Config
     buf = kf.KeyframeBuffer(cfg.test_keyframe_buffer_size, cfg.test_keyframe_pose_distance, cfg.test_optimal_t_measure,
                             cfg.test_optimal_R_measure, store_return_indices=True)
@@ -84,6 +88,8 @@ def run(frames=120, height=192, width=256, views=8, device="cuda:0", verbose=Tru
             out = model("test", cur, src, unbatched_matching_encoder_forward=False, return_mask=True)
             depth = out["depth_pred_s0_b1hw"]
             fuser.fuse_frames(depth, K_depth[None].to(device), cur["cam_T_world_b44"], None)
+            if pc_fuser is not None:
+                pc_fuser.fuse_frames(depth, K_depth[None].to(device), cur["cam_T_world_b44"], cur["image_b3hw"])
         predicted += 1
     vol = fuser.tsdf_fuser_pred
     touched = int((vol.tsdf_weights > 0).sum())
@@ -94,6 +100,10 @@ def run(frames=120, height=192, width=256, views=8, device="cuda:0", verbose=Tru
         if verbose:
             mesh = fuser.get_mesh()
             print(f"mesh: {mesh.vertices.shape[0]} vertices, {mesh.faces.shape[0]} triangles -> {mesh_path}")
+    if point_cloud_path and predicted:
+        pc_fuser.export_point_cloud(point_cloud_path)   # pc_fusion.py:152-172
+        if verbose:
+            print(f"point cloud: {len(pc_fuser.get_point_cloud())} points -> {point_cloud_path}")
     return predicted, touched
 
 
@@ -103,5 +113,6 @@ if __name__ == "__main__":
     ap.add_argument("--height", type=int, default=192)
     ap.add_argument("--width", type=int, default=256)
     ap.add_argument("--mesh", default=None, help="write the fused surface to this .ply file")
+    ap.add_argument("--point-cloud", default=None, help="write the fused point cloud to this .ply file")
     a = ap.parse_args()
-    run(a.frames, a.height, a.width, mesh_path=a.mesh)
+    run(a.frames, a.height, a.width, mesh_path=a.mesh, point_cloud_path=a.point_cloud)

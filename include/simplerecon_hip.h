@@ -506,6 +506,65 @@ int sr_mesh_emit(const void* tsdf_values, int X, int Y, int Z, float level, floa
                  size_t list_scratch_bytes, int64_t active, int64_t num_vertices, int64_t num_faces, float* vertices,
                  float* normals, int* faces, void* stream);
 
+/* ------------------------------------------------------------- point-cloud fusion ----
+ *
+ * Multi-view consistency fusion of predicted depth maps into a point cloud (the reference's pc_fusion.py with
+ * tools/torch_point_cloud_fusion.py:12-118, a Python loop over [100, 3, h*w] torch temporaries), then open3d's voxel
+ * downsampling.  tests/pc_oracle.py implements the same rules in fp64 numpy.
+ *
+ * Inputs of a scene of N frames: depth D [N,h,w] fp32; intrinsics K [N,3,3]; world-to-camera poses P [N,4,4]
+ * (cam_T_world), P_i = [R_i | t_i].
+ *
+ * Rules, per reference frame r.  Its sources are every other frame s != r, in ascending index.  For each pixel
+ * (u = column, v = row, integers) with depth d = D_r[v,u]:
+ *  1. World point X = P_r^-1 (K_r^-1 (u*d, v*d, d)) as a 3-D point, for every d: a zero depth is not excluded and
+ *     gives the camera centre.
+ *  2. Projection into s: q = K_s (R_s X + t_s), z = q_z, x = q_x / z, y = q_y / z.
+ *  3. In bounds: z > 1e-4, 0 <= x <= w-1, 0 <= y <= h-1 (continuous coordinates, closed intervals).
+ *  4. Sampled depth z_s: the nearest texel of D_s as grid_sample(mode="nearest", align_corners=True, zeros padding)
+ *     picks it: (x, y) normalised to [-1, 1] and back, ((g + 1) / 2) * (size - 1), rounded half to even.  A zero in
+ *     D_s is an ordinary value (a source sampled at 0 is consistent when z < z_thresh).
+ *  5. Source s is consistent when it is in bounds and |z - z_s| < z_thresh (strict).  n = number of consistent sources.
+ *  6. Sampled point Y_s = R_s^T (K_s^-1 (x*z_s, y*z_s, z_s) - t_s), at the continuous (x, y), not the texel centre.
+ *  7. avg = (X + sum of Y_s) / (n + 1): the sum runs over the consistent sources whose Y_s has no NaN component, in
+ *     the order X, then s ascending.  The reference frame's own point is always in it.
+ *  8. The pixel is kept when n >= n_consistent_thresh.  Kept points are listed frame by frame, each frame row-major;
+ *     a point's colour is the reference frame's uint8 image at [v,u]; the keep masks [N,h,w] are an output too.
+ *
+ * Voxel downsampling (open3d's voxel_down_sample, restated): in fp64, min_bound = the per-axis minimum of the points
+ * - voxel_size / 2; voxel index = floor((p - min_bound) / voxel_size) with IEEE fp64 division.  Each occupied voxel
+ * gives one point, the fp64 mean of its points cast to fp32, and one colour, the integer mean of its uint8 colours
+ * rounded half up: (sum + cnt / 2) / cnt (our definition; open3d keeps float colours).  Voxels come out in ascending
+ * key = ix * 2^42 + iy * 2^21 + iz; an extent of 2^21 voxels or more on an axis is refused by the caller.
+ *
+ * sr_pc_consistency: one launch fuses the reference frames [ref_begin, ref_begin + ref_count) against all N frames.
+ *  depth        [N,h,w] fp32
+ *  frame_consts [N, SR_PC_FRAME_FLOATS] fp32, computed by the caller in fp64, per frame i:
+ *               [0,12)  K_i [R_i | t_i]                 (3x4 row-major: step 2 as one affine map)
+ *               [12,21) R_i^T K_i^-1, [21,24) -R_i^T t_i (step 6: Y = z_s * (R^T K^-1 (x, y, 1)) - R^T t)
+ *               [24,33) P_i^-1[:3,:3] K_i^-1, [33,36) P_i^-1[:3,3]  (step 1, for i as the reference frame)
+ *  points       [ref_count,h,w,3] fp32: avg of step 7 for every pixel (kept or not)
+ *  counts       [ref_count,h,w] int32: n of step 5
+ * The rules are evaluated in fp32 with these fused constants, and the texel is the nearest one to the continuous
+ * (x, y) (the normalisation round trip of step 4 moves a coordinate by a few ulps only), so decisions within rounding
+ * distance of a threshold or of a texel boundary may differ from the reference's fp32 evaluation.  No atomics: each
+ * pixel's sum is kept in registers in source order, so results do not depend on the schedule.
+ * Refused (SR_ERR_INVALID_ARGUMENT): a NULL pointer, N < 1, h or w < 2, an empty or out-of-range chunk, h*w*3*4 bytes
+ * or ref_count*h*w*3*4 bytes beyond int32 indexing, z_thresh not positive and finite.
+ *
+ * sr_pc_voxel_keys: keys [M] int64 of points [M,3] fp32 for the given fp64 min_bound and voxel_size (indices clamped
+ * to [0, 2^21)).  sr_pc_voxel_mean: given the stable key-sorted permutation `order` [M] int64 and the run starts
+ * `seg_start` [S+1] int64 (seg_start[S] = M), writes out_points [S,3] fp32 and, when colors [M,3] uint8 is not NULL,
+ * out_colors [S,3] uint8: a thread per voxel sums its points in sorted order.  None of the three calls takes scratch;
+ * the library allocates nothing and does not synchronise the host. */
+#define SR_PC_FRAME_FLOATS 36
+int sr_pc_consistency(const float* depth, const float* frame_consts, int N, int h, int w, int ref_begin, int ref_count,
+                      float z_thresh, float* points, int* counts, void* stream);
+int sr_pc_voxel_keys(const float* points, int64_t M, double min_x, double min_y, double min_z, double voxel_size,
+                     int64_t* keys, void* stream);
+int sr_pc_voxel_mean(const float* points, const uint8_t* colors, int64_t M, const int64_t* order,
+                     const int64_t* seg_start, int64_t S, float* out_points, uint8_t* out_colors, void* stream);
+
 /* ------------------------------------------------------ backward (training) -------------
  *
  * Backward of sr_dot_volume_sweep (reference: autograd through CostVolumeManager.build_cost_volume,

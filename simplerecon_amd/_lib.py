@@ -153,6 +153,9 @@ SIGNATURES = {
     "sr_mesh_list_scratch_bytes": (_sz, [_i64]),
     "sr_mesh_count": (_i, [_p, _i, _i, _i, _f, _p, _sz, _p, _p]),
     "sr_mesh_emit": (_i, [_p, _i, _i, _i, _f, _f, _f, _f, _f, _p, _sz, _p, _sz, _i64, _i64, _i64, _p, _p, _p, _p]),
+    "sr_pc_consistency": (_i, [_p, _p, _i, _i, _i, _i, _i, _f, _p, _p, _p]),
+    "sr_pc_voxel_keys": (_i, [_p, _i64, C.c_double, C.c_double, C.c_double, C.c_double, _p, _p]),
+    "sr_pc_voxel_mean": (_i, [_p, _p, _i64, _p, _p, _i64, _p, _p, _p]),
 }
 
 

@@ -153,3 +153,89 @@ def seeded_fill_(module, seed=0, gain=1.0):
                 v = rng.uniform(-0.1, 0.1, size=tuple(p.shape)).astype(np.float32)
             p.copy_(torch.from_numpy(v).to(p.device))
     return module
+
+
+def raycast_scene(N, h, w, seed=0, noise=0.0, holes=0.0, device="cpu"):
+    """A ray-cast indoor scene for point-cloud fusion: a 5 x 3 x 5 m box room with three boxes and two spheres, seen
+    by N cameras on a slow loop inside it.  Depth is exact (up to fp32), so it is multi-view consistent except at
+    occlusions; `noise` adds N(0, noise) relative depth error and `holes` zeroes that fraction of the pixels.
+
+    Returns depths [N,h,w] fp32 (z along the optical axis), images [N,h,w,3] uint8, cam_T_world [N,4,4] fp32 and
+    K [N,3,3] fp32.  The layout, the camera path and the noise come from numpy's generator (the same seed gives the
+    same scene everywhere); the rays are cast in fp64 torch on `device`."""
+    rng = np.random.default_rng(7000 + seed)
+    room = np.array([[-2.5, -1.5, -2.5], [2.5, 1.5, 2.5]])
+    prims = []   # (kind, params, base colour)
+    for k in range(3):
+        a = 2 * np.pi * (k / 3.0) + rng.uniform(-0.4, 0.4)
+        c = np.array([1.85 * np.cos(a), rng.uniform(0.2, 1.0), 1.85 * np.sin(a)])
+        half = rng.uniform(0.2, 0.4, size=3)
+        prims.append(("box", (c - half, c + half), rng.uniform(40, 215, size=3)))
+    for k in range(2):
+        a = 2 * np.pi * (k / 2.0 + 0.25) + rng.uniform(-0.3, 0.3)
+        c = np.array([1.6 * np.cos(a), rng.uniform(-0.6, 0.4), 1.6 * np.sin(a)])
+        prims.append(("sphere", (c, rng.uniform(0.25, 0.4)), rng.uniform(40, 215, size=3)))
+
+    f = 577.87 * (w / 640.0)
+    K = np.array([[f, 0.0, (w - 1) / 2.0 + 0.3], [0.0, f, (h - 1) / 2.0 - 0.2], [0.0, 0.0, 1.0]])
+    cam_T_world = np.zeros((N, 4, 4))
+    for i in range(N):
+        th = 0.05 * i + rng.uniform(-0.01, 0.01)
+        pos = np.array([0.8 * np.cos(th), 0.1 * np.sin(0.07 * i), 0.8 * np.sin(th)])
+        yaw = th + np.pi / 2 + 0.3 * np.sin(0.11 * i)
+        pitch = 0.1 * np.sin(0.05 * i)
+        fwd = np.array([np.cos(yaw) * np.cos(pitch), np.sin(pitch), np.sin(yaw) * np.cos(pitch)])
+        down = np.array([0.0, 1.0, 0.0]) - fwd[1] * fwd
+        down /= np.linalg.norm(down)
+        right = np.cross(down, fwd)
+        T = np.eye(4)
+        T[:3, :3] = np.stack([right, down, fwd], 1)   # world_T_cam: camera x right, y down, z forward
+        T[:3, 3] = pos
+        cam_T_world[i] = np.linalg.inv(T)
+
+    dt = dict(dtype=torch.float64, device=device)
+    vv, uu = torch.meshgrid(torch.arange(h, **dt), torch.arange(w, **dt), indexing="ij")
+    pix = torch.stack([uu, vv, torch.ones_like(uu)], -1).reshape(-1, 3)
+    dir_cam = pix @ torch.as_tensor(np.linalg.inv(K), **dt).T           # z = 1: the hit distance t is the depth
+    wTc = torch.as_tensor(np.linalg.inv(cam_T_world), **dt)
+    d = torch.einsum("nij,pj->npi", wTc[:, :3, :3], dir_cam)            # [N,P,3], not normalised
+    o = wTc[:, None, :3, 3].expand_as(d)
+    inf = torch.tensor(float("inf"), **dt)
+    lo, hi = torch.as_tensor(room[0], **dt), torch.as_tensor(room[1], **dt)
+    t_wall = torch.where(d > 0, (hi - o) / d, (lo - o) / d)
+    t_wall = torch.where(d == 0, inf, t_wall)
+    best, axis = t_wall.min(-1)
+    obj = axis                                                     # 0..2: the wall's axis
+    for pi, (kind, par, _) in enumerate(prims):
+        if kind == "box":
+            blo, bhi = torch.as_tensor(par[0], **dt), torch.as_tensor(par[1], **dt)
+            t1, t2 = (blo - o) / d, (bhi - o) / d
+            tmin = torch.minimum(t1, t2).nan_to_num(nan=-float("inf")).max(-1).values
+            tmax = torch.maximum(t1, t2).nan_to_num(nan=float("inf")).min(-1).values
+            hit = (tmax >= tmin) & (tmin > 0)
+            t = torch.where(hit, tmin, inf)
+        else:
+            c, r = torch.as_tensor(par[0], **dt), par[1]
+            oc = o - c
+            a = (d * d).sum(-1)
+            b = (d * oc).sum(-1)
+            disc = b * b - a * ((oc * oc).sum(-1) - r * r)
+            t = (-b - disc.clamp(min=0).sqrt()) / a
+            t = torch.where((disc >= 0) & (t > 0), t, inf)
+        closer = t < best
+        best = torch.where(closer, t, best)
+        obj = torch.where(closer, torch.full_like(obj, 3 + pi), obj)
+    hitp = o + best[..., None] * d
+    checker = (torch.floor(hitp * 4.0).sum(-1).remainder(2.0))             # 0 / 1
+    base = torch.as_tensor(np.concatenate([np.array([[200, 180, 150], [120, 140, 170], [160, 200, 140]]),
+                                           np.stack([p[2] for p in prims])]), **dt)
+    rgb = base[obj] * (0.7 + 0.3 * checker)[..., None]
+    depth = best.reshape(N, h, w)
+    if noise > 0:
+        depth = depth * (1.0 + torch.as_tensor(rng.standard_normal((N, h, w)) * noise, **dt))
+    if holes > 0:
+        depth = torch.where(torch.as_tensor(rng.random((N, h, w)) < holes, device=device), 0.0, depth)
+    return dict(depths=depth.float().contiguous(),
+                images=rgb.round().clamp(0, 255).to(torch.uint8).reshape(N, h, w, 3).contiguous(),
+                cam_T_world=torch.as_tensor(cam_T_world, dtype=torch.float32, device=device),
+                K=torch.as_tensor(np.repeat(K[None], N, 0), dtype=torch.float32, device=device))
