@@ -565,6 +565,95 @@ int sr_pc_voxel_keys(const float* points, int64_t M, double min_x, double min_y,
 int sr_pc_voxel_mean(const float* points, const uint8_t* colors, int64_t M, const int64_t* order,
                      const int64_t* seg_start, int64_t S, float* out_points, uint8_t* out_colors, void* stream);
 
+/* ------------------------------------------------------------- training losses ----
+ *
+ * The reference's training objective (experiment_modules/depth_model.py:409-500 `compute_losses`, losses.py and
+ * utils/geometry_utils.py:92-133 `NormalGenerator`), forward and backward.  Everything is fp32 in and fp32 out, and
+ * gradients flow to the predictions only: gt depth, masks, poses and intrinsics are data.  tests/loss_oracle.py
+ * restates the rules in fp64 torch.  Maps are dense [B,h,w] (a [B,1,h,w] tensor), normals [B,3,h,w], matrices
+ * row-major [.,4,4].  Refused (SR_ERR_INVALID_ARGUMENT): a NULL pointer, B < 1 or B > 65535, h or w < 3 (the
+ * 5x5 reflect blur needs 3), h*w > 2^28, K outside [1, SR_LOSS_MAX_SOURCES]; a scratch smaller than its query:
+ * SR_ERR_WORKSPACE_TOO_SMALL.  Scratch sizes come from the *_workspace_bytes queries (0 for a refused shape); the
+ * library allocates nothing.
+ *
+ * Three kornia 0.6.7 filters are restated (the reference pins that version):
+ *  - blur_pool2d(x, 3): correlation with [1,2,1]^T [1,2,1] / 16, zero padding 1, stride 2: n pixels -> ceil(n/2).
+ *    The gradient loss's pyramid has 4 levels; level 0 is the map itself.
+ *  - spatial_gradient(x): Sobel / 8 with replicate borders.  gx = correlation with [[-1,0,1],[-2,0,2],[-1,0,1]] / 8
+ *    (positive when values grow with x), gy with its transpose.  A component is non-finite when any of its nine
+ *    taps is, zero-weight taps included (ATen's conv: NaN * 0 = NaN).
+ *  - gaussian_blur2d(x, (5,5), (2,2)): weights exp(-t^2/8), t in -2..2, normalised to sum 1, applied as their 5x5
+ *    outer product, `reflect` padding of 2 (no edge repeat).
+ *
+ * Rules:
+ *  - Normals (NormalGenerator): blur the depth, back-project it (pixel centres at +0.5: P = s * invK[:3,:3] (x+.5,
+ *    y+.5, 1)), take spatial_gradient of the 3 point channels; n = c / max(|c|, 1e-12), c = cross(gx, gy).
+ *  - NormalsLoss: mask = all three components finite in gt and in pred; loss = masked mean of 0.5 (1 - n_pred . n_gt).
+ *  - MSGradientLoss: the sum over the 4 pyramid levels of the mean |grad pred - grad gt| over the gradient components
+ *    (x and y separately) whose gt value is finite.  On depth, not log depth.  An empty level gives NaN.
+ *  - MVDepthLoss, per source k: back-project gt, move it to world (cur_world_T_cam), project into k (K_k cam_T_world_k,
+ *    z' = q_z + eps, pixel = q_xy / z' when |q_z| > eps, else q_xy); sample the source gt depth nearest as
+ *    grid_sample(align_corners=False, zeros) does: normalise to [-1, 1] and back, round half to even, 0 out of bounds.
+ *    Valid: z' < 1.05 s, z' > 0, s > 0 (NaN fails all three).  Error |log s - log z'_pred| with z'_pred the predicted
+ *    depth through the same chain.  mean over the valid pixels whose error is not NaN (nanmean) per k, then the mean
+ *    over k.  An empty k gives NaN, exactly as the reference; its gradient contribution is zero.
+ *  - Depth terms, all on mask_b: ms = sum_i mean |log gt - NN_i(log_pred_s{i})| / 2^i over the scales present (NN_i:
+ *    F.interpolate(mode="nearest") to gt size, source index min(floor(dst * (in/out)), in - 1) in fp32); abs, log_l1,
+ *    si = sqrt(mean d^2 - lambda (mean d)^2) with d = log gt - log_pred_s0; inv_abs on mask_b & depth_pred > 0.1.
+ * The gradient of |x| at 0 is 0.
+ *
+ * Execution: every loss writes fixed-order per-block partials to the scratch and one single-workgroup finalize sums
+ * them in fp64 into `out` on the device: no float atomics (two runs give the same bits) and no host synchronisation;
+ * the backward entry points read the incoming gradient(s) and the forward's `out` (counts, means) from device
+ * memory.  The launch count does not depend on K.
+ *
+ * sr_normals_fwd / _bwd: depth [B,h,w], invK [B,4,4] -> normals [B,3,h,w]; grad_normals -> grad_depth [B,h,w].
+ * sr_normals_loss_fwd: out[2] = {loss, count}.  _bwd: grad_pred [B,3,h,w] of the scalar grad_out[0].
+ * sr_grad_loss_fwd: out[5] = {loss, count of levels 0..3}.  _bwd reads the pyramid the forward left in the scratch:
+ *   pass the same scratch, unchanged.
+ * sr_mv_loss_fwd: src_depth [B,K,h,w], src_K / src_cam_T_world [B,K,4,4]; out[1 + 2K] = {loss, count_k, mean_k};
+ *   valid_mask [B,K,h,w] uint8 and sampled [B,K,h,w] (the sampled source depth) are optional (NULL: not written).
+ * sr_depth_terms_fwd: mask_b [B,h,w] uint8 (0 / 1), log0 [B,h,w] is required, log1..3 [B,h_i,w_i] may be NULL
+ *   (h_i <= h, w_i <= w); out[8] = {ms, abs, inv_abs, log_l1, si, count, inv count, mean d}.  _bwd: grad_outs[5] =
+ *   d{ms, abs, inv_abs, log_l1, si}; writes grad_depth_pred and the grad of every present log scale.  gt_is_log != 0:
+ *   depth_gt holds log depth already (ScaleInvariantLoss on its own; abs and inv_abs are then meaningless).  These
+ *   two take any h, w >= 1. */
+#define SR_LOSS_MAX_SOURCES 15
+size_t sr_normals_workspace_bytes(int B, int h, int w);
+int sr_normals_fwd(const float* depth, const float* invK, int B, int h, int w, float* normals, void* scratch,
+                   size_t scratch_bytes, void* stream);
+int sr_normals_bwd(const float* grad_normals, const float* depth, const float* invK, int B, int h, int w,
+                   float* grad_depth, void* scratch, size_t scratch_bytes, void* stream);
+size_t sr_normals_loss_workspace_bytes(int B, int h, int w);
+int sr_normals_loss_fwd(const float* normals_gt, const float* normals_pred, int B, int h, int w, float* out,
+                        void* scratch, size_t scratch_bytes, void* stream);
+int sr_normals_loss_bwd(const float* grad_out, const float* stats, const float* normals_gt, const float* normals_pred,
+                        int B, int h, int w, float* grad_pred, void* stream);
+size_t sr_grad_loss_workspace_bytes(int B, int h, int w);
+int sr_grad_loss_fwd(const float* depth_gt, const float* depth_pred, int B, int h, int w, float* out, void* scratch,
+                     size_t scratch_bytes, void* stream);
+int sr_grad_loss_bwd(const float* grad_out, const float* stats, const float* depth_gt, const float* depth_pred, int B,
+                     int h, int w, float* grad_pred, void* scratch, size_t scratch_bytes, void* stream);
+size_t sr_mv_loss_workspace_bytes(int B, int K, int h, int w);
+int sr_mv_loss_fwd(const float* depth_pred, const float* depth_gt, const float* src_depth, const float* cur_invK,
+                   const float* src_K, const float* cur_world_T_cam, const float* src_cam_T_world, int B, int K, int h,
+                   int w, float eps, float* out, uint8_t* valid_mask, float* sampled, void* scratch,
+                   size_t scratch_bytes, void* stream);
+int sr_mv_loss_bwd(const float* grad_out, const float* stats, const float* depth_pred, const float* depth_gt,
+                   const float* src_depth, const float* cur_invK, const float* src_K, const float* cur_world_T_cam,
+                   const float* src_cam_T_world, int B, int K, int h, int w, float eps, float* grad_pred,
+                   void* stream);
+size_t sr_depth_terms_workspace_bytes(int B, int h, int w);
+int sr_depth_terms_fwd(const float* depth_gt, const uint8_t* mask_b, const float* depth_pred, const float* log0,
+                       const float* log1, int h1, int w1, const float* log2, int h2, int w2, const float* log3, int h3,
+                       int w3, int B, int h, int w, float si_lambda, int gt_is_log, float* out, void* scratch,
+                       size_t scratch_bytes, void* stream);
+int sr_depth_terms_bwd(const float* grad_outs, const float* stats, const float* depth_gt, const uint8_t* mask_b,
+                       const float* depth_pred, const float* log0, const float* log1, int h1, int w1,
+                       const float* log2, int h2, int w2, const float* log3, int h3, int w3, int B, int h, int w,
+                       float si_lambda, int gt_is_log, float* grad_depth_pred, float* grad_log0, float* grad_log1, float* grad_log2,
+                       float* grad_log3, void* stream);
+
 /* ------------------------------------------------------ backward (training) -------------
  *
  * Backward of sr_dot_volume_sweep (reference: autograd through CostVolumeManager.build_cost_volume,

@@ -156,6 +156,23 @@ SIGNATURES = {
     "sr_pc_consistency": (_i, [_p, _p, _i, _i, _i, _i, _i, _f, _p, _p, _p]),
     "sr_pc_voxel_keys": (_i, [_p, _i64, C.c_double, C.c_double, C.c_double, C.c_double, _p, _p]),
     "sr_pc_voxel_mean": (_i, [_p, _p, _i64, _p, _p, _i64, _p, _p, _p]),
+    "sr_normals_workspace_bytes": (_sz, [_i, _i, _i]),
+    "sr_normals_fwd": (_i, [_p, _p, _i, _i, _i, _p, _p, _sz, _p]),
+    "sr_normals_bwd": (_i, [_p, _p, _p, _i, _i, _i, _p, _p, _sz, _p]),
+    "sr_normals_loss_workspace_bytes": (_sz, [_i, _i, _i]),
+    "sr_normals_loss_fwd": (_i, [_p, _p, _i, _i, _i, _p, _p, _sz, _p]),
+    "sr_normals_loss_bwd": (_i, [_p, _p, _p, _p, _i, _i, _i, _p, _p]),
+    "sr_grad_loss_workspace_bytes": (_sz, [_i, _i, _i]),
+    "sr_grad_loss_fwd": (_i, [_p, _p, _i, _i, _i, _p, _p, _sz, _p]),
+    "sr_grad_loss_bwd": (_i, [_p, _p, _p, _p, _i, _i, _i, _p, _p, _sz, _p]),
+    "sr_mv_loss_workspace_bytes": (_sz, [_i, _i, _i, _i]),
+    "sr_mv_loss_fwd": (_i, [_p, _p, _p, _p, _p, _p, _p, _i, _i, _i, _i, _f, _p, _p, _p, _p, _sz, _p]),
+    "sr_mv_loss_bwd": (_i, [_p, _p, _p, _p, _p, _p, _p, _p, _p, _i, _i, _i, _i, _f, _p, _p]),
+    "sr_depth_terms_workspace_bytes": (_sz, [_i, _i, _i]),
+    "sr_depth_terms_fwd": (_i, [_p, _p, _p, _p, _p, _i, _i, _p, _i, _i, _p, _i, _i, _i, _i, _i, _f, _i, _p, _p, _sz,
+                                _p]),
+    "sr_depth_terms_bwd": (_i, [_p, _p, _p, _p, _p, _p, _p, _i, _i, _p, _i, _i, _p, _i, _i, _i, _i, _i, _f, _i, _p, _p,
+                                _p, _p, _p, _p]),
 }
 
 

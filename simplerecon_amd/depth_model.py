@@ -1,6 +1,7 @@
 """DepthModel shell -- the caller of the hot path, API-compatible with the reference's
 experiment_modules/depth_model.py `DepthModel.forward` (:247-407) and `__init__` (:68-189),
-without the PyTorch-Lightning / losses / training machinery (out of scope).
+without the PyTorch-Lightning machinery (out of scope); the training objective (compute_losses,
+step) runs on the HIP loss kernels of simplerecon_amd.losses.
 
     model = DepthModel(opts)                      # opts: reference options.Options or default_options()
     outputs = model("test", cur_data, src_data, unbatched_matching_encoder_forward=True, return_mask=True)
@@ -179,6 +180,9 @@ class DepthModel(nn.Module):
         self._prior_streams = {}
         # opt-in: run both encoders under no_grad when autograd is recording (frozen-encoder fine-tune)
         self.freeze_encoders = False
+        # training objective, per depth-map size: plain attributes, out of the module registry, so that the
+        # state_dict keeps the reference's five prefixes
+        self._loss_modules = {}
 
     # ---- reference depth_model.py:191-245 ----------------------------------------------------
     def compute_matching_feats(self, cur_image, src_image, unbatched_matching_encoder_forward):
@@ -337,6 +341,54 @@ class DepthModel(nn.Module):
         return self.forward_tensors(cur_image, src_image, src_cam_T_cur_cam, cur_cam_T_src_cam, src_K, cur_invK,
                                     unbatched_matching_encoder_forward=unbatched_matching_encoder_forward,
                                     return_mask=return_mask, flip=flip)
+
+    # ---- training objective: reference depth_model.py:409-605 -----------------------------------
+    def _losses_for(self, height, width):
+        m = self._loss_modules.get((height, width))
+        if m is None:
+            from . import losses
+            from .geometry import NormalGenerator
+            m = self._loss_modules[(height, width)] = dict(
+                compute_normals=NormalGenerator(height, width), grad_loss=losses.MSGradientLoss(),
+                normals_loss=losses.NormalsLoss(), mv_depth_loss=losses.MVDepthLoss(height, width))
+        return m
+
+    def compute_normals(self, depth_b1hw, invK_b44):
+        """Normals estimated from depth (reference depth_model.py:156-159, NormalGenerator): [B,3,h,w]."""
+        return self._losses_for(*depth_b1hw.shape[-2:])["compute_normals"](depth_b1hw, invK_b44)
+
+    def compute_losses(self, cur_data, src_data, outputs):
+        """The reference's loss cocktail (depth_model.py:409-500): a dict with its nine keys; `loss` = ms_loss +
+        grad_loss + normals_loss + 0.2 mv_loss (Equation 6 of the SimpleRecon paper).  `outputs` must hold
+        "normals_pred_b3hw" and `cur_data` "normals_b3hw" (see step()).  Every term is differentiable with respect to
+        its prediction inputs."""
+        from . import losses
+        depth_gt = cur_data["depth_b1hw"]
+        depth_pred = outputs["depth_pred_s0_b1hw"]
+        m = self._losses_for(*depth_gt.shape[-2:])
+        logs = {i: outputs[f"log_depth_pred_s{i}_b1hw"] for i in range(4) if f"log_depth_pred_s{i}_b1hw" in outputs}
+        if not logs:
+            raise Exception("Could not find a valid scale to compute si loss!")
+        terms = losses.depth_terms(depth_gt, cur_data["mask_b_b1hw"], depth_pred, logs)
+        grad_loss = m["grad_loss"](depth_gt, depth_pred)
+        normals_loss = m["normals_loss"](cur_data["normals_b3hw"], outputs["normals_pred_b3hw"])
+        mv_loss = m["mv_depth_loss"](depth_pred_b1hw=depth_pred, cur_depth_b1hw=depth_gt,
+                                     src_depth_bk1hw=src_data["depth_b1hw"], cur_invK_b44=cur_data["invK_s0_b44"],
+                                     src_K_bk44=src_data["K_s0_b44"], cur_world_T_cam_b44=cur_data["world_T_cam_b44"],
+                                     src_cam_T_world_bk44=src_data["cam_T_world_b44"])
+        loss = terms["ms_loss"] + 1.0 * grad_loss + 1.0 * normals_loss + 0.2 * mv_loss
+        return {"loss": loss, "si_loss": terms["si_loss"], "grad_loss": grad_loss, "abs_loss": terms["abs_loss"],
+                "normals_loss": normals_loss, "ms_loss": terms["ms_loss"], "inv_abs_loss": terms["inv_abs_loss"],
+                "log_l1_loss": terms["log_l1_loss"], "mv_loss": mv_loss}
+
+    def step(self, phase, batch, batch_idx=0):
+        """A training / validation step (reference depth_model.py:502-605) without Lightning logging or metrics:
+        forward, normals of gt and prediction, compute_losses; returns losses["loss"]."""
+        cur_data, src_data = batch
+        outputs = self(phase, cur_data, src_data)
+        cur_data["normals_b3hw"] = self.compute_normals(cur_data["depth_b1hw"], cur_data["invK_s0_b44"])
+        outputs["normals_pred_b3hw"] = self.compute_normals(outputs["depth_pred_s0_b1hw"], cur_data["invK_s0_b44"])
+        return self.compute_losses(cur_data, src_data, outputs)["loss"]
 
     def image_prior_pyramid(self, cur_image):
         """`self.encoder(cur_image)` (reference depth_model.py:358), launched on a side HIP stream when the encoder

@@ -124,6 +124,27 @@ class Project3D(nn.Module):
         return _Project.apply(pts, K, T, self._eps)   # differentiable in the points
 
 
+class NormalGenerator(nn.Module):
+    """Normals from depth (reference geometry_utils.py:92-133): 5x5 / std 2 gaussian blur, back-projection, Sobel,
+    normalised cross product -- csrc/sr_losses.hip, differentiable in the depth map.  Holds no buffers."""
+
+    def __init__(self, height: int, width: int, smoothing_kernel_size: int = 5, smoothing_kernel_std: float = 2.0):
+        super().__init__()
+        if smoothing_kernel_size != 5 or smoothing_kernel_std != 2.0:
+            raise ValueError("the HIP normal generator implements the reference's 5x5, std 2.0 smoothing only")
+        if height < 3 or width < 3:
+            raise ValueError("NormalGenerator needs maps of at least 3x3 (reflect padding of 2)")
+        self.height, self.width = height, width
+        self.kernel_size, self.std = smoothing_kernel_size, smoothing_kernel_std
+
+    def forward(self, depth_b1hw, invK_b44):
+        """depth [B,1,h,w], invK [B,4,4] -> unit normals [B,3,h,w] (NaN where the blurred window holds a NaN)."""
+        from . import losses
+        if tuple(depth_b1hw.shape[-2:]) != (self.height, self.width):
+            raise ValueError(f"depth map {tuple(depth_b1hw.shape)} does not match {self.height}x{self.width}")
+        return losses.normals_from_depth(depth_b1hw, invK_b44)
+
+
 def pose_distance(pose_b44):
     """DVMVS pose distance (reference geometry_utils.py:178-191): (combined, R_measure, t_measure), each [B] -- the very
     values the metadata-MLP sweep computes for its pose channels (csrc/sr_dot_volume.hip: sr_geom_kernel).

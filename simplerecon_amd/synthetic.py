@@ -239,3 +239,43 @@ def raycast_scene(N, h, w, seed=0, noise=0.0, holes=0.0, device="cpu"):
                 images=rgb.round().clamp(0, 255).to(torch.uint8).reshape(N, h, w, 3).contiguous(),
                 cam_T_world=torch.as_tensor(cam_T_world, dtype=torch.float32, device=device),
                 K=torch.as_tensor(np.repeat(K[None], N, 0), dtype=torch.float32, device=device))
+
+
+def training_batch(B, K, h, w, seed=0, device="cpu", holes=0.003, matching_scale=1):
+    """A (cur_data, src_data) training batch with the reference's keys, from raycast_scene: gt depths [B,1,h,w] and
+    source depths [B,K,1,h,w] with NaN holes (random pixels and one rectangle per map, some touching the border),
+    `mask_b_b1hw` / `mask_b1hw` (finite depth inside [MIN_DEPTH, MAX_DEPTH]), images at 2h x 2w, K / invK at scale 0
+    (the depth map) and at `matching_scale`, and the poses.  Frame b * (K + 1) is the current view of batch item b,
+    the K frames after it its sources."""
+    n = B * (K + 1)
+    sc = raycast_scene(n, h, w, seed=seed, holes=holes, device="cpu")
+    img = raycast_scene(n, 2 * h, 2 * w, seed=seed, device="cpu")["images"]
+    rng = np.random.default_rng(9100 + seed)
+    depth = sc["depths"].clone()
+    depth[depth == 0] = float("nan")
+    for i in range(n):
+        rh, rw = int(rng.integers(2, max(3, h // 4))), int(rng.integers(2, max(3, w // 4)))
+        y0, x0 = int(rng.integers(0, h - rh + 1)), int(rng.integers(0, w - rw + 1))
+        if i % 2 == 0:
+            x0 = 0 if i % 4 == 0 else w - rw   # touch the border
+        depth[i, y0:y0 + rh, x0:x0 + rw] = float("nan")
+    images = (img.permute(0, 3, 1, 2).float() / 255.0 - 0.45) / 0.225
+    Ks = torch.eye(4).repeat(n, 1, 1)
+    Ks[:, :3, :3] = sc["K"]
+    cTw = sc["cam_T_world"]
+    wTc = torch.linalg.inv(cTw.double()).float()
+    cur = torch.arange(B) * (K + 1)
+    src = cur[:, None] + 1 + torch.arange(K)[None]
+    mask = torch.isfinite(depth) & (depth > MIN_DEPTH) & (depth < MAX_DEPTH)
+    cur_data = {"image_b3hw": images[cur], "depth_b1hw": depth[cur].unsqueeze(1),
+                "mask_b_b1hw": mask[cur].unsqueeze(1), "mask_b1hw": mask[cur].unsqueeze(1).float(),
+                "cam_T_world_b44": cTw[cur], "world_T_cam_b44": wTc[cur]}
+    src_data = {"image_b3hw": images[src], "depth_b1hw": depth[src].unsqueeze(2),
+                "cam_T_world_b44": cTw[src], "world_T_cam_b44": wTc[src]}
+    for s in sorted({0, matching_scale}):
+        Kx = Ks.clone()
+        Kx[:, :2] /= 2 ** s
+        invK = torch.linalg.inv(Kx.double()).float()
+        cur_data[f"K_s{s}_b44"], cur_data[f"invK_s{s}_b44"] = Kx[cur], invK[cur]
+        src_data[f"K_s{s}_b44"], src_data[f"invK_s{s}_b44"] = Kx[src], invK[src]
+    return ({k: v.to(device) for k, v in cur_data.items()}, {k: v.to(device) for k, v in src_data.items()})
