@@ -654,6 +654,59 @@ int sr_depth_terms_bwd(const float* grad_outs, const float* stats, const float* 
                        float si_lambda, int gt_is_log, float* grad_depth_pred, float* grad_log0, float* grad_log1, float* grad_log2,
                        float* grad_log3, void* stream);
 
+/* ------------------------------------------------------------- depth metrics ------
+ *
+ * The reference's depth metrics (utils/metrics_utils.py `compute_depth_metrics_batched`, used per test batch by
+ * test.py:203-455, and `compute_depth_metrics`, used by the validation step, experiment_modules/depth_model.py:573-596).
+ * tests/metrics_oracle.py restates the rules in numpy.
+ *
+ *  gt    [B,H,W]  ground-truth depth;  pred [B,h,w] predicted depth;  mask [B,H,W] uint8 (0 / nonzero) or NULL.
+ *  valid: mask != 0 when a mask is given, else gt > min_depth (fp32 compare; a NaN gt is not valid; test.py uses 0.5).
+ *  resample: SR_RESAMPLE_IDENTITY (h == H and w == W) or SR_RESAMPLE_NEAREST: gt pixel (y, x) reads pred at the pixel
+ *    F.interpolate(mode="nearest") picks, per axis src = dst if in == out, dst >> 1 if out == 2 in, else
+ *    min((int)floorf((float)dst * ((float)in / (float)out)), in - 1).  The resampled map is never written.
+ *
+ * Per valid pixel, fp32 in the reference's operation order: d = gt - pred; the five error terms |d|, |d| / gt,
+ * d * d / gt, d * d, (logf(gt) - logf(pred))^2; ratio = max(gt / pred, pred / gt), NaN when either quotient is NaN
+ * (torch.max).  Sums and counts are fp64.
+ * Rules:
+ *  - Batched rule (per frame, out_frame): invalid pixels are dropped from everything.  Each error metric is the mean of
+ *    its term over the valid pixels where that term is not NaN (nanmean), so each metric has its own count; a metric
+ *    with no such pixel (a frame with no valid pixel included) is NaN.  rmse = sqrt(mean d^2), rmse_log =
+ *    sqrt(mean log^2), the square root taken in fp64 on the fp64 mean before rounding to fp32.
+ *  - Accuracy: a_t = (number of valid pixels with ratio < t) / (number of valid pixels), rounded to fp32; a NaN ratio
+ *    is not accurate.  The thresholds compare in fp32: 1.05f (a5), 1.1f (a10, and a0 = a10), 1.25f (a25, and
+ *    a1 = a25), 1.5625f (a2), 1.953125f (a3); a ratio exactly (float)1.05 is not in a5.  mult_a != 0 multiplies them
+ *    by 100.0f in fp32 after the division.
+ *  - Quirks kept: pred < 0 (gt > 0) makes both quotients negative, so the pixel is accurate in every a-metric, while
+ *    logf(pred) is NaN and the pixel leaves rmse_log only.  pred == 0: ratio = inf (not accurate), log term inf.  pred
+ *    NaN: the pixel leaves the five error means and is not accurate.  pred = inf: the error metrics are inf.
+ *  - Pooled rule (out_pooled, `compute_depth_metrics` on the selection of every valid pixel of the batch): the same
+ *    terms with plain means: a NaN term makes its metric NaN; no valid pixel makes every metric NaN.
+ *  - Outputs: out_frame [B,12] in the reference's key order abs_diff, abs_rel, sq_rel, rmse, rmse_log, a5, a10, a25,
+ *    a0, a1, a2, a3; out_count [B] int32, the valid pixels of each frame; out_pooled [12] in the same order, or NULL.
+ *
+ * Execution: a block per (frame, tile of 4096 gt pixels) writes one fixed-order fp64 record to the scratch, and one
+ * single-workgroup finalize reduces a frame's records in a fixed order and the frames' totals in frame order: no float
+ * atomics, no host synchronisation, two runs give the same bits, and since a frame's records depend only on (H, W, h,
+ * w), frame b gives the same bits scored alone or in any batch.  Two launches per call.
+ * Refused (SR_ERR_INVALID_ARGUMENT): a NULL gt, pred, out_frame, out_count or scratch; B < 1 or B > 65535; an empty
+ * map; H*W or h*w above SR_METRICS_MAX_PIXELS (2^24: counts stay exact in fp32 and int32); identity with h != H or
+ * w != W; an unknown resample mode.  A scratch smaller than sr_depth_metrics_workspace_bytes(B, H, W) (0 for a refused
+ * shape): SR_ERR_WORKSPACE_TOO_SMALL.  The library allocates nothing.
+ *
+ * sr_depth_metrics_gather (tests only): writes out [B,H,W] = pred read through the index map of `resample`, the same
+ * device code the metrics use. */
+#define SR_RESAMPLE_IDENTITY 0
+#define SR_RESAMPLE_NEAREST 1
+#define SR_METRICS_MAX_PIXELS (1 << 24)
+size_t sr_depth_metrics_workspace_bytes(int B, int H, int W);
+int sr_depth_metrics(const float* gt, const float* pred, const uint8_t* mask, float min_depth, int B, int H, int W,
+                     int h, int w, int resample, int mult_a, float* out_frame, int32_t* out_count, float* out_pooled,
+                     void* scratch, size_t scratch_bytes, void* stream);
+int sr_depth_metrics_gather(const float* pred, int B, int H, int W, int h, int w, int resample, float* out,
+                            void* stream);
+
 /* ------------------------------------------------------ backward (training) -------------
  *
  * Backward of sr_dot_volume_sweep (reference: autograd through CostVolumeManager.build_cost_volume,

@@ -173,6 +173,9 @@ SIGNATURES = {
                                 _p]),
     "sr_depth_terms_bwd": (_i, [_p, _p, _p, _p, _p, _p, _p, _i, _i, _p, _i, _i, _p, _i, _i, _i, _i, _i, _f, _i, _p, _p,
                                 _p, _p, _p, _p]),
+    "sr_depth_metrics_workspace_bytes": (_sz, [_i, _i, _i]),
+    "sr_depth_metrics": (_i, [_p, _p, _p, _f, _i, _i, _i, _i, _i, _i, _i, _p, _p, _p, _p, _sz, _p]),
+    "sr_depth_metrics_gather": (_i, [_p, _i, _i, _i, _i, _i, _i, _p, _p]),
 }
 
 

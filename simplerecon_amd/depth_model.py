@@ -381,9 +381,25 @@ class DepthModel(nn.Module):
                 "normals_loss": normals_loss, "ms_loss": terms["ms_loss"], "inv_abs_loss": terms["inv_abs_loss"],
                 "log_l1_loss": terms["log_l1_loss"], "mv_loss": mv_loss}
 
+    def compute_metrics(self, cur_data, outputs, phase, high_res_validation=False):
+        """The metrics the reference's step logs (depth_model.py:573-596): compute_depth_metrics (pooled rule, mult_a
+        False) of depth_pred_s0_b1hw against depth_b1hw on mask_b_b1hw, or, when high_res_validation is set outside
+        training, of the prediction upsampled bilinearly (align_corners=False) against full_res_depth_b1hw on
+        full_res_mask_b_b1hw.  A dict of 0-dim device tensors in the reference's key order; no host synchronisation."""
+        from . import metrics
+        with torch.no_grad():
+            depth_pred = outputs["depth_pred_s0_b1hw"].detach()
+            if phase == "train" or not high_res_validation:
+                return metrics.masked_depth_metrics(cur_data["depth_b1hw"], depth_pred, cur_data["mask_b_b1hw"])
+            full_gt = cur_data["full_res_depth_b1hw"]
+            full_pred = torch.nn.functional.interpolate(depth_pred, full_gt.size()[-2:], mode="bilinear",
+                                                        align_corners=False)
+            return metrics.masked_depth_metrics(full_gt, full_pred, cur_data["full_res_mask_b_b1hw"])
+
     def step(self, phase, batch, batch_idx=0):
-        """A training / validation step (reference depth_model.py:502-605) without Lightning logging or metrics:
-        forward, normals of gt and prediction, compute_losses; returns losses["loss"]."""
+        """A training / validation step (reference depth_model.py:502-605) without Lightning logging: forward, normals
+        of gt and prediction, compute_losses; returns losses["loss"].  The metrics the reference logs come from
+        compute_metrics()."""
         cur_data, src_data = batch
         outputs = self(phase, cur_data, src_data)
         cur_data["normals_b3hw"] = self.compute_normals(cur_data["depth_b1hw"], cur_data["invK_s0_b44"])
