@@ -707,6 +707,83 @@ int sr_depth_metrics(const float* gt, const float* pred, const uint8_t* mask, fl
 int sr_depth_metrics_gather(const float* pred, int B, int H, int W, int h, int w, int resample, float* out,
                             void* stream);
 
+/* ------------------------------------------------------------- mesh metrics -------
+ *
+ * Scores a reconstruction against a ground truth as TransformerFusion's / NeuralRecon's mesh evaluation does (the
+ * reference README's "Mesh Fusion" table): exact nearest neighbours between two point sets, area-weighted sampling of a
+ * triangle mesh, and the Acc / Comp / Chamfer / Precision / Recall / F-score reduction.  tests/mesh_metrics_oracle.py
+ * restates every rule in numpy.  Point sets are dense [n,3] fp32; counts are below 2^31.
+ *
+ * Nearest neighbour.  For every query q of Q [M,3] and the targets P [N,3] (N >= 1):
+ *  - d2 = (dx*dx + dy*dy) + dz*dz in fp32 with dx = q.x - p.x, dy = q.y - p.y, dz = q.z - p.z, each operation rounded
+ *    on its own (no FMA contraction).  out_d2 = the minimum of d2 over all N targets, bit for bit; out_index = the
+ *    smallest target index among the targets with that d2 (numpy's argmin); out_dist = sqrtf(out_d2), correctly
+ *    rounded (numpy's fp32 np.sqrt).  The library's sqrtf is the correctly rounded one at -O3 -fno-fast-math; the
+ *    __fsqrt_rn intrinsic of this toolchain is the bare hardware approximation and is not used.
+ *  - Grid (sr_nn_grid_plan, on the host): the targets' box [min, max] (fp64, from the caller), extents e_a, E = max
+ *    e_a.  Fine cell edge h: E * 0.8^k for the smallest k in [0, 200) with prod_a (floor(e_a / h) + 1) >= N (about one
+ *    target per cell), then h * 1.25^j for the smallest j in [0, 200) whose table fits max_cells; E = 0 gives h = 1.
+ *    dims g_a = floor(e_a / h) + 1.  A coarse cell is 8^3 fine cells; the table holds 512 * prod_a ceil(g_a / 8)
+ *    <= max_cells <= SR_NN_MAX_CELLS (2^26) cells, plus one entry.
+ *  - Cell of a point: t_a = (p_a - min_a) / h in fp64, c_a = floor(t_a) clamped into [0, g_a).  Key = (coarse cell,
+ *    row-major over (x, y, z) coarse indices) * 512 + (c_x & 7) * 64 + (c_y & 7) * 8 + (c_z & 7).
+ *  - Search: Chebyshev shells of fine cells around the query's cell, r < SR_NN_FINE_SHELLS, then shells of coarse
+ *    cells until the whole grid is covered.  After every shell the query stops when its best d2 is strictly below a
+ *    lower bound of the fp32 d2 of every target outside the searched box, and a coarse cell is skipped when its own
+ *    lower bound is strictly above the best d2; both bounds hold after rounding (relative margin 2^-18; the argument is
+ *    in csrc/sr_meshmetrics.hip).  Loops are bounded by the grid dimensions and N.
+ *  - Coordinates must be finite with |x| <= SR_NN_MAX_COORD (1e18: d2 cannot overflow).  The caller passes the boxes
+ *    of both sets; a non-finite box, or one beyond the limit, is SR_ERR_INVALID_ARGUMENT.
+ * Use: sr_nn_grid_plan -> sr_nn_keys(targets) -> a stable sort of the keys (the caller's: torch.sort) ->
+ * sr_nn_build (sorted targets [N,4] fp32 = (x, y, z, bits of the int32 index), 16-byte aligned, and the cell-start
+ * table [table_entries] int32) -> sr_nn_query.  Queries may be visited in any order (query_order [M] int64, a
+ * permutation, or NULL); sorting them by sr_nn_keys keeps the lanes of a wave in neighbouring cells.  Results do not
+ * depend on the order.  out_d2, out_dist and out_index [M] are each optional.
+ *
+ * Surface sampling.  sr_sample_surface_cdf writes cdf [F] fp64, the inclusive prefix sum of the face areas
+ * 0.5 |(B - A) x (C - A)| (fp64 from the fp32 vertices), summed in a fixed order: chunks of 64 faces in face order, the
+ * chunk totals in chunk order in 256 contiguous slices.  Faces with an index outside [0, V) count as zero area (the
+ * caller refuses them).  sr_sample_surface then writes n points, sample i:
+ *    s = mix(seed), h_k = mix(s ^ (3 i + k)) for k = 0, 1, 2, in uint64 with wrap-around, where mix is splitmix64's
+ *    finaliser: z += 0x9E3779B97F4A7C15; z = (z ^ (z >> 30)) * 0xBF58476D1CE4E5B9; z = (z ^ (z >> 27)) *
+ *    0x94D049BB133111EB; z ^ (z >> 31).
+ *    x = (double)(h_0 >> 12) * 2^-52 * total (fp64, < total); face = the smallest f with cdf[f] > x, so a zero-area
+ *    face is never chosen.  u = (h_1 >> 40) * 2^-24, v = (h_2 >> 40) * 2^-24 (fp32, in [0, 1)); s = sqrtf(u);
+ *    a = 1 - s, b = s * (1 - v), c = s * v; p = (a * A + b * B) + c * C per coordinate in fp32.
+ * out_face [n] int32 (optional) receives the face.  A zero total area is refused by the caller.
+ *
+ * Metrics.  dist_pred_to_gt [m] and dist_gt_to_pred [n] are nearest-neighbour distances; threshold t > 0.  Per block
+ * of 4096 distances, fixed-order fp64 sums of the distances and of the count with dist < t (strict, fp32 compare),
+ * then one single-workgroup finalize writes out[8] fp64 = {acc = mean pred->gt, comp = mean gt->pred, chamfer =
+ * (acc + comp) / 2, precision = fraction of pred within t, recall = fraction of gt within t, f_score = 2PR / (P + R)
+ * (0 when P + R is 0), count of pred within t, count of gt within t}.  m = 0 (an empty prediction; dist_gt_to_pred is
+ * then not read): acc and precision NaN, comp and chamfer +inf, recall 0, f_score 0.  n must be >= 1.
+ *
+ * No float atomics (two runs give the same bits) and no host synchronisation in any call; the library allocates
+ * nothing.  Refused (SR_ERR_INVALID_ARGUMENT): NULL required pointers, counts outside their range, a grid whose table
+ * exceeds SR_NN_MAX_CELLS or does not have table_entries entries, a misaligned buffer; a scratch smaller than its query: SR_ERR_WORKSPACE_TOO_SMALL. */
+#define SR_NN_MAX_CELLS (1 << 26)
+#define SR_NN_FINE_SHELLS 3
+#define SR_NN_MAX_COORD 1e18
+int sr_nn_grid_plan(int64_t n_targets, const double* target_box /* host [6]: min x, y, z, max x, y, z */,
+                    int64_t max_cells, double* cell /* host */, int* dims /* host [3] */,
+                    int64_t* table_entries /* host */);
+int sr_nn_keys(const float* points, int64_t n, double min_x, double min_y, double min_z, double cell, int gx, int gy,
+               int gz, int32_t* keys, void* stream);
+int sr_nn_build(const float* targets, int64_t n, const int32_t* sorted_keys, const int64_t* order,
+                int64_t table_entries, float* sorted_targets, int32_t* cell_start, void* stream);
+int sr_nn_query(const float* queries, int64_t m, const int64_t* query_order, const float* sorted_targets, int64_t n,
+                const int32_t* cell_start, int64_t table_entries, double min_x, double min_y, double min_z, double cell,
+                int gx, int gy, int gz, float* out_d2, float* out_dist, int32_t* out_index, void* stream);
+size_t sr_sample_surface_workspace_bytes(int64_t num_faces);
+int sr_sample_surface_cdf(const float* vertices, int64_t num_vertices, const int32_t* faces, int64_t num_faces,
+                          double* cdf, void* scratch, size_t scratch_bytes, void* stream);
+int sr_sample_surface(const float* vertices, int64_t num_vertices, const int32_t* faces, int64_t num_faces,
+                      const double* cdf, int64_t n, uint64_t seed, float* out_points, int32_t* out_face, void* stream);
+size_t sr_mesh_metrics_workspace_bytes(int64_t m, int64_t n);
+int sr_mesh_metrics(const float* dist_pred_to_gt, int64_t m, const float* dist_gt_to_pred, int64_t n, float threshold,
+                    double* out, void* scratch, size_t scratch_bytes, void* stream);
+
 /* ------------------------------------------------------ backward (training) -------------
  *
  * Backward of sr_dot_volume_sweep (reference: autograd through CostVolumeManager.build_cost_volume,

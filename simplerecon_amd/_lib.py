@@ -176,6 +176,16 @@ SIGNATURES = {
     "sr_depth_metrics_workspace_bytes": (_sz, [_i, _i, _i]),
     "sr_depth_metrics": (_i, [_p, _p, _p, _f, _i, _i, _i, _i, _i, _i, _i, _p, _p, _p, _p, _sz, _p]),
     "sr_depth_metrics_gather": (_i, [_p, _i, _i, _i, _i, _i, _i, _p, _p]),
+    "sr_nn_grid_plan": (_i, [_i64, _p, _i64, _p, _p, _p]),
+    "sr_nn_keys": (_i, [_p, _i64, C.c_double, C.c_double, C.c_double, C.c_double, _i, _i, _i, _p, _p]),
+    "sr_nn_build": (_i, [_p, _i64, _p, _p, _i64, _p, _p, _p]),
+    "sr_nn_query": (_i, [_p, _i64, _p, _p, _i64, _p, _i64, C.c_double, C.c_double, C.c_double, C.c_double, _i, _i, _i,
+                         _p, _p, _p, _p]),
+    "sr_sample_surface_workspace_bytes": (_sz, [_i64]),
+    "sr_sample_surface_cdf": (_i, [_p, _i64, _p, _i64, _p, _p, _sz, _p]),
+    "sr_sample_surface": (_i, [_p, _i64, _p, _i64, _p, _i64, C.c_uint64, _p, _p, _p]),
+    "sr_mesh_metrics_workspace_bytes": (_sz, [_i64, _i64]),
+    "sr_mesh_metrics": (_i, [_p, _i64, _p, _i64, _f, _p, _p, _sz, _p]),
 }
 
 

@@ -57,12 +57,15 @@ def _mesh_folder(fuser, mask_pred_depth, fusion_use_raw_lowest_cost):
 
 
 def evaluate(model, scans, output_dir, name, split="test", batch_size=4, run_fusion=False, fuser_factory=None,
-             mask_pred_depth=False, fusion_use_raw_lowest_cost=False):
+             mask_pred_depth=False, fusion_use_raw_lowest_cost=False, gt_mesh_factory=None):
     """Scores `model` on `scans` as test.py does and writes output_dir/scores/{scan}_metrics.json (`/` in the scan
     name becomes `_`), all_scene_avg_metrics_{split}.json and all_frame_avg_metrics_{split}.json.  With run_fusion,
     `fuser_factory(scan_name)` (default: tsdf.OurFuser on the model's device) fuses the nearest-upsampled depths --
     set to -1 outside the cost volume's overall mask with mask_pred_depth, or replaced by the cost volume's lowest-cost
     depths with fusion_use_raw_lowest_cost -- and each scan's mesh goes to output_dir/meshes/<folder>/{scan}.ply.
+    With run_fusion and `gt_mesh_factory(scan_name)` returning a ground truth (a TriangleMesh, a PointCloud or a PLY path; None skips the
+    scan), the exported mesh is scored against it by mesh_metrics.mesh_metrics with its defaults, into
+    scores/{scan}_mesh_metrics.json and all_scene_avg_mesh_metrics_{split}.json.
 
     Returns (all_frame_metrics, all_scene_metrics), the two top-level ResultsAveragers with final averages."""
     device = _model_device(model)
@@ -76,6 +79,8 @@ def evaluate(model, scans, output_dir, name, split="test", batch_size=4, run_fus
 
     all_frame_metrics = metrics.ResultsAverager(name, "frame metrics")
     all_scene_metrics = metrics.ResultsAverager(name, "scene metrics")
+    score_meshes = run_fusion and gt_mesh_factory is not None
+    all_scene_mesh_metrics = metrics.ResultsAverager(name, "scene mesh metrics") if score_meshes else None
     with torch.inference_mode():
         start_time = torch.cuda.Event(enable_timing=True)
         end_time = torch.cuda.Event(enable_timing=True)
@@ -120,7 +125,19 @@ def evaluate(model, scans, output_dir, name, split="test", batch_size=4, run_fus
                 mesh_dir = os.path.join(output_dir, "meshes",
                                         _mesh_folder(fuser, mask_pred_depth, fusion_use_raw_lowest_cost))
                 os.makedirs(mesh_dir, exist_ok=True)
-                fuser.export_mesh(os.path.join(mesh_dir, f"{scan.replace('/', '_')}.ply"))
+                mesh_path = os.path.join(mesh_dir, f"{scan.replace('/', '_')}.ply")
+                fuser.export_mesh(mesh_path)
+                gt_mesh = gt_mesh_factory(scan) if score_meshes else None
+                if gt_mesh is not None:
+                    from .mesh_metrics import mesh_metrics
+                    scene_mesh_metrics = metrics.ResultsAverager(name, f"scene {scan} mesh metrics")
+                    scene_mesh_metrics.update_results(mesh_metrics(mesh_path, gt_mesh, device=device))
+                    scene_mesh_metrics.compute_final_average()
+                    all_scene_mesh_metrics.update_results(scene_mesh_metrics.final_metrics)
+                    print("\nScene mesh metrics:")
+                    scene_mesh_metrics.print_sheets_friendly(include_metrics_names=True, print_running_metrics=False)
+                    scene_mesh_metrics.output_json(
+                        os.path.join(scores_dir, f"{scan.replace('/', '_')}_mesh_metrics.json"))
 
             scene_frame_metrics.compute_final_average()
             all_scene_metrics.update_results(scene_frame_metrics.final_metrics)
@@ -138,4 +155,9 @@ def evaluate(model, scans, output_dir, name, split="test", batch_size=4, run_fus
             averager.output_json(os.path.join(scores_dir, f"all_{kind}_avg_metrics_{split}.json"))
             if kind == "scene":
                 print("")
+        if all_scene_mesh_metrics is not None and all_scene_mesh_metrics.elem_metrics_list:
+            print("\nFinal mesh metrics:")
+            all_scene_mesh_metrics.compute_final_average()
+            all_scene_mesh_metrics.pretty_print_results(print_running_metrics=False)
+            all_scene_mesh_metrics.output_json(os.path.join(scores_dir, f"all_scene_avg_mesh_metrics_{split}.json"))
     return all_frame_metrics, all_scene_metrics

@@ -155,15 +155,10 @@ def seeded_fill_(module, seed=0, gain=1.0):
     return module
 
 
-def raycast_scene(N, h, w, seed=0, noise=0.0, holes=0.0, device="cpu"):
-    """A ray-cast indoor scene for point-cloud fusion: a 5 x 3 x 5 m box room with three boxes and two spheres, seen
-    by N cameras on a slow loop inside it.  Depth is exact (up to fp32), so it is multi-view consistent except at
-    occlusions; `noise` adds N(0, noise) relative depth error and `holes` zeroes that fraction of the pixels.
-
-    Returns depths [N,h,w] fp32 (z along the optical axis), images [N,h,w,3] uint8, cam_T_world [N,4,4] fp32 and
-    K [N,3,3] fp32.  The layout, the camera path and the noise come from numpy's generator (the same seed gives the
-    same scene everywhere); the rays are cast in fp64 torch on `device`."""
-    rng = np.random.default_rng(7000 + seed)
+def _scene_layout(rng):
+    """raycast_scene's room and primitives, drawn from `rng` (the draws come first, so the camera path that follows them
+    is unchanged): room [2,3] (min, max corner) and [(kind, params, base colour)] for three boxes ((lo, hi) corners)
+    and two spheres ((centre, radius))."""
     room = np.array([[-2.5, -1.5, -2.5], [2.5, 1.5, 2.5]])
     prims = []   # (kind, params, base colour)
     for k in range(3):
@@ -175,6 +170,79 @@ def raycast_scene(N, h, w, seed=0, noise=0.0, holes=0.0, device="cpu"):
         a = 2 * np.pi * (k / 2.0 + 0.25) + rng.uniform(-0.3, 0.3)
         c = np.array([1.6 * np.cos(a), rng.uniform(-0.6, 0.4), 1.6 * np.sin(a)])
         prims.append(("sphere", (c, rng.uniform(0.25, 0.4)), rng.uniform(40, 215, size=3)))
+    return room, prims
+
+
+def _box_faces(lo, hi, spacing, inward):
+    """The six faces of an axis-aligned box as quad grids of about `spacing`, two triangles per quad; normals point
+    out of the box (into it when inward)."""
+    verts, tris, base = [], [], 0
+    for a in range(3):
+        b, c = (a + 1) % 3, (a + 2) % 3
+        nb = max(1, int(np.ceil((hi[b] - lo[b]) / spacing)))
+        nc = max(1, int(np.ceil((hi[c] - lo[c]) / spacing)))
+        ub = np.linspace(lo[b], hi[b], nb + 1)
+        uc = np.linspace(lo[c], hi[c], nc + 1)
+        gb, gc = np.meshgrid(ub, uc, indexing="ij")
+        i = np.arange(nb)[:, None] * (nc + 1) + np.arange(nc)[None, :]
+        q = np.stack([i, i + nc + 1, i + nc + 2, i + 1], -1).reshape(-1, 4)   # counter-clockwise about e_b x e_c = e_a
+        for side, val in ((-1, lo[a]), (1, hi[a])):
+            v = np.empty((gb.size, 3))
+            v[:, a], v[:, b], v[:, c] = val, gb.ravel(), gc.ravel()
+            t = np.concatenate([q[:, [0, 1, 2]], q[:, [0, 2, 3]]], 0)
+            if (side < 0) != inward:
+                t = t[:, ::-1]
+            verts.append(v)
+            tris.append(t + base)
+            base += len(v)
+    return verts, tris
+
+
+def _sphere_faces(centre, radius, spacing):
+    n_lat = max(4, int(np.ceil(np.pi * radius / spacing)))
+    n_lon = max(8, int(np.ceil(2 * np.pi * radius / spacing)))
+    th = np.linspace(0.0, np.pi, n_lat + 1)[:, None]
+    ph = np.linspace(0.0, 2 * np.pi, n_lon + 1)[None, :]
+    v = np.stack([np.sin(th) * np.cos(ph), np.cos(th) + 0 * ph, np.sin(th) * np.sin(ph)], -1).reshape(-1, 3)
+    i = np.arange(n_lat)[:, None] * (n_lon + 1) + np.arange(n_lon)[None, :]
+    q = np.stack([i, i + 1, i + n_lon + 2, i + n_lon + 1], -1).reshape(-1, 4)
+    t = np.concatenate([q[:, [0, 1, 2]], q[:, [0, 2, 3]]], 0)
+    return np.asarray(centre) + radius * v, t
+
+
+def raycast_scene_mesh(seed=0, spacing=0.02):
+    """The analytic ground truth of raycast_scene(seed=seed) as a CPU TriangleMesh: the room's walls (normals inward),
+    the three boxes and the two spheres (normals outward), tessellated at about `spacing` metres.  Primitives are
+    tessellated whole: parts inside another primitive are kept, pole triangles of the spheres have zero area."""
+    from .tsdf import TriangleMesh
+    room, prims = _scene_layout(np.random.default_rng(7000 + seed))
+    verts, tris = _box_faces(room[0], room[1], spacing, inward=True)
+    base = sum(len(v) for v in verts)
+    for kind, par, _ in prims:
+        if kind == "box":
+            vs, ts = _box_faces(par[0], par[1], spacing, inward=False)
+        else:
+            v, t = _sphere_faces(par[0], par[1], spacing)
+            vs, ts = [v], [t]
+        for v, t in zip(vs, ts):
+            verts.append(v)
+            tris.append(t + base)
+            base += len(v)
+    v = torch.from_numpy(np.concatenate(verts, 0).astype(np.float32))
+    f = torch.from_numpy(np.concatenate(tris, 0).astype(np.int32))
+    return TriangleMesh(v, f)
+
+
+def raycast_scene(N, h, w, seed=0, noise=0.0, holes=0.0, device="cpu"):
+    """A ray-cast indoor scene for point-cloud fusion: a 5 x 3 x 5 m box room with three boxes and two spheres, seen
+    by N cameras on a slow loop inside it.  Depth is exact (up to fp32), so it is multi-view consistent except at
+    occlusions; `noise` adds N(0, noise) relative depth error and `holes` zeroes that fraction of the pixels.
+
+    Returns depths [N,h,w] fp32 (z along the optical axis), images [N,h,w,3] uint8, cam_T_world [N,4,4] fp32 and
+    K [N,3,3] fp32.  The layout, the camera path and the noise come from numpy's generator (the same seed gives the
+    same scene everywhere); the rays are cast in fp64 torch on `device`."""
+    rng = np.random.default_rng(7000 + seed)
+    room, prims = _scene_layout(rng)
 
     f = 577.87 * (w / 640.0)
     K = np.array([[f, 0.0, (w - 1) / 2.0 + 0.3], [0.0, f, (h - 1) / 2.0 - 0.2], [0.0, 0.0, 1.0]])

@@ -11,6 +11,8 @@ Mesh export (`TSDF.extract_mesh` / `TSDF.save`, `OurFuser.export_mesh` / `get_me
 (`sr_mesh_count` + `sr_mesh_emit`, csrc/sr_mesh.hip) and returns a `TriangleMesh`; the reference copies the volume to the
 host and runs skimage + trimesh there (tools/tsdf.py:128-168).  The surface rules are in include/simplerecon_hip.h.
 
+`TSDF.from_mesh` and `OurFuser(gt_path=...)` size the volume from a ground-truth mesh read by `ply.read_ply`.
+
 Not provided: `to_mesh` (its contract is a trimesh.Trimesh) and the open3d fuser.  There is no CPU fallback: tensors
 must live on the GPU.
 """
@@ -133,6 +135,22 @@ class TSDF:
         vol._origin_f32 = origin.clone()
         vol._generated = True
         return vol
+
+    @classmethod
+    def from_mesh(cls, mesh: TriangleMesh, voxel_size: float, device="cuda"):
+        """A volume over the mesh's vertex bounds padded by 3 voxels on every side (tsdf.py:51-67): bounds computed in
+        fp64 from the vertices, then from_bounds."""
+        v = mesh.vertices.detach().cpu().double().numpy().reshape(-1, 3)
+        if len(v) == 0:
+            raise ValueError("TSDF.from_mesh: the mesh has no vertices")
+        if not np.isfinite(v).all():
+            raise ValueError("TSDF.from_mesh: the mesh has non-finite vertices")
+        lo, hi = v.min(0), v.max(0)
+        bounds = {}
+        for i, a in enumerate("xyz"):
+            bounds[a + "min"] = float(lo[i] - 3 * voxel_size)
+            bounds[a + "max"] = float(hi[i] + 3 * voxel_size)
+        return cls.from_bounds(bounds, voxel_size, device=device)
 
     @classmethod
     def generate_voxel_coords(cls, origin: torch.Tensor, volume_dims: Tuple[int, int, int], voxel_size: float):
@@ -281,18 +299,24 @@ class TSDFFuser:
 
 
 class OurFuser:
-    """The fuser behind `--depth_fuser ours` (reference tools/fusers_helper.py:25-83): a dense TSDF over the given bounds
-    (default: the reference's +-10 m cube when no ground-truth mesh limits the extent)."""
+    """The fuser behind `--depth_fuser ours` (reference tools/fusers_helper.py:25-83): a dense TSDF over the bounds of
+    the ground-truth mesh at `gt_path` (a PLY file, padded by 3 voxels: TSDF.from_mesh), else over the given bounds
+    (default: the reference's +-10 m cube)."""
 
     def __init__(self, gt_path=None, fusion_resolution=0.04, max_fusion_depth=3, fuse_color=False, bounds=None,
                  device="cuda"):
-        if gt_path:
-            raise NotImplementedError("bounds from a ground-truth mesh need trimesh; pass bounds=dict(xmin=..., ...)")
         self.fusion_resolution = fusion_resolution
         self.max_fusion_depth = max_fusion_depth
-        if bounds is None:
-            bounds = dict(xmin=-10.0, xmax=10.0, ymin=-10.0, ymax=10.0, zmin=-10.0, zmax=10.0)
-        tsdf_pred = TSDF.from_bounds(bounds, voxel_size=fusion_resolution, device=device)
+        if gt_path:
+            from .ply import read_ply
+            gt_mesh = read_ply(gt_path)
+            if not isinstance(gt_mesh, TriangleMesh):
+                raise ValueError(f"{gt_path} holds a point cloud, not a mesh")
+            tsdf_pred = TSDF.from_mesh(gt_mesh, voxel_size=fusion_resolution, device=device)
+        else:
+            if bounds is None:
+                bounds = dict(xmin=-10.0, xmax=10.0, ymin=-10.0, ymax=10.0, zmin=-10.0, zmax=10.0)
+            tsdf_pred = TSDF.from_bounds(bounds, voxel_size=fusion_resolution, device=device)
         self.tsdf_fuser_pred = TSDFFuser(tsdf_pred, max_depth=max_fusion_depth)
 
     def fuse_frames(self, depths_b1hw, K_b44, cam_T_world_b44, color_b3hw=None):
