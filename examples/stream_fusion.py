@@ -1,11 +1,13 @@
 """End-to-end streaming example on synthetic data: posed frames -> online keyframe / source selection
 (simplerecon_amd.keyframes) -> DepthModel.forward (image-prior + matching encoders, plane-sweep cost volume, cost-volume
-encoder and UNet++ decoder, all on HIP kernels) -> TSDF fusion of the predicted depth (simplerecon_amd.tsdf) -> with
+encoder and UNet++ decoder, all on HIP kernels) -> TSDF fusion of the predicted depth (simplerecon_amd.tsdf; with
+--fuser open3d the sparse, unbounded colour volume of simplerecon_amd.scalable_tsdf, --color for vertex colours) -> with
 --mesh, marching cubes on the GPU and a PLY file; with --point-cloud, multi-view consistency fusion of the same depth maps
 into a coloured point cloud (simplerecon_amd.point_cloud, the reference's pc_fusion.py).  It mirrors what the reference's test.py does per scan
 (test.py:210-410) without datasets or checkpoints.
 
     python examples/stream_fusion.py [--frames 120] [--height 192] [--width 256] [--mesh out.ply] [--point-cloud out.ply]
+                                     [--fuser {ours,open3d}] [--color]
 
 Weights are random, so the depth maps are meaningless -- the point is the data flow and the API.
 """
@@ -21,6 +23,7 @@ from simplerecon_amd import depth_model as dm  # noqa: E402
 from simplerecon_amd import keyframes as kf  # noqa: E402
 from simplerecon_amd import synthetic  # noqa: E402
 from simplerecon_amd.point_cloud import PointCloudFuser  # noqa: E402
+from simplerecon_amd.scalable_tsdf import Open3DFuser  # noqa: E402
 from simplerecon_amd.tsdf import OurFuser  # noqa: E402
 
 
@@ -48,15 +51,18 @@ def camera_path(n, seed=0):
 
 
 def run(frames=120, height=192, width=256, views=8, device="cuda:0", verbose=True, mesh_path=None,
-        point_cloud_path=None):
+        point_cloud_path=None, fuser_name="ours", color=False):
     opts = dm.default_options(image_width=width, image_height=height, model_num_views=views)
     model = dm.DepthModel(opts)
     for i, m in enumerate((model.encoder, model.matching_model, model.cost_volume_net, model.depth_decoder,
                            model.cost_volume.mlp)):
         synthetic.seeded_fill_(m, seed=20 + i)
     model = model.to(device).eval()
-    fuser = OurFuser(bounds=dict(xmin=-2.0, xmax=6.0, ymin=-2.0, ymax=2.0, zmin=-1.0, zmax=7.0), max_fusion_depth=3.0,
-                     device=device)
+    if fuser_name == "open3d":   # sparse: grows where the depth lands, no bounds needed
+        fuser = Open3DFuser(max_fusion_depth=3.0, fuse_color=color, device=device)
+    else:
+        fuser = OurFuser(bounds=dict(xmin=-2.0, xmax=6.0, ymin=-2.0, ymax=2.0, zmin=-1.0, zmax=7.0),
+                         max_fusion_depth=3.0, fuse_color=color, device=device)
     pc_fuser = PointCloudFuser(fusion_size=(height, width)) if point_cloud_path else None   # pc_fusion.py:122-150
     cfg = kf.DVMVS_Config
     buf = kf.KeyframeBuffer(cfg.test_keyframe_buffer_size, cfg.test_keyframe_pose_distance, cfg.test_optimal_t_measure,
@@ -87,14 +93,20 @@ def run(frames=120, height=192, width=256, views=8, device="cuda:0", verbose=Tru
         with torch.inference_mode():
             out = model("test", cur, src, unbatched_matching_encoder_forward=False, return_mask=True)
             depth = out["depth_pred_s0_b1hw"]
-            fuser.fuse_frames(depth, K_depth[None].to(device), cur["cam_T_world_b44"], None)
+            fuser.fuse_frames(depth, K_depth[None].to(device), cur["cam_T_world_b44"], cur["image_b3hw"])
             if pc_fuser is not None:
                 pc_fuser.fuse_frames(depth, K_depth[None].to(device), cur["cam_T_world_b44"], cur["image_b3hw"])
         predicted += 1
-    vol = fuser.tsdf_fuser_pred
-    touched = int((vol.tsdf_weights > 0).sum())
+    if fuser_name == "open3d":
+        vol = fuser.volume
+        touched = int((vol.weights > 0).sum())
+        shape = f"{vol.num_blocks} blocks of 16^3"
+    else:
+        vol = fuser.tsdf_fuser_pred
+        touched = int((vol.tsdf_weights > 0).sum())
+        shape = str(tuple(vol.shape))
     if verbose:
-        print(f"{frames} frames -> {predicted} keyframes predicted and fused; TSDF {tuple(vol.shape)}: {touched} voxels touched")
+        print(f"{frames} frames -> {predicted} keyframes predicted and fused; TSDF {shape}: {touched} voxels touched")
     if mesh_path:
         fuser.export_mesh(mesh_path)   # test.py:405-410
         if verbose:
@@ -114,5 +126,9 @@ if __name__ == "__main__":
     ap.add_argument("--width", type=int, default=256)
     ap.add_argument("--mesh", default=None, help="write the fused surface to this .ply file")
     ap.add_argument("--point-cloud", default=None, help="write the fused point cloud to this .ply file")
+    ap.add_argument("--fuser", choices=["ours", "open3d"], default="ours",
+                    help="ours: dense TSDF over fixed bounds; open3d: sparse colour TSDF, unbounded")
+    ap.add_argument("--color", action="store_true", help="fuse vertex colours (the open3d fuser; ours ignores it)")
     a = ap.parse_args()
-    run(a.frames, a.height, a.width, mesh_path=a.mesh, point_cloud_path=a.point_cloud)
+    run(a.frames, a.height, a.width, mesh_path=a.mesh, point_cloud_path=a.point_cloud, fuser_name=a.fuser,
+        color=a.color)

@@ -784,6 +784,73 @@ size_t sr_mesh_metrics_workspace_bytes(int64_t m, int64_t n);
 int sr_mesh_metrics(const float* dist_pred_to_gt, int64_t m, const float* dist_gt_to_pred, int64_t n, float threshold,
                     double* out, void* scratch, size_t scratch_bytes, void* stream);
 
+/* ------------------------------------------------------------- sparse TSDF --------
+ *
+ * Sparse colour TSDF fusion: the reference's second depth fuser (tools/fusers_helper.py, Open3DFuser, on Open3D's legacy
+ * ScalableTSDFVolume with RGB8 colour).  The volume is a set of blocks of 16^3 voxels that grows where the depth maps
+ * land.  The rules below restate Open3D's integrate / extract_triangle_mesh from memory of its algorithm: they are this
+ * project's contract, and bit parity with Open3D itself is unpinned (nobody could check it against Open3D).
+ * tests/sparse_tsdf_oracle.py restates every rule in numpy.
+ *
+ * Parameters: voxel_length vl, sdf_trunc (3 vl for the fuser), unit = 16 vl; 2 sdf_trunc < unit.
+ * Block key: (bx, by, bz) with each coordinate in [-2^20, 2^20), key = (bx + 2^20) << 42 | (by + 2^20) << 21 |
+ * (bz + 2^20) >= 0: ascending keys are x-major order.  SR_STSDF_KEY_NONE (-1) marks an empty candidate.
+ * Voxel l of a block (l = (lx * 16 + ly) * 16 + lz, z fastest) has the global index g = 16 b + (lx, ly, lz).
+ * Pool: [capacity][5][4096] fp32 per block slot: tsdf, weight, red, green, blue (0..255).  Fresh blocks are all zero.
+ * A frame's depth D [h,w] fp32 has already had values above max_depth set to 0 (the caller's preprocessing).
+ *
+ * Touch (fp64; sr_stsdf_touch).  Pixels (u, v) with u % 4 == 0, v % 4 == 0 and d > 0 (NaN fails): p_cam = ((u - cx) d
+ * / fx, (v - cy) d / fy, d); p_world = M p_cam with M = inv(cam_T_world) rows 0..2, computed by the caller in fp64,
+ * each row ((m0 x + m1 y) + m2 z) + m3.  Per axis lo = floor((p - sdf_trunc) / unit), hi = floor((p + sdf_trunc) /
+ * unit); every block in [lo, hi]^3 is touched by the frame.  A non-finite p_world or a block outside the key range is
+ * skipped.  Output cand_keys [B][S][8] int64, S = ceil(h/4) * ceil(w/4), pixel-major: the up to 8 blocks of the
+ * pixel, SR_STSDF_KEY_NONE for the rest.
+ * Touch masks (sr_stsdf_block_masks): masks[inverse[i]] |= 1 << (i / cand_per_frame) for every candidate i that is
+ * not SR_STSDF_KEY_NONE (inverse: the caller's torch.unique of cand_keys; masks zeroed by the caller); cand_keys
+ * is sr_stsdf_touch's output for B <= 64 frames (n_cand = B * cand_per_frame, cand_per_frame = 8 S).
+ *
+ * Integration (fp32, no FMA contraction, in this order; sr_stsdf_integrate).  Each block of the call (slot >= 0)
+ * applies the frames of its mask in ascending frame order, and no others; per voxel and frame f:
+ *  - centre c = ((float)g + 0.5f) * vl per axis; p = R c + t row by row as ((r0 x + r1 y) + r2 z) + t; skip if
+ *    p.z <= 0.
+ *  - u_f = ((p.x * fx) / p.z + cx) + 0.5f, v_f likewise; skip unless 0.0001f <= u_f < w - 0.0001f and 0.0001f <= v_f
+ *    < h - 0.0001f; u = (int)u_f, v = (int)v_f.  D = depth[v][u]; skip if D <= 0.
+ *  - a = (u - cx) / fx, b = (v - cy) / fy, sdf = (D - p.z) * sqrtf((1 + a * a) + b * b) (correctly rounded sqrtf).
+ *  - if sdf > -sdf_trunc (NaN fails): t' = min(1, sdf / sdf_trunc); tsdf = (tsdf * W + t') / (W + 1);
+ *    rgb = (rgb * W + c) / (W + 1) per channel, c the pixel's uint8 colour (colour NULL: 178); W = W + 1.
+ * frames [B][SR_STSDF_FRAME_FLOATS] fp32: R row-major [0,9), t [9,12), fx, fy, cx, cy [12,16) (cam_T_world and K).
+ * color [B][3][h][w] uint8 or NULL.
+ *
+ * Mesh extraction (sr_stsdf_mesh_count, sr_stsdf_mesh_emit).  The rules of "mesh extraction" above, on the fp32 tsdf
+ * (clamped to [-1, 1], not rounded through fp16), level 0, where a voxel with W == 0 or in an unallocated block is NaN.
+ * Blocks in ascending key order (keys [n] sorted ascending, slots [n] their pool slots).  Vertices are numbered block
+ * by block, then by l, then x, y, z edge; faces likewise by block, l, loop order.  Voxel-unit positions p use the
+ * global g (exact while |g| < 2^24); vertex = (p + 0.5f) * vl; vertex colour = (c0 + t * (c1 - c0)) / 255 per channel,
+ * c0 / c1 the rgb of the edge's lower / upper voxel and t the edge parameter.  No normals.
+ * sr_stsdf_mesh_count writes block_counts [2][n] int32 (vertices, faces of each block).  The caller forms
+ * block_offsets [2][n] int64, their exclusive prefix sums, and reads the totals; sr_stsdf_mesh_emit then writes
+ * vertices [V,3] fp32, colors [V,3] fp32 and faces [F,3] int32, with vertex_table [n][3][4096] int32 as scratch.
+ *
+ * The library allocates nothing and no call synchronises with the host.  Only the touch masks use atomics (integer OR:
+ * the result does not depend on the order), so every output is the same bits on every run.  Refused
+ * (SR_ERR_INVALID_ARGUMENT): NULL required pointers, B outside [1, 64], h or w outside [1, 2^15], 2 sdf_trunc >= unit,
+ * non-positive voxel_length or sdf_trunc, a slot outside [0, capacity). */
+#define SR_STSDF_FRAME_FLOATS 16
+#define SR_STSDF_MAX_FRAMES 64
+#define SR_STSDF_KEY_NONE (-1ll)
+int sr_stsdf_touch(const float* depth, int B, int h, int w, const double* frames_inv /* [B][16]: M rows 0..2, fx, fy,
+                   cx, cy */, double sdf_trunc, double unit, int64_t* cand_keys, void* stream);
+int sr_stsdf_block_masks(const int64_t* cand_keys, const int64_t* inverse, int64_t n_cand, int64_t cand_per_frame,
+                         uint64_t* masks, void* stream);
+int sr_stsdf_integrate(float* pool, int64_t capacity, const int64_t* block_keys, const int64_t* block_slots,
+                       const uint64_t* block_masks, int64_t n_blocks, const float* frames, const float* depth,
+                       const uint8_t* color, int B, int h, int w, float voxel_length, float sdf_trunc, void* stream);
+int sr_stsdf_mesh_count(const float* pool, int64_t capacity, const int64_t* keys, const int64_t* slots, int64_t n_blocks,
+                        int32_t* block_counts, void* stream);
+int sr_stsdf_mesh_emit(const float* pool, int64_t capacity, const int64_t* keys, const int64_t* slots, int64_t n_blocks,
+                       float voxel_length, const int64_t* block_offsets, int64_t num_vertices, int64_t num_faces,
+                       int32_t* vertex_table, float* vertices, float* colors, int32_t* faces, void* stream);
+
 /* ------------------------------------------------------ backward (training) -------------
  *
  * Backward of sr_dot_volume_sweep (reference: autograd through CostVolumeManager.build_cost_volume,

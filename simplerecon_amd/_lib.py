@@ -186,6 +186,11 @@ SIGNATURES = {
     "sr_sample_surface": (_i, [_p, _i64, _p, _i64, _p, _i64, C.c_uint64, _p, _p, _p]),
     "sr_mesh_metrics_workspace_bytes": (_sz, [_i64, _i64]),
     "sr_mesh_metrics": (_i, [_p, _i64, _p, _i64, _f, _p, _p, _sz, _p]),
+    "sr_stsdf_touch": (_i, [_p, _i, _i, _i, _p, C.c_double, C.c_double, _p, _p]),
+    "sr_stsdf_block_masks": (_i, [_p, _p, _i64, _i64, _p, _p]),
+    "sr_stsdf_integrate": (_i, [_p, _i64, _p, _p, _p, _i64, _p, _p, _p, _i, _i, _i, _f, _f, _p]),
+    "sr_stsdf_mesh_count": (_i, [_p, _i64, _p, _p, _i64, _p, _p]),
+    "sr_stsdf_mesh_emit": (_i, [_p, _i64, _p, _p, _i64, _f, _p, _i64, _i64, _p, _p, _p, _p, _p]),
 }
 
 

@@ -46,23 +46,30 @@ def _model_device(model):
     return torch.device("cuda")
 
 
-def _mesh_folder(fuser, mask_pred_depth, fusion_use_raw_lowest_cost):
-    """test.py's mesh folder name: {fusion_resolution}_{max depth}_ours, then _masked / _raw_cv."""
-    name = f"{getattr(fuser, 'fusion_resolution', 0.04)}_{getattr(fuser, 'max_fusion_depth', 3)}_ours"
+def _mesh_folder(fuser, mask_pred_depth, fusion_use_raw_lowest_cost, fuse_color=False):
+    """test.py's mesh folder name (test.py:139-146): {fusion_resolution}_{max depth}_{depth fuser}, then _masked /
+    _color / _raw_cv.  The fuser's name is its `depth_fuser` attribute ("ours" when it has none)."""
+    name = (f"{getattr(fuser, 'fusion_resolution', 0.04)}_{getattr(fuser, 'max_fusion_depth', 3)}_"
+            f"{getattr(fuser, 'depth_fuser', 'ours')}")
     if mask_pred_depth:
         name += "_masked"
+    if fuse_color:
+        name += "_color"
     if fusion_use_raw_lowest_cost:
         name += "_raw_cv"
     return name
 
 
 def evaluate(model, scans, output_dir, name, split="test", batch_size=4, run_fusion=False, fuser_factory=None,
-             mask_pred_depth=False, fusion_use_raw_lowest_cost=False, gt_mesh_factory=None):
+             mask_pred_depth=False, fusion_use_raw_lowest_cost=False, gt_mesh_factory=None, depth_fuser="ours",
+             fuse_color=False):
     """Scores `model` on `scans` as test.py does and writes output_dir/scores/{scan}_metrics.json (`/` in the scan
     name becomes `_`), all_scene_avg_metrics_{split}.json and all_frame_avg_metrics_{split}.json.  With run_fusion,
-    `fuser_factory(scan_name)` (default: tsdf.OurFuser on the model's device) fuses the nearest-upsampled depths --
+    `fuser_factory(scan_name)` (default: on the model's device, tsdf.OurFuser for depth_fuser="ours" or
+    scalable_tsdf.Open3DFuser(fuse_color=fuse_color) for depth_fuser="open3d") fuses the nearest-upsampled depths --
     set to -1 outside the cost volume's overall mask with mask_pred_depth, or replaced by the cost volume's lowest-cost
-    depths with fusion_use_raw_lowest_cost -- and each scan's mesh goes to output_dir/meshes/<folder>/{scan}.ply.
+    depths with fusion_use_raw_lowest_cost -- and each scan's mesh goes to output_dir/meshes/<folder>/{scan}.ply, <folder> as test.py names it:
+    {fusion_resolution}_{max depth}_{fuser's depth_fuser}[_masked][_color][_raw_cv].
     With run_fusion and `gt_mesh_factory(scan_name)` returning a ground truth (a TriangleMesh, a PointCloud or a PLY path; None skips the
     scan), the exported mesh is scored against it by mesh_metrics.mesh_metrics with its defaults, into
     scores/{scan}_mesh_metrics.json and all_scene_avg_mesh_metrics_{split}.json.
@@ -71,11 +78,19 @@ def evaluate(model, scans, output_dir, name, split="test", batch_size=4, run_fus
     device = _model_device(model)
     scores_dir = os.path.join(output_dir, "scores")
     os.makedirs(scores_dir, exist_ok=True)
+    if depth_fuser not in ("ours", "open3d"):
+        raise ValueError(f"depth_fuser must be 'ours' or 'open3d', got {depth_fuser!r}")
     if fuser_factory is None and run_fusion:
-        from .tsdf import OurFuser
+        if depth_fuser == "open3d":
+            from .scalable_tsdf import Open3DFuser
 
-        def fuser_factory(_scan):
-            return OurFuser(device=device)
+            def fuser_factory(_scan):
+                return Open3DFuser(fuse_color=fuse_color, device=device)
+        else:
+            from .tsdf import OurFuser
+
+            def fuser_factory(_scan):
+                return OurFuser(device=device)
 
     all_frame_metrics = metrics.ResultsAverager(name, "frame metrics")
     all_scene_metrics = metrics.ResultsAverager(name, "scene metrics")
@@ -123,7 +138,7 @@ def evaluate(model, scans, output_dir, name, split="test", batch_size=4, run_fus
 
             if run_fusion:
                 mesh_dir = os.path.join(output_dir, "meshes",
-                                        _mesh_folder(fuser, mask_pred_depth, fusion_use_raw_lowest_cost))
+                                        _mesh_folder(fuser, mask_pred_depth, fusion_use_raw_lowest_cost, fuse_color))
                 os.makedirs(mesh_dir, exist_ok=True)
                 mesh_path = os.path.join(mesh_dir, f"{scan.replace('/', '_')}.ply")
                 fuser.export_mesh(mesh_path)

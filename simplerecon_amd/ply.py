@@ -4,7 +4,7 @@
                    -> point_cloud.PointCloud otherwise
 
 Reads `binary_little_endian` and `ascii` files.  Vertex properties may have any scalar type: `x, y, z` are kept as fp32
-and, for point clouds, `red, green, blue` as uint8; every other property (ScanNet's `alpha`, normals, ...) is skipped.
+and `red, green, blue` as uint8 for point clouds, as fp32 in [0, 1] (integer values / 255) for meshes; every other property (ScanNet's `alpha`, normals, ...) is skipped.
 Faces are `list <uchar|char|ushort|short|int|uint> <int|uint> vertex_indices` (or `vertex_index`); triangles are taken
 as they are and polygons with more vertices are fan-triangulated around their first vertex (v0, vi, vi+1).  Other
 elements (edges, materials, ...) are skipped.  It reads everything TriangleMesh.write_ply and PointCloud.write_ply
@@ -168,8 +168,8 @@ def _triangles(faces, nverts, name):
 
 
 def read_ply(path):
-    """Reads a PLY file: a CPU tsdf.TriangleMesh (vertices fp32, faces int32, normals None) when it has a face element,
-    else a CPU point_cloud.PointCloud (points fp32, colours uint8 when red / green / blue are present)."""
+    """Reads a PLY file: a CPU tsdf.TriangleMesh (vertices fp32, faces int32, normals None, colors [V,3] fp32 in [0, 1]
+    when red / green / blue are present, else None) when it has a face element, else a CPU point_cloud.PointCloud (points fp32, colours uint8 when red / green / blue are present)."""
     from .point_cloud import PointCloud
     from .tsdf import TriangleMesh
     with open(path, "rb") as fh:
@@ -198,7 +198,14 @@ def read_ply(path):
         if key is None:
             raise ValueError(f"{path}: the face element has no vertex_indices list")
         tri = _triangles(f[key], len(pts), str(path))
-        return TriangleMesh(torch.from_numpy(np.ascontiguousarray(pts)), torch.from_numpy(tri.astype(np.int32)))
+        colors = None
+        if all(c in v and not isinstance(v[c], list) for c in ("red", "green", "blue")):
+            # integer colours are 0..255 (write_ply's uchar); float colours are taken as they are, in [0, 1]
+            chans = [np.asarray(v[c]) for c in ("red", "green", "blue")]
+            colors = torch.from_numpy(np.stack([a.astype(np.float32) / np.float32(255) if a.dtype.kind in "iu"
+                                                else a.astype(np.float32) for a in chans], 1).reshape(-1, 3).copy())
+        return TriangleMesh(torch.from_numpy(np.ascontiguousarray(pts)), torch.from_numpy(tri.astype(np.int32)),
+                            colors=colors)
     cols = None
     if all(c in v and not isinstance(v[c], list) for c in ("red", "green", "blue")):
         cols = torch.from_numpy(np.stack([np.asarray(v[c]).astype(np.uint8) for c in ("red", "green", "blue")], 1)

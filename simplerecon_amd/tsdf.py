@@ -13,8 +13,9 @@ host and runs skimage + trimesh there (tools/tsdf.py:128-168).  The surface rule
 
 `TSDF.from_mesh` and `OurFuser(gt_path=...)` size the volume from a ground-truth mesh read by `ply.read_ply`.
 
-Not provided: `to_mesh` (its contract is a trimesh.Trimesh) and the open3d fuser.  There is no CPU fallback: tensors
-must live on the GPU.
+The reference's other fuser, `depth_fuser="open3d"` (sparse, unbounded, with colour), is
+`scalable_tsdf.Open3DFuser`.  Not provided: `to_mesh` (its contract is a trimesh.Trimesh).  There is no CPU fallback:
+tensors must live on the GPU.
 """
 import ctypes as C
 import os
@@ -28,19 +29,24 @@ from . import _lib
 
 class TriangleMesh:
     """An indexed triangle mesh: `vertices` [V,3] fp32, `faces` [F,3] int32 (counter-clockwise seen from the side of
-    increasing TSDF, i.e. from free space), `normals` [V,3] fp32 unit vectors or None."""
+    increasing TSDF, i.e. from free space), `normals` [V,3] fp32 unit vectors or None, `colors` [V,3] fp32 in [0, 1]
+    or None."""
 
-    def __init__(self, vertices: torch.Tensor, faces: torch.Tensor, normals: Optional[torch.Tensor] = None):
+    def __init__(self, vertices: torch.Tensor, faces: torch.Tensor, normals: Optional[torch.Tensor] = None,
+                 colors: Optional[torch.Tensor] = None):
         self.vertices = vertices
         self.faces = faces
         self.normals = normals
+        self.colors = colors
 
     def cpu(self):
-        return TriangleMesh(self.vertices.cpu(), self.faces.cpu(), None if self.normals is None else self.normals.cpu())
+        return TriangleMesh(self.vertices.cpu(), self.faces.cpu(), None if self.normals is None else self.normals.cpu(),
+                            None if self.colors is None else self.colors.cpu())
 
     def write_ply(self, path):
-        """Binary little-endian PLY: `float x,y,z` (+ `nx,ny,nz`) per vertex and a `list uchar int vertex_indices` face
-        element -- the layout trimesh writes."""
+        """Binary little-endian PLY: `float x,y,z` (+ `nx,ny,nz`) (+ `uchar red,green,blue`, clamp(floor(c * 255 + 0.5))
+        of the [0, 1] colours) per vertex and a `list uchar int vertex_indices` face element -- the layout trimesh
+        writes."""
         v = self.vertices.detach().cpu().numpy().astype("<f4", copy=False).reshape(-1, 3)
         f = self.faces.detach().cpu().numpy().astype("<i4", copy=False).reshape(-1, 3)
         names = ["x", "y", "z"]
@@ -48,14 +54,24 @@ class TriangleMesh:
         if self.normals is not None:
             names += ["nx", "ny", "nz"]
             cols.append(self.normals.detach().cpu().numpy().astype("<f4", copy=False).reshape(-1, 3))
-        vrec = np.empty(len(v), dtype=[(n, "<f4") for n in names])
+        fields = [(n, "<f4") for n in names]
+        if self.colors is not None:
+            fields += [(n, "u1") for n in ("red", "green", "blue")]
+        vrec = np.empty(len(v), dtype=fields)
         for idx, n in enumerate(names):
             vrec[n] = cols[idx // 3][:, idx % 3]
+        if self.colors is not None:
+            c = self.colors.detach().cpu().numpy().astype(np.float32, copy=False).reshape(-1, 3)
+            c8 = np.clip(np.floor(c * np.float32(255) + np.float32(0.5)), 0, 255).astype(np.uint8)
+            for idx, n in enumerate(("red", "green", "blue")):
+                vrec[n] = c8[:, idx]
         frec = np.empty(len(f), dtype=[("n", "u1"), ("i", "<i4", (3,))])
         frec["n"] = 3
         frec["i"] = f
         header = ["ply", "format binary_little_endian 1.0", f"element vertex {len(v)}"]
         header += [f"property float {n}" for n in names]
+        if self.colors is not None:
+            header += [f"property uchar {n}" for n in ("red", "green", "blue")]
         header += [f"element face {len(f)}", "property list uchar int vertex_indices", "end_header"]
         with open(path, "wb") as fh:
             fh.write(("\n".join(header) + "\n").encode("ascii"))
