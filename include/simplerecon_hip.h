@@ -43,11 +43,9 @@ extern "C" {
  * integer; the split modes take 0 = off (fp32 MFMA: the product path), 1 = bf16 pieces, 2 = f16 pieces (-1 = the unknown
  * string an environment variable held: the entry points that honour the mode return SR_ERR_INVALID_ARGUMENT). */
 enum {
-  SR_OPT_MLP_SPLIT = 0, SR_OPT_WINO_SPLIT, SR_OPT_WINO_XCD, SR_OPT_WINO_STAGGER, SR_OPT_WINO_WG_PER_CU, SR_OPT_WINO_NT,
-  SR_OPT_WINO_KSPLIT, SR_OPT_CONV_WINO, SR_OPT_CONV_TILE, SR_OPT_CONV_KSPLIT, SR_OPT_MLP_VEC_STORE, SR_OPT_MLP_XCD,
-  SR_OPT_MLP_BWD_VALU, SR_OPT_T16_XCD, SR_OPT_POOL_BW, SR_OPT_POOL_XCD, SR_OPT_PW_NT, SR_OPT_PW_KS, SR_OPT_PT_CFG, SR_OPT_PT_KS,
-  SR_OPT_DOT_LDS, SR_OPT_DOT_QUAD, SR_OPT_DOT_LDS_G, SR_OPT_DOT_LDS_CULL, SR_OPT_DOT_LDS_CAP, SR_OPT_UPSAMPLE_QUAD,
-  SR_OPT_POOL_STREAM,
+  SR_OPT_MLP_SPLIT = 0, SR_OPT_WINO_SPLIT, SR_OPT_WINO_XCD, SR_OPT_WINO_NT, SR_OPT_WINO_KSPLIT, SR_OPT_CONV_WINO,
+  SR_OPT_CONV_TILE, SR_OPT_CONV_KSPLIT, SR_OPT_PW_NT, SR_OPT_PW_KS, SR_OPT_PT_CFG, SR_OPT_PT_KS, SR_OPT_DOT_LDS,
+  SR_OPT_DOT_LDS_G, SR_OPT_DOT_LDS_CULL, SR_OPT_DOT_LDS_CAP, SR_OPT_UPSAMPLE_QUAD, SR_OPT_POOL_STREAM,
   SR_OPT_COUNT
 };
 int sr_option_count(void);
@@ -907,7 +905,7 @@ int sr_mul_fwd(const float* a, const float* b, float* out, int64_t n, void* stre
  * by sr_volume_prepare WITH T_cur_src (pose features) for the same sources; `scratch`
  * (sr_mlp_volume_bwd_scratch_bytes, 256-byte aligned) holds the channels-last d_src image and weight transposes.
  * hidden = 128, C = 16, up to 15 views (MLP width <= 416); SR_ERR_UNSUPPORTED otherwise.  The six GEMM-shaped phases run on
- * the fp32 matrix cores (v_mfma_f32_32x32x2_f32); SR_MLP_BWD_VALU=1 selects the round-1 VALU kernel (<= 9 views).
+ * the fp32 matrix cores (v_mfma_f32_32x32x2_f32).
  * Feature-map and weight gradients are accumulated with hardware fp32 atomics (summation order not fixed). */
 size_t sr_mlp_volume_bwd_scratch_bytes(int B, int K, int C, int h, int w, int hidden);
 int sr_mlp_volume_bwd(const float* grad_cv, int64_t g_sb, int64_t g_sd, int64_t g_sp, const float* cur,

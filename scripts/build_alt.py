@@ -1,5 +1,5 @@
-"""Builds an ALTERNATIVE libsimplerecon_hip.so with extra hipcc flags (ablation / A-B builds), next to the product
-library:  python scripts/build_alt.py NAME -DSR_WINO_REGV=0 ...  ->  simplerecon_amd/alt/libsr_NAME.so
+"""Builds an ALTERNATIVE libsimplerecon_hip.so with extra hipcc flags (trace / A-B builds), next to the product
+library:  python scripts/build_alt.py NAME -DSR_WINO_TRACE ...  ->  simplerecon_amd/alt/libsr_NAME.so
 Select it at run time with SR_HIP_LIBRARY=simplerecon_amd/alt/libsr_NAME.so (simplerecon_amd/_lib.py)."""
 import concurrent.futures
 import os

@@ -1,4 +1,4 @@
-"""Single-shape conv micro-benchmark (HIP events), for ablations via SR_CONV_DEBUG."""
+"""Single-shape conv micro-benchmark (HIP events)."""
 import sys, os
 sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
 import torch
@@ -25,4 +25,4 @@ for (B, ci, H, W, co, k) in shapes:
             e1.record(); e1.synchronize()
             t = e0.elapsed_time(e1) * 1e-3 / n
         fl = 2.0 * B * H * W * co * ci * k * k
-        print(f"dbg={os.environ.get('SR_CONV_DEBUG','0'):>2s} {str((B,ci,H,W,co,k)):30s} res={int(with_res)} {t*1e6:9.1f} us {fl/t/1e12:7.1f} TF", flush=True)
+        print(f"{str((B,ci,H,W,co,k)):30s} res={int(with_res)} {t*1e6:9.1f} us {fl/t/1e12:7.1f} TF", flush=True)

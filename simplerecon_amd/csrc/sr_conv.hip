@@ -43,14 +43,6 @@ typedef float f32x16 __attribute__((ext_vector_type(16)));
 #endif
 __host__ __device__ constexpr int sr_ck(int ks, int stride = 1) { return (ks == 1 && stride == 1) ? SR_CK1 : 16; }
 
-// Phase-ablation switches (env SR_CONV_DEBUG) exist only in -DSR_CONV_ABLATION builds; in production they are compile-time 0,
-// which keeps dead branches out of the hot loops (they cost registers: the MLP sweep spilled because of them).
-#ifdef SR_CONV_ABLATION
-#define SR_CV_DBG(bit) (p.debug & (bit))
-#else
-#define SR_CV_DBG(bit) 0
-#endif
-
 struct SrConvParams {
   const float* in; int64_t in_sb; int in_sp;        // batch stride, pixel stride (elements)
   const float* wp;                                  // packed weights [taps][G][2][Co_pad][4]
@@ -62,7 +54,6 @@ struct SrConvParams {
   float slope;                                      // >= 0: LeakyReLU slope; SR_ACT_NONE; SR_ACT_SILU
   int pad_y, pad_x;                                 // zero (or replicate) padding above / left of the image
   int vec4;                                         // input rows 16-byte aligned
-  int debug;                                        // ablation bits (env SR_CONV_DEBUG), 0 in production
   int replicate;                                    // padding_mode="replicate": halo coordinates clamp to the border
   // split-K (1x1 convs with a long channel chain on few tiles): a work item covers 1/ksplit of the input slabs and
   // stores its raw partial sums (no bias / residual / activation) to part + ks * part_stride, dense channels-last
@@ -105,7 +96,7 @@ __device__ __forceinline__ void sr_conv_stage_setup(const SrConvParams& p, int i
       iy = min(max(iy, 0), p.H - 1);
       ix = min(max(ix, 0), p.W - 1);
     }
-    const bool ok = (e < G::ELEMS) && (iy >= 0) && (iy < p.H) && (ix >= 0) && (ix < p.W) && !SR_CV_DBG(4);
+    const bool ok = (e < G::ELEMS) && (iy >= 0) && (iy < p.H) && (ix >= 0) && (ix < p.W);
     offs[it] = ok ? (iy * p.W + ix) * p.in_sp + 4 * q : -1;
   }
 }
@@ -242,7 +233,7 @@ __global__ __launch_bounds__(256) void sr_conv_kernel(SrConvParams p) {
 #pragma unroll
         for (int r = 0; r < 16; ++r) acc[m][n][r] = 0.0f;
     float rpf[RES_PF ? MT : 1][RES_PF ? NT : 1][16];  // prefetched residual values (RES_PF only)
-    const float* __restrict__ resp = (p.res && !partial && !SR_CV_DBG(2)) ? p.res + (int64_t)t.b * p.res_sb : nullptr;
+    const float* __restrict__ resp = (p.res && !partial) ? p.res + (int64_t)t.b * p.res_sb : nullptr;
 
     for (int ch = c_beg; ch < c_end; ++ch) {
       const float* tile = tiles[buf];
@@ -317,7 +308,7 @@ __global__ __launch_bounds__(256) void sr_conv_kernel(SrConvParams p) {
       const float slope = sr_uniform(partial ? SR_ACT_NONE : p.slope);   // scalar: tested once per 16-value fragment
       const bool no_res = (resp == nullptr);
       // interior tiles (workgroup-uniform test) take a branch-free path
-      const bool full = (t.oy0 + TH <= p.Ho) && (t.ox0 + CM <= p.Wo) && (t.co0 + 32 * NT <= p.Cout) && !SR_CV_DBG(1);
+      const bool full = (t.oy0 + TH <= p.Ho) && (t.ox0 + CM <= p.Wo) && (t.co0 + 32 * NT <= p.Cout);
 #pragma unroll
       for (int m = 0; m < MT; ++m) {
         const int oyb = t.oy0 + (wave * MT + m) * RM;
@@ -369,7 +360,7 @@ __global__ __launch_bounds__(256) void sr_conv_kernel(SrConvParams p) {
 #pragma unroll
             for (int r = 0; r < 16; ++r) {
               const int row = (8 * (r >> 2)) / CM, colc = (8 * (r >> 2)) % CM + (r & 3);
-              if (ok[r] && (!SR_CV_DBG(1) || o16[r] == 1.2345e33f)) outp[ob + (unsigned)((row * p.Wo + colc) * osp)] = o16[r];
+              if (ok[r]) outp[ob + (unsigned)((row * p.Wo + colc) * osp)] = o16[r];
             }
           }
         }
@@ -656,11 +647,6 @@ static int sr_conv2d_dispatch(const float* in, int64_t in_batch_stride, int in_p
     p.ksplit = fit < 2 ? 1 : (fit < SR_CONV_KSPLIT_MAX ? (int)fit : SR_CONV_KSPLIT_MAX);   // upper bound: the launch plans
     p.part = (float*)workspace;
   }
-#ifdef SR_CONV_ABLATION   // (ablation builds only: the product library reads no environment on a launch path)
-  { static int dbg = -1; if (dbg < 0) { const char* e = getenv("SR_CONV_DEBUG"); dbg = e ? atoi(e) : 0; } p.debug = dbg; }
-#else
-  p.debug = 0;
-#endif
   p.vec4 = (((uintptr_t)in & 15) == 0) && (in_pix_stride % 4 == 0) && (in_batch_stride % 4 == 0);
   hipStream_t stream = (hipStream_t)stream_;
   const SrConvCfg cfg = sr_conv_cfg(p, B, stride, ksize);

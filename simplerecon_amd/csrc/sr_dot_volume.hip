@@ -434,12 +434,7 @@ extern "C" int sr_dot_volume_sweep(const float* cur, const float* invK_cur, cons
     case 4: hipLaunchKernelGGL(sr_dot_volume_kernel<4>, grid, block, lds, stream, p); break;
     case 8: hipLaunchKernelGGL(sr_dot_volume_kernel<8>, grid, block, lds, stream, p); break;
     case 12: hipLaunchKernelGGL(sr_dot_volume_kernel<12>, grid, block, lds, stream, p); break;
-    case 16: {
-      const int quad = sr_opt(SR_OPT_DOT_QUAD);  // 0 selects the generic lane-per-pixel kernel (ablation)
-      if (quad) hipLaunchKernelGGL(sr_dot_volume_kernel16q, grid, block, lds, stream, p);
-      else hipLaunchKernelGGL(sr_dot_volume_kernel<16>, grid, block, lds, stream, p);
-      break;
-    }
+    case 16: hipLaunchKernelGGL(sr_dot_volume_kernel16q, grid, block, lds, stream, p); break;
     case 24: hipLaunchKernelGGL(sr_dot_volume_kernel<24>, grid, block, lds, stream, p); break;
     case 32: hipLaunchKernelGGL(sr_dot_volume_kernel<32>, grid, block, lds, stream, p); break;
     default: return SR_ERR_UNSUPPORTED;

@@ -175,11 +175,7 @@ __device__ __forceinline__ void sr_stage_load(const SrLdsCtx& c, sr_f4 (&v)[NU],
       const int ry = (int)(((unsigned)ch * rcp_nchunk) >> 16), cx = ch - ry * nchunk;   // (scalar)
       const int gy = min(max(miny - 1 + ry, 0), c.h - 1);                               // (scalar)
       const int gx = min(max(lane_x0 + cx * 16, 0), c.w - 1);
-#ifdef SR_DOT_ABL_HOT   // (timing experiment: every staging load hits the same L1-resident texels -- what the load latency costs)
-      v[U] = __builtin_bit_cast(sr_f4, __builtin_amdgcn_raw_buffer_load_b128(rs_img, (gx & 1) * 64 + (c.lane & 3) * 16, (gy & 1) * 64, 0));
-#else
       v[U] = __builtin_bit_cast(sr_f4, __builtin_amdgcn_raw_buffer_load_b128(rs_img, gx * 64 + (c.lane & 3) * 16, gy * c.w * 64, 0));
-#endif
       sr_stage_load<U + 1, NU, U0>(c, v, rcp_nchunk, nchunk, nchunks, lane_x0, miny, rs_img);
     }
   }

@@ -191,14 +191,14 @@ __device__ __forceinline__ float4 sr_maxblur_generic(const float* __restrict__ i
   return acc;
 }
 
-// One thread = a block of 2 x BW output pixels x 4 channels (BW = 2 or 4).  Interior blocks stream their 7 x (2 BW + 3) input
-// window row by row (49 float4 loads for 4 outputs, 77 for 8): vertical max with the previous row, horizontal max,
-// horizontal blur for the BW output columns, then the row's contribution to the two output rows.  (BW = 4 is an ablation
-// switch: measured slower, see sr_maxblurpool_nhwc_fwd.)
-template <int BW>
+// One thread = a block of 2 x BW output pixels x 4 channels (BW = 2).  Interior blocks stream their 7 x (2 BW + 3) input
+// window row by row (49 float4 loads for 4 outputs): vertical max with the previous row, horizontal max, horizontal blur
+// for the BW output columns, then the row's contribution to the two output rows.  (BW = 4 issued 9.6 instead of 12.25
+// loads per output and was slower, 0.70 vs 0.45 ms per 64 images: half the threads, twice the registers.)
 __global__ __launch_bounds__(256) void sr_maxblurpool_kernel(const float* __restrict__ in, int64_t in_sb, int in_sp,
                                                              float* __restrict__ out, int64_t out_sb, int out_sp,
                                                              int H, int W, int Ho, int Wo, int C4, int xcd_order) {
+  constexpr int BW = 2;            // output columns per thread
   constexpr int WC = 2 * BW + 3;   // input columns of a block's window
   const int Hm = H - 1, Wm = W - 1;
   const int bx = (Wo + BW - 1) / BW, by = (Ho + 1) / 2;
@@ -675,7 +675,6 @@ struct SrT16Params {
   int H, W, Cin, Cout, replicate;
   int tiles_x, tiles_y, total;
   float out_slope;
-  int xcd_order;                      // 1: tiles of a round are dealt to the XCDs in contiguous eighths (SR_T16_XCD, default 1)
 };
 
 __global__ void sr_t16_pack_kernel(const float* __restrict__ w /*[Cout,Cin,3,3]*/, float* __restrict__ packed, int Cout,
@@ -701,7 +700,7 @@ __global__ __launch_bounds__(256, 3) void sr_t16_kernel(SrT16Params p) {
     // XCD-aware work order (r04; as in sr_wino_kernel): in a full round the grid's tiles are dealt to the XCDs in contiguous
     // eighths, so that the halo two neighbouring tiles share is fetched into one L2
     int tile = work;
-    if (p.xcd_order && (gridDim.x & 7) == 0) {
+    if ((gridDim.x & 7) == 0) {
       const int G = (int)gridDim.x, r0 = work / G * G;
       if (r0 + G <= p.total) { const int bb = work - r0; tile = r0 + (bb & 7) * (G >> 3) + (bb >> 3); }
     }
@@ -845,7 +844,6 @@ extern "C" int sr_conv3x3_c16_nhwc_fwd(const float* in, int64_t in_batch_stride,
   p.out_slope = leaky_slope;
   int blocks = 3 * sr_cus();
   if (blocks > p.total) blocks = p.total;
-  p.xcd_order = sr_opt(SR_OPT_T16_XCD);   // (ablation; results are identical)
   const bool norm = in_stats != nullptr, act = in_leaky_slope >= 0.f;
   if (norm && act) hipLaunchKernelGGL((sr_t16_kernel<true, true>), dim3(blocks), dim3(256), 0, (hipStream_t)stream_, p);
   else if (norm) hipLaunchKernelGGL((sr_t16_kernel<true, false>), dim3(blocks), dim3(256), 0, (hipStream_t)stream_, p);
@@ -928,19 +926,11 @@ extern "C" int sr_maxblurpool_nhwc_fwd(const float* in, int64_t in_batch_stride,
     hipLaunchKernelGGL(sr_maxblurpool_stream_kernel, dim3(p.stream_wgs + frame_wgs, B), dim3(256), 0, (hipStream_t)stream_, p);
     return sr_hip_rc(hipGetLastError());
   }
-  int bw = 2;   // output columns per thread.  4 (SR_POOL_BW=4, Wo % 4 == 0) issues 9.6 instead of 12.25 loads per output and is
-  if (sr_opt(SR_OPT_POOL_BW) == 4 && Wo % 4 == 0) bw = 4;   // SLOWER: 0.70 vs 0.45 ms per 64 images
-                                                                                            // (half the threads, twice the registers)
-  const int64_t total = (int64_t)((Ho + 1) / 2) * ((Wo + bw - 1) / bw) * (C / 4);
+  const int64_t total = (int64_t)((Ho + 1) / 2) * ((Wo + 1) / 2) * (C / 4);   // 2 x 2 output pixels per thread
   const int blocks = (int)((total + 255) / 256 < 8192 ? (total + 255) / 256 : 8192);
-  int xcd = ((int64_t)blocks * 256 >= total) && (((int64_t)blocks * B) % 8 == 0);   // no striding, whole eighths
-  if (sr_opt(SR_OPT_POOL_XCD) == 0) xcd = 0;          // (ablation; results are identical)
-  if (bw == 4)
-    hipLaunchKernelGGL((sr_maxblurpool_kernel<4>), dim3(blocks, B), dim3(256), 0, (hipStream_t)stream_, in, in_batch_stride,
-                       in_pix_stride, out, out_batch_stride, out_pix_stride, H, W, Ho, Wo, C / 4, xcd);
-  else
-    hipLaunchKernelGGL((sr_maxblurpool_kernel<2>), dim3(blocks, B), dim3(256), 0, (hipStream_t)stream_, in, in_batch_stride,
-                       in_pix_stride, out, out_batch_stride, out_pix_stride, H, W, Ho, Wo, C / 4, xcd);
+  const int xcd = ((int64_t)blocks * 256 >= total) && (((int64_t)blocks * B) % 8 == 0);   // no striding, whole eighths
+  hipLaunchKernelGGL(sr_maxblurpool_kernel, dim3(blocks, B), dim3(256), 0, (hipStream_t)stream_, in, in_batch_stride,
+                     in_pix_stride, out, out_batch_stride, out_pix_stride, H, W, Ho, Wo, C / 4, xcd);
   return sr_hip_rc(hipGetLastError());
 }
 

@@ -117,12 +117,10 @@ struct SrMlpParams {
   int B, K, h, w, D;
   int tiles;              // ceil(h*w / 64)
   int chunk, chunks;      // planes per work unit, ceil(D / chunk)
-  float inv_w, inv_h, slope;
-  int debug;              // ablation bits (env SR_MLP_DEBUG), 0 in production
-  int xcd_order;          // 1: each XCD (workgroup index mod 8) sweeps its own contiguous eighth of the work units
   int vec_store;          // channels-last volume (plane stride 1): a lane keeps the costs of its unit's planes and
                           // stores them as 16-byte pieces at the end of the unit (instead of one 4-byte store per plane
                           // into 64 different 256-byte rows: r02 PMC counted 6.7x the volume's bytes in WRITE_SIZE)
+  float inv_w, inv_h, slope;
 };
 
 __device__ __forceinline__ void sr_swap_halves(float fa, float fb, float& bP, float& bQ) {
@@ -162,16 +160,6 @@ __device__ __forceinline__ void sr_l1_step_init(f32x16 (&acc)[2][4], const f32x1
   acc[1][3] = SR_MFMA(wA.w, bQ, hc[1][3]);
 }
 
-// Ablation switches (env SR_MLP_DEBUG) exist only in -DSR_MLP_ABLATION builds; in production they are compile-time 0.
-#ifdef SR_MLP_ABLATION
-#define SR_MLP_DBG(bit) (p.debug & (bit))
-#else
-#define SR_MLP_DBG(bit) 0
-#endif
-
-#ifndef SR_MLP_NT_TAPS
-#define SR_MLP_NT_TAPS 0
-#endif
 #define SR_LDS_W3_FLOATS 256  // w3tab (128) + b3 + pad, in front of W1 in LDS
 
 template <bool W1_LDS, bool W2_LDS>
@@ -211,7 +199,7 @@ __global__ __launch_bounds__(256, 1) void sr_mlp_volume_kernel(SrMlpParams p) {
   long wave0 = (long)blockIdx.x * (blockDim.x >> 6) + (threadIdx.x >> 6);
   long nwaves = (long)gridDim.x * (blockDim.x >> 6);
   long unit_end = nunits;
-  if (p.xcd_order && (gridDim.x & 7) == 0) {
+  if ((gridDim.x & 7) == 0) {
     const long u8 = (nunits + 7) / 8;
     const int xcd = blockIdx.x & 7;
     nwaves = (long)(gridDim.x >> 3) * (blockDim.x >> 6);
@@ -297,20 +285,9 @@ __global__ __launch_bounds__(256, 1) void sr_mlp_volume_kernel(SrMlpParams p) {
       const float4* t_ne = reinterpret_cast<const float4*>(img + (size_t)smp.o_ne * C);
       const float4* t_sw = reinterpret_cast<const float4*>(img + (size_t)smp.o_sw * C);
       const float4* t_se = reinterpret_cast<const float4*>(img + (size_t)smp.o_se * C);
-      if (!SR_MLP_DBG(2)) {
 #pragma unroll
-        for (int i = 0; i < 4; ++i) {
-#if SR_MLP_NT_TAPS   // streaming policy for the taps: they should not push the W1 / W2 blocks of a streaming variant out of L2
-          typedef float nt_f4 __attribute__((ext_vector_type(4)));
-          auto ntl = [](const float4* q) {
-            const nt_f4 v = __builtin_nontemporal_load(reinterpret_cast<const nt_f4*>(q));
-            return make_float4(v.x, v.y, v.z, v.w);
-          };
-          taps[i] = ntl(&t_nw[i]); taps[4 + i] = ntl(&t_ne[i]); taps[8 + i] = ntl(&t_sw[i]); taps[12 + i] = ntl(&t_se[i]);
-#else
-          taps[i] = t_nw[i]; taps[4 + i] = t_ne[i]; taps[8 + i] = t_sw[i]; taps[12 + i] = t_se[i];
-#endif
-        }
+      for (int i = 0; i < 4; ++i) {
+        taps[i] = t_nw[i]; taps[4 + i] = t_ne[i]; taps[8 + i] = t_sw[i]; taps[12 + i] = t_se[i];
       }
     };
     // pieces of the per-view feature assembly (o = fn or f); the ray pieces need no taps
@@ -442,7 +419,7 @@ __global__ __launch_bounds__(256, 1) void sr_mlp_volume_kernel(SrMlpParams p) {
         const float4 wA = wn0;
         wn0 = wn1;
         wn1 = wn2;
-        if (!SR_MLP_DBG(1)) wn2 = w2[(size_t)min(t + 3, 64) * 64];
+        wn2 = w2[(size_t)min(t + 3, 64) * 64];
         const float aP = acc[0][t >> 4][t & 15], aQ = acc[1][t >> 4][t & 15];
         const float bP = sr_vmax_mfma(aP, p.slope * aP), bQ = sr_vmax_mfma(aQ, p.slope * aQ);
         acc2[0][0] = SR_MFMA(wA.x, bP, t == 0 ? zero16 : acc2[0][0]);
@@ -563,9 +540,6 @@ template <> struct SrSplitFmt<2> {   // two fp16 pieces: 22-24 significant bits 
 //   table  [0,512):   w3tab (128) | b3 (1) | pad | b2tab at 256 (128: C layout, [half][mt][r])
 //   W2     8 steps x [mt 4][piece 2][lane 64][4 words]                        = 16384 words
 //   W1var  per view: step A [mt 4][piece 2][lane 64][4] (2048) + metadata step [mt 4][piece 2][lane 32][4] (1024)
-#ifndef SR_SPL_ABL
-#define SR_SPL_ABL 0   // phase ablation (tuning builds only; wrong results): 1 no tap loads, 2 no layer-1 MFMAs, 4 no layer-2 MFMAs
-#endif
 #define SR_SPL_TAB 512
 #define SR_SPL_W2_WORDS 16384
 #define SR_SPL_VIEW_WORDS 3072
@@ -710,7 +684,7 @@ __global__ __launch_bounds__(256, 1) void sr_mlp_volume_split_kernel(SrMlpParams
   long wave0 = (long)blockIdx.x * (blockDim.x >> 6) + (threadIdx.x >> 6);
   long nwaves = (long)gridDim.x * (blockDim.x >> 6);
   long unit_end = nunits;
-  if (p.xcd_order && (gridDim.x & 7) == 0) {   // XCD-contiguous unit ranges, as in sr_mlp_volume_kernel
+  if ((gridDim.x & 7) == 0) {   // XCD-contiguous unit ranges, as in sr_mlp_volume_kernel
     const long u8 = (nunits + 7) / 8;
     const int xcd = blockIdx.x & 7;
     nwaves = (long)(gridDim.x >> 3) * (blockDim.x >> 6);
@@ -797,8 +771,7 @@ __global__ __launch_bounds__(256, 1) void sr_mlp_volume_split_kernel(SrMlpParams
       const float4* t_se = reinterpret_cast<const float4*>(img + (size_t)smp.o_se * C);
 #pragma unroll
       for (int i = 0; i < 4; ++i) {
-        if (SR_SPL_ABL & 1) { taps[i] = taps[4 + i] = taps[8 + i] = taps[12 + i] = make_float4(smp.w_nw, smp.w_ne, smp.w_sw, smp.w_se); }
-        else { taps[i] = t_nw[i]; taps[4 + i] = t_ne[i]; taps[8 + i] = t_sw[i]; taps[12 + i] = t_se[i]; }
+        taps[i] = t_nw[i]; taps[4 + i] = t_ne[i]; taps[8 + i] = t_sw[i]; taps[12 + i] = t_se[i];
       }
     };
     float rv0, rv1, rv2, rsd, rdot;
@@ -840,10 +813,10 @@ __global__ __launch_bounds__(256, 1) void sr_mlp_volume_split_kernel(SrMlpParams
         sr_swap_halves_u4(sr_u4v{ph[8], ph[9], ph[10], ph[11]}, zero4, mPh, mQh);                        \
         sr_swap_halves_u4(sr_u4v{pl[8], pl[9], pl[10], pl[11]}, zero4, mPl, mQl);                        \
         issue_view(kn);                                                                                  \
-        if (!(SR_SPL_ABL & 2) || (FIRST)) sr_spl_step<FMT, (FIRST) ? 1 : 0>(acc, hc, wk + lane, 64, bPh, bPl, bQh, bQl); \
+        sr_spl_step<FMT, (FIRST) ? 1 : 0>(acc, hc, wk + lane, 64, bPh, bPl, bQh, bQl);                   \
         SR_RAY_A(fn, g, kn) SR_RAY_B(fn) SR_RAY_C(fn)                                                    \
         SR_SB                                                                                            \
-        if (!(SR_SPL_ABL & 2)) sr_spl_step<FMT, 0>(acc, hc, wk + 512 + (lane & 31), 32, mPh, mPl, mQh, mQl); \
+        sr_spl_step<FMT, 0>(acc, hc, wk + 512 + (lane & 31), 32, mPh, mPl, mQh, mQl);                    \
         SR_INTERP2(fn, 0, 0) SR_INTERP2(fn, 0, 1) SR_INTERP2(fn, 1, 0) SR_INTERP2(fn, 1, 1)              \
         SR_INTERP2(fn, 2, 0) SR_INTERP2(fn, 2, 1) SR_INTERP2(fn, 3, 0) SR_INTERP2(fn, 3, 1)              \
         SR_DOT(fn)                                                                                       \
@@ -874,7 +847,7 @@ __global__ __launch_bounds__(256, 1) void sr_mlp_volume_split_kernel(SrMlpParams
           }
         const sr_u4v* w2 = W2s + (size_t)s * 512 + lane;
         if (s == 0) sr_spl_step<FMT, 2>(acc2, acc2, w2, 64, bh[0], bl[0], bh[1], bl[1]);
-        else if (!(SR_SPL_ABL & 4)) sr_spl_step<FMT, 0>(acc2, acc2, w2, 64, bh[0], bl[0], bh[1], bl[1]);
+        else sr_spl_step<FMT, 0>(acc2, acc2, w2, 64, bh[0], bl[0], bh[1], bl[1]);
       }
 
       // layer 3 (128 -> 1) on acc2 + b2; w3tab and b2tab in LDS (C layout)
@@ -996,11 +969,6 @@ static int sr_mlp_volume_sweep_reserved(const float* cur, const float* invK_cur,
   p.inv_w = (float)(1.0 / (double)w);
   p.inv_h = (float)(1.0 / (double)h);
   p.slope = leaky_slope;
-#ifdef SR_MLP_ABLATION   // (ablation builds only)
-  { static int dbg = -1; if (dbg < 0) { const char* e = getenv("SR_MLP_DEBUG"); dbg = e ? atoi(e) : 0; } p.debug = dbg; }
-#else
-  p.debug = 0;
-#endif
 
   // planes per work unit: as many as possible (the hoisted invariant part is paid once per unit) while the
   // units still spread evenly over the 4*CUs persistent waves
@@ -1019,8 +987,6 @@ static int sr_mlp_volume_sweep_reserved(const float* cur, const float* invK_cur,
   p.chunks = (D + best - 1) / best;
   p.vec_store = (cv_sd == 1) && (p.chunk % 4 == 0) && (cv_sp % 4 == 0) && (cv_sb % 4 == 0) &&
                 (((uintptr_t)out_cv & 15) == 0);
-  if (sr_opt(SR_OPT_MLP_VEC_STORE) == 0) p.vec_store = 0;   // ablation
-  p.xcd_order = sr_opt(SR_OPT_MLP_XCD);
   const long nunits = (long)B * p.tiles * p.chunks;
   const int blocks = (int)((nunits + 3) / 4 < cus ? (nunits + 3) / 4 : cus);
   const size_t w3_bytes = SR_LDS_W3_FLOATS * sizeof(float);

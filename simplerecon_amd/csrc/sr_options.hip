@@ -18,13 +18,11 @@ namespace {
 
 struct OptDef { const char* name; int dflt; int kind; };   // kind 0: integer, 1: split-precision mode string
 const OptDef kDefs[SR_OPT_COUNT] = {
-    {"SR_MLP_SPLIT", 0, 1},       {"SR_WINO_SPLIT", 0, 1},     {"SR_WINO_XCD", 1, 0},        {"SR_WINO_STAGGER", 0, 0},
-    {"SR_WINO_WG_PER_CU", 2, 0},  {"SR_WINO_NT", 0, 0},        {"SR_WINO_KSPLIT", 0, 0},     {"SR_CONV_WINO", 1, 0},
-    {"SR_CONV_TILE", 0, 0},       {"SR_CONV_KSPLIT", 1, 0},    {"SR_MLP_VEC_STORE", 1, 0},   {"SR_MLP_XCD", 1, 0},
-    {"SR_MLP_BWD_VALU", 0, 0},    {"SR_T16_XCD", 1, 0},        {"SR_POOL_BW", 0, 0},         {"SR_POOL_XCD", 1, 0},
+    {"SR_MLP_SPLIT", 0, 1},       {"SR_WINO_SPLIT", 0, 1},     {"SR_WINO_XCD", 1, 0},        {"SR_WINO_NT", 0, 0},
+    {"SR_WINO_KSPLIT", 0, 0},     {"SR_CONV_WINO", 1, 0},      {"SR_CONV_TILE", 0, 0},       {"SR_CONV_KSPLIT", 1, 0},
     {"SR_PW_NT", 0, 0},           {"SR_PW_KS", 0, 0},          {"SR_PT_CFG", -1, 0},         {"SR_PT_KS", 0, 0},
-    {"SR_DOT_LDS", 1, 0},         {"SR_DOT_QUAD", 1, 0},       {"SR_DOT_LDS_G", 0, 0},       {"SR_DOT_LDS_CULL", 1, 0},
-    {"SR_DOT_LDS_CAP", 634, 0},   {"SR_UPSAMPLE_QUAD", 1, 0},  {"SR_POOL_STREAM", 1, 0},
+    {"SR_DOT_LDS", 1, 0},         {"SR_DOT_LDS_G", 0, 0},      {"SR_DOT_LDS_CULL", 1, 0},    {"SR_DOT_LDS_CAP", 634, 0},
+    {"SR_UPSAMPLE_QUAD", 1, 0},   {"SR_POOL_STREAM", 1, 0},
 };
 std::atomic<int> g_val[SR_OPT_COUNT];
 std::once_flag g_once;

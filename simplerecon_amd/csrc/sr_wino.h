@@ -20,14 +20,6 @@ typedef float f32x16 __attribute__((ext_vector_type(16)));
 #define SR_WINO_PD 3   // prefetch distance in steps (< NB)
 #endif
 
-#ifndef SR_WINO_PIPE
-#define SR_WINO_PIPE 1   // 1: next slab stored mid-slab, barrier after step 5, its first transform half under steps 6-7
-#endif
-
-#ifndef SR_WINO_PRIME
-#define SR_WINO_PRIME 0   // 1: the next region's first weight fragments + first transform are issued in the epilogue's second half
-#endif
-
 #define WN_TR 4
 #define WN_TC 8
 #define WN_PH (2 * WN_TR + 2)  // 10 patch rows
@@ -43,14 +35,6 @@ typedef float f32x16 __attribute__((ext_vector_type(16)));
 #define WN_STAGE_ELEMS (WN_PH * WN_PW * 4)  // float4 elements per slab (720)
 #define WN_STAGE_PER_THREAD 3
 
-// Phase-ablation switches (env SR_WINO_DEBUG) exist only in -DSR_WINO_ABLATION builds; in production they are compile-time 0,
-// which keeps dead branches out of the hot loops (they cost registers: the MLP sweep spilled because of them).
-#ifdef SR_WINO_ABLATION
-#define SR_WN_DBG(bit) (p.debug & (bit))
-#else
-#define SR_WN_DBG(bit) 0
-#endif
-
 struct SrWinoParams {
   const float* in; int64_t in_sb; int in_sp;
   const float* wu;                                  // packed U: [16][G][2][Co_pad][4]
@@ -61,12 +45,10 @@ struct SrWinoParams {
   int regions_x, regions_y, co_blocks, total;
   float slope;
   int vec4;
-  int debug;  // ablation bits (env SR_WINO_DEBUG), 0 in production
   // split-K: a work item covers 1/ksplit of the input slabs and stores its raw partial output (no bias / residual /
   // activation) to part + ks * part_stride (dense channels-last [B, H*W, Cout]); sr_wino_reduce_kernel finishes.
   int ksplit; float* part; int64_t part_stride;
   int xcd_order;   // 1: items of a round are dealt to the XCDs in contiguous eighths (SR_WINO_XCD, default 1)
-  int stagger;     // the second half of the persistent grid (the second workgroup of every CU) starts this many s_sleep(127) late
 #ifdef SR_WINO_TRACE
   unsigned long long* trace;  // [blocks][SR_TR_REGIONS][SR_TR_EVENTS] shader-clock stamps (debug builds only)
 #endif
@@ -86,10 +68,6 @@ struct SrWinoParams {
 
 // float4 add / sub as two packed fp32 pairs (v_pk_add_f32): the transforms are pure add / sub work
 typedef float wn_f2 __attribute__((ext_vector_type(2)));
-#ifdef SR_WINO_NOPK   // ablation: plain fp32 adds instead of v_pk_add_f32 (packed fp32 VALU beside MFMAs)
-__device__ __forceinline__ float4 f4sub(float4 a, float4 b) { return make_float4(a.x - b.x, a.y - b.y, a.z - b.z, a.w - b.w); }
-__device__ __forceinline__ float4 f4add(float4 a, float4 b) { return make_float4(a.x + b.x, a.y + b.y, a.z + b.z, a.w + b.w); }
-#else
 __device__ __forceinline__ float4 f4sub(float4 a, float4 b) {
   const wn_f2 lo = wn_f2{a.x, a.y} - wn_f2{b.x, b.y}, hi = wn_f2{a.z, a.w} - wn_f2{b.z, b.w};
   return make_float4(lo.x, lo.y, hi.x, hi.y);
@@ -98,7 +76,6 @@ __device__ __forceinline__ float4 f4add(float4 a, float4 b) {
   const wn_f2 lo = wn_f2{a.x, a.y} + wn_f2{b.x, b.y}, hi = wn_f2{a.z, a.w} + wn_f2{b.z, b.w};
   return make_float4(lo.x, lo.y, hi.x, hi.y);
 }
-#endif
 
 // ---- buffer addressing (r04) ----------------------------------------------------------------------------------------
 // Every VALU instruction the kernel issues outside its MFMA stream costs ~13 clocks while the co-resident workgroup

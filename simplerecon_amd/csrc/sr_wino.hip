@@ -14,7 +14,7 @@
 //   T  wave w applies B^T d B for frequency row ur = w -- exactly the rows it multiplies.  Lane (i, kk) transforms tile
 //      i for the channel quads 2g + kk, g = 0, 1: precisely the A operands of its own MFMAs, so V lives in REGISTERS
 //      (r03; it used to make a ds_write / ds_read round trip through a 40 KB V array).  The transform of group g = 1 is
-//      issued under the MFMAs of group 0, and (SR_WINO_PIPE) the transform of the NEXT slab's group 0 under the MFMAs of
+//      issued under the MFMAs of group 0, and the transform of the NEXT slab's group 0 under the MFMAs of
 //      group 1: the next slab is stored to LDS at step 3, the slab barrier sits after step 5,
 //   M  wave w multiplies the 4 "frequencies" xi = 4w..4w+3:  M_xi[tile, co] += V_xi[tile, ci] . U_xi[ci, co]
 //      (U streams from L2 in B-fragment order, prefetched 3 steps ahead through 4 rotating register sets).
@@ -212,13 +212,13 @@ __global__ __launch_bounds__(256, NT == 1 ? SR_WINO_NT1_WAVES : SR_WINO_WAVES) v
       } else {
 #pragma unroll
         for (int it = 0; it < WN_STAGE_PER_THREAD; ++it)
-          stg[it] = SR_WN_DBG(4) ? make_float4(0.f, 0.f, 0.f, 0.f) : wn_io_load<IO>(rs_in, (unsigned)offs[it], so);
+          stg[it] = wn_io_load<IO>(rs_in, (unsigned)offs[it], so);
       }
     } else {
 #pragma unroll
       for (int it = 0; it < WN_STAGE_PER_THREAD; ++it) {
         const int c = c0 + 4 * ((tid + it * 256) & 3);
-        const bool ok = (offs[it] >= 0) & (c < p.Cin) & !SR_WN_DBG(4);
+        const bool ok = (offs[it] >= 0) & (c < p.Cin);
         const float* src = in_b + (ok ? offs[it] + c0 : 0);
         float4 v = make_float4(0.f, 0.f, 0.f, 0.f);
         if (ok) {
@@ -239,9 +239,6 @@ __global__ __launch_bounds__(256, NT == 1 ? SR_WINO_NT1_WAVES : SR_WINO_WAVES) v
   auto stage_store = [&](const float4 (&stg)[WN_STAGE_PER_THREAD], float* raw) {
     *reinterpret_cast<float4*>(&raw[st_lds0]) = stg[0];
     *reinterpret_cast<float4*>(&raw[st_lds0 + 64 * WN_ROW]) = stg[1];
-#ifdef SR_WINO_DBG_NOPAD
-    if (tid + 512 < WN_STAGE_ELEMS)
-#endif
     *reinterpret_cast<float4*>(&raw[st_lds2]) = stg[2];
   };
   (void)rv_base;
@@ -251,7 +248,7 @@ __global__ __launch_bounds__(256, NT == 1 ? SR_WINO_NT1_WAVES : SR_WINO_WAVES) v
   auto load_b = [&](int ch, int s, float4 (&dst)[NT]) {   // step s = (g, uc): all four frequencies of group 0, then group 1
     const int xi = 4 * wave + (s & 3), g = s >> 2;
     const char* wrec = reinterpret_cast<const char*>(reinterpret_cast<const float4*>(p.wu) +
-                                                     (SR_WN_DBG(32) ? (int64_t)0 : (int64_t)(xi * p.G + 2 * ch + g) * rec));
+                                                     (int64_t)(xi * p.G + 2 * ch + g) * rec);
 #pragma unroll
     for (int n = 0; n < NT; ++n) dst[n] = *reinterpret_cast<const float4*>(wrec + (wu_lane + 512u * n));
   };
@@ -277,28 +274,18 @@ __global__ __launch_bounds__(256, NT == 1 ? SR_WINO_NT1_WAVES : SR_WINO_WAVES) v
   };
 
   // Software pipeline: slab c of a region sits in raw buffer (c odd ? A : B); slab c+1 is fetched into registers at
-  // the top of slab c.  SR_WINO_PIPE: it is stored to the other buffer after step 3 (the last read of this wave's own
-  // transform of slab c is in step 3, the other buffer's last readers finished a slab ago), the workgroup barrier sits
-  // after step 5, and steps 6 / 7 carry the transform of slab c+1's first channel group -- so a slab boundary costs no
-  // serial LDS latency chain.  Otherwise: stored at the end of slab c, barrier, transform at the top of slab c+1.
-  // With an even slab count the NEXT region's slab 0 follows the same way during the last slab -- it lands in B,
-  // which the epilogue leaves alone, and is issued in front of the epilogue's stores (VMEM returns in order).  r04: the
-  // rest of the next region's prologue -- its first weight fragments and the transform of its first channel group --
-  // is then issued in the SECOND half of the epilogue (behind the O exchange, where the accumulators are dead), under
-  // the output stores, instead of in front of the next region's first MFMA.
+  // the top of slab c and stored to the other buffer after step 3 (the last read of this wave's own transform of slab c
+  // is in step 3, the other buffer's last readers finished a slab ago); the workgroup barrier sits after step 5, and
+  // steps 6 / 7 carry the transform of slab c+1's first channel group -- so a slab boundary costs no serial LDS latency
+  // chain.  With an even slab count the NEXT region's slab 0 follows the same way during the last slab -- it lands in
+  // B, which the epilogue leaves alone, and is issued in front of the epilogue's stores (VMEM returns in order).
   float4 stg[WN_STAGE_PER_THREAD];
   const bool chain = !(chunks & 1);
   bool staged = false;      // the next region's slab 0 sits in raw B
-  bool primed_w = false, primed_t = false;   // ... and its first weight fragments / first A operands are already in registers
   float4 b_f[NB][NT];
   float4 av[2][4];   // A operands of the current slab: [g][uc]
   float4 wq[4];
   Region reg = decode(blockIdx.x < (unsigned)p.total ? (int)blockIdx.x : 0), nxt = reg;
-  // SR_WINO_STAGGER (experiment, default 0): two persistent workgroups share a CU and run items of equal length; if they start
-  // together they stay in phase -- both in their MFMA streams, then both in their epilogues.  The switch delays the second half
-  // of the grid once, at launch (host side: what it does and does not buy).
-  if (p.stagger > 0 && blockIdx.x >= (gridDim.x >> 1))
-    for (int s = 0; s < p.stagger; ++s) __builtin_amdgcn_s_sleep(127);
   for (int work = blockIdx.x; work < p.total; work += gridDim.x) {
     const int b = reg.b, oy0 = reg.oy0, ox0 = reg.ox0, co0 = reg.co0, sl0 = reg.ks * chunks;
     wu_lane = (unsigned)(kk * p.Co_pad + co0 + i) * 16u;
@@ -320,22 +307,16 @@ __global__ __launch_bounds__(256, NT == 1 ? SR_WINO_NT1_WAVES : SR_WINO_WAVES) v
     // cost 128 VALU instructions per region, each ~13 clocks while the co-resident workgroup keeps the matrix pipe busy)
     f32x16 acc[4][NT];
 
-    if (!primed_w) {
 #pragma unroll
-      for (int s = 0; s < PD; ++s) load_b(sl0, s, b_f[s]);
-    }
+    for (int s = 0; s < PD; ++s) load_b(sl0, s, b_f[s]);
     SR_TR(1);
 
-#if SR_WINO_PIPE
     float4 pa[2], pb[2];   // patch rows on their way from LDS to the next slab's transform
-    if (!primed_t) {  // first slab of the region: its group 0 has no MFMAs to hide under
-      SR_WN_PIN("+v"(rv_a), "+v"(rv_b));
+    // first slab of the region: its group 0 has no MFMAs to hide under
+    SR_WN_PIN("+v"(rv_a), "+v"(rv_b));
 #pragma unroll
-      for (int c = 0; c < 4; ++c) wq[c] = rv_col(rawB, 0, c);
-      rv_row(wq, av[0]);
-    }
-#endif
-    primed_w = primed_t = false;
+    for (int c = 0; c < 4; ++c) wq[c] = rv_col(rawB, 0, c);
+    rv_row(wq, av[0]);
     auto slab = [&](auto first_tag, const int ch) {
       constexpr bool FIRST = decltype(first_tag)::value;   // first slab of the region: accumulators start from 0
       const bool more = ch + 1 < chunks;
@@ -351,17 +332,9 @@ __global__ __launch_bounds__(256, NT == 1 ? SR_WINO_NT1_WAVES : SR_WINO_WAVES) v
       const float* raw = (ch & 1) ? rawA : rawB;
       float* raw_next = (ch & 1) ? rawB : rawA;
       SR_WN_PIN("+v"(rv_a), "+v"(rv_b), "+v"(st_lds0), "+v"(st_lds2), "+v"(wu_lane));
-#if !SR_WINO_PIPE
-      if (!SR_WN_DBG(2)) {
-#pragma unroll
-        for (int c = 0; c < 4; ++c) wq[c] = rv_col(raw, 0, c);
-        rv_row(wq, av[0]);
-      }
-#endif
       if (ch < 5) SR_TR(2 + 2 * ch);
 
       // ---- M: this wave's 4 frequencies x 2 channel groups (same products in the same order as ever: bit-identical) ----
-      if (!SR_WN_DBG(8))
 #pragma unroll
       for (int s = 0; s < STEPS; ++s) {
         const int cbuf = s % NB, g = s >> 2, uc = s & 3;
@@ -387,14 +360,12 @@ __global__ __launch_bounds__(256, NT == 1 ? SR_WINO_NT1_WAVES : SR_WINO_WAVES) v
         __builtin_amdgcn_sched_barrier(0);
         // steps 0-3: one patch column of this slab's channel group 1 each (LDS latency << a step's 8 MFMAs)
         if (s < 4) wq[s] = rv_col(raw, 1, s);
-#if SR_WINO_PIPE
         // steps 6, 7: the next slab's channel group 0 (its patch was stored at step 3, barrier after step 5); the LDS
         // reads are issued one slot before their use.  Unconditional (no branch in the MFMA stream): after the last slab
         // of a region the values are simply not used.
         if (s == 6) { wq[0] = rv_fma(pa[0], pb[0]); wq[1] = rv_fma(pa[1], pb[1]);
                       rv_ld(raw_next, 0, 2, pa[0], pb[0]); rv_ld(raw_next, 0, 3, pa[1], pb[1]); }
         if (s == 7) { wq[2] = rv_fma(pa[0], pb[0]); wq[3] = rv_fma(pa[1], pb[1]); }
-#endif
         __builtin_amdgcn_sched_barrier(0);
 #pragma unroll
         for (int n = 0; n < NT; ++n)
@@ -405,26 +376,18 @@ __global__ __launch_bounds__(256, NT == 1 ? SR_WINO_NT1_WAVES : SR_WINO_WAVES) v
         __builtin_amdgcn_sched_barrier(0);
         if (s == 3) {
           rv_row(wq, av[1]);
-#if SR_WINO_PIPE
           stage_store(stg, raw_next);   // unconditional: after the last slab of the last region it stores stale registers
-#endif                                  // into a buffer nobody reads before it is restaged
+                                        // into a buffer nobody reads before it is restaged
           __builtin_amdgcn_sched_barrier(0);
         }
-#if SR_WINO_PIPE
         if (s == 5) {   // every wave has stored its share of the next slab and finished reading this one
           __syncthreads();
           rv_ld(raw_next, 0, 0, pa[0], pb[0]); rv_ld(raw_next, 0, 1, pa[1], pb[1]);
           __builtin_amdgcn_sched_barrier(0);
         }
-#endif
       }
       if (ch < 5) SR_TR(3 + 2 * ch);   // this wave's MFMAs issued
-#if SR_WINO_PIPE
-      if (more) rv_row(wq, av[0]);     // (after the last slab of a region: the next region's, done under the epilogue)
-#else
-      if (more || has_next) stage_store(stg, raw_next);
-      __syncthreads();
-#endif
+      if (more) rv_row(wq, av[0]);     // (after the last slab of a region: the next region's is done at its top)
     };
     slab(std::true_type{}, 0);
     for (int ch = 1; ch < chunks; ++ch) slab(std::false_type{}, ch);
@@ -444,215 +407,184 @@ __global__ __launch_bounds__(256, NT == 1 ? SR_WINO_NT1_WAVES : SR_WINO_WAVES) v
     // Y = A^T M A is separable: wave w holds the whole frequency ROW ur = w (its 4 accumulators are the columns
     // uc = 0..3), so the column half (M A) is done in registers and only 2 of 4 values per (tile, channel) go
     // through LDS: O[ur][b][tile][co] (64 KB for both N-tiles -> one pass, two barriers).
-    // The next region's prologue pieces that ride in the epilogue's second half (PIPE builds with a staged next region):
-    auto prime_next = [&]() {
-#if SR_WINO_PIPE && SR_WINO_PRIME
-      if (has_next) {
-        SR_WN_PIN("+v"(rv_a), "+v"(rv_b));
-        if (SR_WINO_PRIME & 1) {
-          wu_lane = (unsigned)(kk * p.Co_pad + nxt.co0 + i) * 16u;
-          const int nsl0 = nxt.ks * chunks;
+    constexpr int CO = 32 * NT;           // channels per workgroup
+    if (VOUT) {
+      // Vector epilogue (Cout % 4 == 0, 16-byte aligned output / residual rows): a thread owns (tile, 4 consecutive
+      // channels) units -- float4 residual loads, ds_read_b128 of the exchanged slab, float4 stores.  All of them
+      // through buffer descriptors: ONE lane offset per tensor (the unit's first pixel, channel quad), the other
+      // seven (unit, pixel) positions are scalar deltas; border regions / channel tails switch lanes off by offset.
+      constexpr int CG = CO / 4;            // channel groups per workgroup
+      constexpr int UNITS = 32 * CG / 256;  // = NT
+      constexpr int TILE_ROWS_PER_UNIT = (256 / CG) / 8;   // tile rows between a thread's consecutive units
+      const int cg = tid % CG;
+      const int tile0 = tid / CG;
+      const int tr0 = tile0 >> 3, tc0 = tile0 & 7;
+      const __amdgpu_buffer_rsrc_t rs_out = wn_rsrc(outp, ((int64_t)(p.H * p.W - 1) * out_sp + p.Cout) * ES);
+      const __amdgpu_buffer_rsrc_t rs_res =
+          wn_rsrc(resp ? (const void*)resp : (const void*)p.wu,
+                  resp ? ((int64_t)(p.H * p.W - 1) * p.res_sp + p.Cout) * ES : (int64_t)0);
+      const __amdgpu_buffer_rsrc_t rs_bias = wn_rsrc(bias_p ? (const void*)bias_p : (const void*)p.wu,
+                                                     bias_p ? (int64_t)p.Cout * 4 : (int64_t)0);
+      const bool okc = co0 + 4 * cg < p.Cout;
+      const bool full = (oy0 + 2 * WN_TR <= p.H) & (ox0 + 2 * WN_TC <= p.W) & (co0 + CO <= p.Cout);   // uniform
+      const unsigned pix0 = (unsigned)((2 * tr0) * p.W + 2 * tc0);
+      const unsigned v_out = (pix0 * out_sp + 4u * cg) * ES, v_res = (pix0 * (unsigned)p.res_sp + 4u * cg) * ES;
+      const unsigned s_out0 = ((unsigned)(oy0 * p.W + ox0) * out_sp + (unsigned)co0) * ES;
+      const unsigned s_res0 = ((unsigned)(oy0 * p.W + ox0) * (unsigned)p.res_sp + (unsigned)co0) * ES;
+      auto d_pix = [&](int it, int q) {   // scalar: pixel delta of (unit, pixel) from the unit-0 / pixel-0 position
+        return (unsigned)((2 * TILE_ROWS_PER_UNIT * it + (q >> 1)) * p.W + (q & 1));
+      };
+      // FULL = the region lies inside the image and the channel block inside Cout (every region of the 240x320 and
+      // 120x160 levels): one lane offset per tensor serves all eight (unit, pixel) positions.  Otherwise a per-position
+      // offset, WN_OOB outside the image / past Cout.
+      // LDS offsets of the O exchange as ONE register each + immediates (laundered per region: hoisted out of the work
+      // loop, the compiler kept 16 precomputed addresses in scratch and reloaded them in front of every ds_write)
+      int o_wr = (wave * 2 * 32 + 4 * kk) * CO + i, o_rd = tile0 * CO + 4 * cg;
+      asm volatile("" : "+v"(o_wr), "+v"(o_rd));
+      // a - b as fma(-1, b, a) with a -1 the compiler cannot see: v_pk_fma_f32 (the same single rounding as the
+      // subtraction).  Written as a - b, the compiler scalarises the 32 packed subtractions of the column transform
+      // into 64 v_sub_f32.
+      float neg1s = -1.0f;
+      asm volatile("" : "+s"(neg1s));
+      const wn_f2 neg1 = {neg1s, neg1s};
+      unsigned rsp4 = (unsigned)p.res_sp * ES, osp4 = out_sp * ES;   // (pinned: the eight scalar deltas are recomputed per
+      SR_WN_PIN("+s"(rsp4), "+s"(osp4));                             //  region on the SALU, not parked in VGPR lanes)
+      const bool fast_leaky = slope >= 0.0f && slope <= 1.0f;        // LeakyReLU as max(v, slope v): v_pk_mul + 2 v_max per pair
+      const wn_f2 slope2 = {slope, slope};
+      auto epilogue = [&](auto full_tag, auto res_tag) {
+        constexpr bool FULL = decltype(full_tag)::value, RES = decltype(res_tag)::value;
+        unsigned okm = 0;   // bit 4 it + q: position inside the image and channel quad below Cout
+        if (!FULL) {
 #pragma unroll
-          for (int s = 0; s < PD; ++s) load_b(nsl0, s, b_f[s]);
-          primed_w = true;
-        }
-        if (SR_WINO_PRIME & 2) {
-#pragma unroll
-          for (int c = 0; c < 4; ++c) wq[c] = rv_col(rawB, 0, c);
-          rv_row(wq, av[0]);
-          primed_t = true;
-        }
-      }
-#endif
-    };
-    if (!SR_WN_DBG(16)) {
-      constexpr int CO = 32 * NT;           // channels per workgroup
-      if (VOUT) {
-        // Vector epilogue (Cout % 4 == 0, 16-byte aligned output / residual rows): a thread owns (tile, 4 consecutive
-        // channels) units -- float4 residual loads, ds_read_b128 of the exchanged slab, float4 stores.  All of them
-        // through buffer descriptors: ONE lane offset per tensor (the unit's first pixel, channel quad), the other
-        // seven (unit, pixel) positions are scalar deltas; border regions / channel tails switch lanes off by offset.
-        constexpr int CG = CO / 4;            // channel groups per workgroup
-        constexpr int UNITS = 32 * CG / 256;  // = NT
-        constexpr int TILE_ROWS_PER_UNIT = (256 / CG) / 8;   // tile rows between a thread's consecutive units
-        const int cg = tid % CG;
-        const int tile0 = tid / CG;
-        const int tr0 = tile0 >> 3, tc0 = tile0 & 7;
-        const __amdgpu_buffer_rsrc_t rs_out = wn_rsrc(outp, ((int64_t)(p.H * p.W - 1) * out_sp + p.Cout) * ES);
-        const __amdgpu_buffer_rsrc_t rs_res =
-            wn_rsrc(resp ? (const void*)resp : (const void*)p.wu,
-                    resp ? ((int64_t)(p.H * p.W - 1) * p.res_sp + p.Cout) * ES : (int64_t)0);
-        const __amdgpu_buffer_rsrc_t rs_bias = wn_rsrc(bias_p ? (const void*)bias_p : (const void*)p.wu,
-                                                       bias_p ? (int64_t)p.Cout * 4 : (int64_t)0);
-        const bool okc = co0 + 4 * cg < p.Cout;
-#ifdef SR_WINO_FORCE_BORDER   // (test builds: every region through the per-position epilogue)
-        const bool full = false;
-#else
-        const bool full = (oy0 + 2 * WN_TR <= p.H) & (ox0 + 2 * WN_TC <= p.W) & (co0 + CO <= p.Cout);   // uniform
-#endif
-        const unsigned pix0 = (unsigned)((2 * tr0) * p.W + 2 * tc0);
-        const unsigned v_out = (pix0 * out_sp + 4u * cg) * ES, v_res = (pix0 * (unsigned)p.res_sp + 4u * cg) * ES;
-        const unsigned s_out0 = ((unsigned)(oy0 * p.W + ox0) * out_sp + (unsigned)co0) * ES;
-        const unsigned s_res0 = ((unsigned)(oy0 * p.W + ox0) * (unsigned)p.res_sp + (unsigned)co0) * ES;
-        auto d_pix = [&](int it, int q) {   // scalar: pixel delta of (unit, pixel) from the unit-0 / pixel-0 position
-          return (unsigned)((2 * TILE_ROWS_PER_UNIT * it + (q >> 1)) * p.W + (q & 1));
-        };
-        // FULL = the region lies inside the image and the channel block inside Cout (every region of the 240x320 and
-        // 120x160 levels): one lane offset per tensor serves all eight (unit, pixel) positions.  Otherwise a per-position
-        // offset, WN_OOB outside the image / past Cout.
-        // LDS offsets of the O exchange as ONE register each + immediates (laundered per region: hoisted out of the work
-        // loop, the compiler kept 16 precomputed addresses in scratch and reloaded them in front of every ds_write)
-        int o_wr = (wave * 2 * 32 + 4 * kk) * CO + i, o_rd = tile0 * CO + 4 * cg;
-        asm volatile("" : "+v"(o_wr), "+v"(o_rd));
-        // a - b as fma(-1, b, a) with a -1 the compiler cannot see: v_pk_fma_f32 (the same single rounding as the
-        // subtraction).  Written as a - b, the compiler scalarises the 32 packed subtractions of the column transform
-        // into 64 v_sub_f32.
-        float neg1s = -1.0f;
-        asm volatile("" : "+s"(neg1s));
-        const wn_f2 neg1 = {neg1s, neg1s};
-        unsigned rsp4 = (unsigned)p.res_sp * ES, osp4 = out_sp * ES;   // (pinned: the eight scalar deltas are recomputed per
-        SR_WN_PIN("+s"(rsp4), "+s"(osp4));                             //  region on the SALU, not parked in VGPR lanes)
-        const bool fast_leaky = slope >= 0.0f && slope <= 1.0f;        // LeakyReLU as max(v, slope v): v_pk_mul + 2 v_max per pair
-        const wn_f2 slope2 = {slope, slope};
-        auto epilogue = [&](auto full_tag, auto res_tag) {
-          constexpr bool FULL = decltype(full_tag)::value, RES = decltype(res_tag)::value;
-          unsigned okm = 0;   // bit 4 it + q: position inside the image and channel quad below Cout
-          if (!FULL) {
-#pragma unroll
-            for (int it = 0; it < UNITS; ++it)
-#pragma unroll
-              for (int q = 0; q < 4; ++q) {
-                const int oy = oy0 + 2 * (tr0 + TILE_ROWS_PER_UNIT * it) + (q >> 1), ox = ox0 + 2 * tc0 + (q & 1);
-                okm |= (unsigned)(okc & (oy < p.H) & (ox < p.W)) << (4 * it + q);
-              }
-          }
-          auto lane_off = [&](unsigned v, int it, int q) { return (FULL || ((okm >> (4 * it + q)) & 1u)) ? v : WN_OOB; };
-          float4 rv[UNITS][4];
-          if (RES) {
-#pragma unroll
-            for (int it = 0; it < UNITS; ++it)
-#pragma unroll
-              for (int q = 0; q < 4; ++q)
-                rv[it][q] = wn_io_load<IO>(rs_res, lane_off(v_res, it, q), s_res0 + d_pix(it, q) * rsp4);
-          }
-          const float4 bv = wn_buf_load(rs_bias, (FULL || okc) ? 16u * cg : WN_OOB, (unsigned)co0 * 4u);
-          SR_TR(10);
-#pragma unroll
-          for (int n = 0; n < NT; ++n) {
-            // whole-vector arithmetic: packed fp32 adds, half the VALU instructions of the element-wise form (every VALU
-            // instruction here costs matrix-pipe time of the co-resident workgroup)
-#pragma unroll
-            for (int r = 0; r < 16; r += 2) {   // register PAIRS spelled out: v_pk_add_f32 (the f32x16 form compiled to scalar adds)
-              const wn_f2 m0 = {acc[0][n][r], acc[0][n][r + 1]}, m1 = {acc[1][n][r], acc[1][n][r + 1]};
-              const wn_f2 m2 = {acc[2][n][r], acc[2][n][r + 1]}, m3 = {acc[3][n][r], acc[3][n][r + 1]};
-              const wn_f2 c0 = (m0 + m1) + m2;
-              const wn_f2 c1 = __builtin_elementwise_fma(neg1, m3, __builtin_elementwise_fma(neg1, m2, m1));   // (m1 - m2) - m3
-              float* o0 = &O[o_wr + ((r & 3) + 8 * (r >> 2)) * CO + 32 * n];
-              float* o1 = o0 + 32 * CO;
-              o0[0] = c0.x; o0[CO] = c0.y;
-              o1[0] = c1.x; o1[CO] = c1.y;
-            }
-          }
-          SR_TR(11);
-          __syncthreads();
-          SR_TR(13);
-          __builtin_amdgcn_sched_barrier(0);   // (keeps the prologue pieces out of the column transform: registers)
-          prime_next();   // the accumulators are dead: next region's first weights + first transform, under the stores
-          __builtin_amdgcn_sched_barrier(0);
-#pragma unroll
-          for (int it = 0; it < UNITS; ++it) {
-            float4 t[4][2];
-#pragma unroll
-            for (int ur = 0; ur < 4; ++ur)
-#pragma unroll
-              for (int bb = 0; bb < 2; ++bb)
-                t[ur][bb] = *reinterpret_cast<const float4*>(&O[o_rd + ((ur * 2 + bb) * 32 + (256 / CG) * it) * CO]);
-            const float4 y[4] = {f4add(f4add(t[0][0], t[1][0]), t[2][0]), f4add(f4add(t[0][1], t[1][1]), t[2][1]),
-                                 f4sub(f4sub(t[1][0], t[2][0]), t[3][0]), f4sub(f4sub(t[1][1], t[2][1]), t[3][1])};
-            float o16[16];
+          for (int it = 0; it < UNITS; ++it)
 #pragma unroll
             for (int q = 0; q < 4; ++q) {
-              float4 v = f4add(y[q], bv);
-              if (RES) v = f4add(v, rv[it][q]);
-              if (fast_leaky) {   // (same values as sr_activate_group's max(v, slope v), with the products packed)
-                const wn_f2 lo = wn_f2{v.x, v.y} * slope2, hi = wn_f2{v.z, v.w} * slope2;
-                v = make_float4(sr_vmax(v.x, lo.x), sr_vmax(v.y, lo.y), sr_vmax(v.z, hi.x), sr_vmax(v.w, hi.y));
-              }
-              o16[4 * q + 0] = v.x; o16[4 * q + 1] = v.y; o16[4 * q + 2] = v.z; o16[4 * q + 3] = v.w;
+              const int oy = oy0 + 2 * (tr0 + TILE_ROWS_PER_UNIT * it) + (q >> 1), ox = ox0 + 2 * tc0 + (q & 1);
+              okm |= (unsigned)(okc & (oy < p.H) & (ox < p.W)) << (4 * it + q);
             }
-            if (!fast_leaky) sr_activate_group(o16, slope);
+        }
+        auto lane_off = [&](unsigned v, int it, int q) { return (FULL || ((okm >> (4 * it + q)) & 1u)) ? v : WN_OOB; };
+        float4 rv[UNITS][4];
+        if (RES) {
 #pragma unroll
-            for (int q = 0; q < 4; ++q) {
-              if (!SR_WN_DBG(1) || o16[4 * q] == 1.2345e33f)
-                wn_io_store<IO>(make_float4(o16[4 * q], o16[4 * q + 1], o16[4 * q + 2], o16[4 * q + 3]), rs_out,
-                             lane_off(v_out, it, q), s_out0 + d_pix(it, q) * osp4);
-            }
-          }
-        };
-        if (full) { if (resp) epilogue(std::true_type{}, std::true_type{}); else epilogue(std::true_type{}, std::false_type{}); }
-        else { if (resp) epilogue(std::false_type{}, std::true_type{}); else epilogue(std::false_type{}, std::false_type{}); }
-#ifdef SR_WINO_TRACE
-        if (tr_region > 0) SR_TR(15);
-#endif
-        __syncthreads();
-        SR_TR(14);
-      } else {
-        constexpr int UNITS = 32 * CO / 256;  // (tile, channel) units per thread
-        // (1) residual values first: their latency hides under the LDS exchange (and never sits between stores)
-        float rv[UNITS][4];
-        bool ok[UNITS][4];
-        unsigned opix[UNITS][4];
-        const int co = tid & (CO - 1);
-        const int cog = co0 + co;
-        const bool okc = cog < p.Cout;
+          for (int it = 0; it < UNITS; ++it)
 #pragma unroll
-        for (int it = 0; it < UNITS; ++it) {
-          const int tile = tid / CO + (256 / CO) * it;
-          const int tr = tile >> 3, tc = tile & 7;
+            for (int q = 0; q < 4; ++q)
+              rv[it][q] = wn_io_load<IO>(rs_res, lane_off(v_res, it, q), s_res0 + d_pix(it, q) * rsp4);
+        }
+        const float4 bv = wn_buf_load(rs_bias, (FULL || okc) ? 16u * cg : WN_OOB, (unsigned)co0 * 4u);
+        SR_TR(10);
 #pragma unroll
-          for (int q = 0; q < 4; ++q) {
-            const int oy = oy0 + 2 * tr + (q >> 1), ox = ox0 + 2 * tc + (q & 1);
-            ok[it][q] = okc & (oy < p.H) & (ox < p.W);
-            opix[it][q] = (unsigned)(oy * p.W + ox);
-            const bool ld = ok[it][q] & (resp != nullptr);
-            const float v = (resp ? resp : p.in)[ld ? opix[it][q] * (unsigned)p.res_sp + cog : 0u];
-            rv[it][q] = ld ? v : 0.0f;
+        for (int n = 0; n < NT; ++n) {
+          // whole-vector arithmetic: packed fp32 adds, half the VALU instructions of the element-wise form (every VALU
+          // instruction here costs matrix-pipe time of the co-resident workgroup)
+#pragma unroll
+          for (int r = 0; r < 16; r += 2) {   // register PAIRS spelled out: v_pk_add_f32 (the f32x16 form compiled to scalar adds)
+            const wn_f2 m0 = {acc[0][n][r], acc[0][n][r + 1]}, m1 = {acc[1][n][r], acc[1][n][r + 1]};
+            const wn_f2 m2 = {acc[2][n][r], acc[2][n][r + 1]}, m3 = {acc[3][n][r], acc[3][n][r + 1]};
+            const wn_f2 c0 = (m0 + m1) + m2;
+            const wn_f2 c1 = __builtin_elementwise_fma(neg1, m3, __builtin_elementwise_fma(neg1, m2, m1));   // (m1 - m2) - m3
+            float* o0 = &O[o_wr + ((r & 3) + 8 * (r >> 2)) * CO + 32 * n];
+            float* o1 = o0 + 32 * CO;
+            o0[0] = c0.x; o0[CO] = c0.y;
+            o1[0] = c1.x; o1[CO] = c1.y;
           }
         }
-        // (2) column transform in registers, then LDS
-#pragma unroll
-        for (int n = 0; n < NT; ++n)
-#pragma unroll
-          for (int r = 0; r < 16; ++r) {
-            const int tile = (r & 3) + 8 * (r >> 2) + 4 * kk;
-            const float m0 = acc[0][n][r], m1 = acc[1][n][r], m2 = acc[2][n][r], m3 = acc[3][n][r];
-            O[((wave * 2 + 0) * 32 + tile) * CO + 32 * n + i] = (m0 + m1) + m2;
-            O[((wave * 2 + 1) * 32 + tile) * CO + 32 * n + i] = (m1 - m2) - m3;
-          }
+        SR_TR(11);
         __syncthreads();
-        prime_next();
-        // (3) row transform, + bias + residual, LeakyReLU, store
-        const float bv = (bias_p && okc) ? bias_p[cog] : 0.0f;
+        SR_TR(13);
+        __builtin_amdgcn_sched_barrier(0);
 #pragma unroll
         for (int it = 0; it < UNITS; ++it) {
-          const int tile = tid / CO + (256 / CO) * it;
-          float t[4][2];
+          float4 t[4][2];
 #pragma unroll
           for (int ur = 0; ur < 4; ++ur)
 #pragma unroll
-            for (int bb = 0; bb < 2; ++bb) t[ur][bb] = O[((ur * 2 + bb) * 32 + tile) * CO + co];
-          const float y[4] = {(t[0][0] + t[1][0]) + t[2][0], (t[0][1] + t[1][1]) + t[2][1],
-                              (t[1][0] - t[2][0]) - t[3][0], (t[1][1] - t[2][1]) - t[3][1]};
-          float o4[4];
+            for (int bb = 0; bb < 2; ++bb)
+              t[ur][bb] = *reinterpret_cast<const float4*>(&O[o_rd + ((ur * 2 + bb) * 32 + (256 / CG) * it) * CO]);
+          const float4 y[4] = {f4add(f4add(t[0][0], t[1][0]), t[2][0]), f4add(f4add(t[0][1], t[1][1]), t[2][1]),
+                               f4sub(f4sub(t[1][0], t[2][0]), t[3][0]), f4sub(f4sub(t[1][1], t[2][1]), t[3][1])};
+          float o16[16];
 #pragma unroll
-          for (int q = 0; q < 4; ++q) o4[q] = y[q] + bv + rv[it][q];
-          sr_activate_group(o4, slope);
+          for (int q = 0; q < 4; ++q) {
+            float4 v = f4add(y[q], bv);
+            if (RES) v = f4add(v, rv[it][q]);
+            if (fast_leaky) {   // (same values as sr_activate_group's max(v, slope v), with the products packed)
+              const wn_f2 lo = wn_f2{v.x, v.y} * slope2, hi = wn_f2{v.z, v.w} * slope2;
+              v = make_float4(sr_vmax(v.x, lo.x), sr_vmax(v.y, lo.y), sr_vmax(v.z, hi.x), sr_vmax(v.w, hi.y));
+            }
+            o16[4 * q + 0] = v.x; o16[4 * q + 1] = v.y; o16[4 * q + 2] = v.z; o16[4 * q + 3] = v.w;
+          }
+          if (!fast_leaky) sr_activate_group(o16, slope);
 #pragma unroll
-          for (int q = 0; q < 4; ++q)
-            if (ok[it][q] && (!SR_WN_DBG(1) || o4[q] == 1.2345e33f)) outp[opix[it][q] * out_sp + cog] = o4[q];
+          for (int q = 0; q < 4; ++q) {
+            wn_io_store<IO>(make_float4(o16[4 * q], o16[4 * q + 1], o16[4 * q + 2], o16[4 * q + 3]), rs_out,
+                            lane_off(v_out, it, q), s_out0 + d_pix(it, q) * osp4);
+          }
         }
-        __syncthreads();
+      };
+      if (full) { if (resp) epilogue(std::true_type{}, std::true_type{}); else epilogue(std::true_type{}, std::false_type{}); }
+      else { if (resp) epilogue(std::false_type{}, std::true_type{}); else epilogue(std::false_type{}, std::false_type{}); }
+#ifdef SR_WINO_TRACE
+      if (tr_region > 0) SR_TR(15);
+#endif
+      __syncthreads();
+      SR_TR(14);
+    } else {
+      constexpr int UNITS = 32 * CO / 256;  // (tile, channel) units per thread
+      // (1) residual values first: their latency hides under the LDS exchange (and never sits between stores)
+      float rv[UNITS][4];
+      bool ok[UNITS][4];
+      unsigned opix[UNITS][4];
+      const int co = tid & (CO - 1);
+      const int cog = co0 + co;
+      const bool okc = cog < p.Cout;
+#pragma unroll
+      for (int it = 0; it < UNITS; ++it) {
+        const int tile = tid / CO + (256 / CO) * it;
+        const int tr = tile >> 3, tc = tile & 7;
+#pragma unroll
+        for (int q = 0; q < 4; ++q) {
+          const int oy = oy0 + 2 * tr + (q >> 1), ox = ox0 + 2 * tc + (q & 1);
+          ok[it][q] = okc & (oy < p.H) & (ox < p.W);
+          opix[it][q] = (unsigned)(oy * p.W + ox);
+          const bool ld = ok[it][q] & (resp != nullptr);
+          const float v = (resp ? resp : p.in)[ld ? opix[it][q] * (unsigned)p.res_sp + cog : 0u];
+          rv[it][q] = ld ? v : 0.0f;
+        }
       }
+      // (2) column transform in registers, then LDS
+#pragma unroll
+      for (int n = 0; n < NT; ++n)
+#pragma unroll
+        for (int r = 0; r < 16; ++r) {
+          const int tile = (r & 3) + 8 * (r >> 2) + 4 * kk;
+          const float m0 = acc[0][n][r], m1 = acc[1][n][r], m2 = acc[2][n][r], m3 = acc[3][n][r];
+          O[((wave * 2 + 0) * 32 + tile) * CO + 32 * n + i] = (m0 + m1) + m2;
+          O[((wave * 2 + 1) * 32 + tile) * CO + 32 * n + i] = (m1 - m2) - m3;
+        }
+      __syncthreads();
+      // (3) row transform, + bias + residual, LeakyReLU, store
+      const float bv = (bias_p && okc) ? bias_p[cog] : 0.0f;
+#pragma unroll
+      for (int it = 0; it < UNITS; ++it) {
+        const int tile = tid / CO + (256 / CO) * it;
+        float t[4][2];
+#pragma unroll
+        for (int ur = 0; ur < 4; ++ur)
+#pragma unroll
+          for (int bb = 0; bb < 2; ++bb) t[ur][bb] = O[((ur * 2 + bb) * 32 + tile) * CO + co];
+        const float y[4] = {(t[0][0] + t[1][0]) + t[2][0], (t[0][1] + t[1][1]) + t[2][1],
+                            (t[1][0] - t[2][0]) - t[3][0], (t[1][1] - t[2][1]) - t[3][1]};
+        float o4[4];
+#pragma unroll
+        for (int q = 0; q < 4; ++q) o4[q] = y[q] + bv + rv[it][q];
+        sr_activate_group(o4, slope);
+#pragma unroll
+        for (int q = 0; q < 4; ++q)
+          if (ok[it][q]) outp[opix[it][q] * out_sp + cog] = o4[q];
+      }
+      __syncthreads();
     }
     reg = has_next ? nxt : decode(work + (int)gridDim.x < p.total ? work + (int)gridDim.x : work);
   }
@@ -830,22 +762,10 @@ static int sr_wino_run(const float* in, int64_t in_batch_stride, int in_pix_stri
   p.part_stride = (int64_t)B * H * W * Cout;
   p.co_blocks = p.Co_pad / (32 * nt);
   p.total = p.regions_x * p.regions_y * p.co_blocks * B * p.ksplit;
-#ifdef SR_WINO_ABLATION   // (ablation builds: read per call, so that one process can sweep the switches)
-  { const char* e = getenv("SR_WINO_DEBUG"); p.debug = e ? atoi(e) : 0; }
-#else
-  p.debug = 0;
-#endif
   p.xcd_order = sr_opt(SR_OPT_WINO_XCD);
-  p.stagger = sr_opt(SR_OPT_WINO_STAGGER);   // experiment switch, see below
   hipStream_t stream = (hipStream_t)stream_;
   int blocks = sr_wino_num_cus() * (nt == 1 ? SR_WINO_NT1_WAVES : SR_WINO_WAVES);
-  if (sr_opt(SR_OPT_WINO_WG_PER_CU) == 1) blocks = sr_wino_num_cus();  // ablation
   if (blocks > p.total) blocks = p.total;
-  if (p.stagger < 0) p.stagger = 0;
-  // (Measured, r04: an offset of 3 x s_sleep(127) is -14 % / -15 % on 64 -> 64 / 192 -> 64 @ 8x240x320 in an isolated loop over
-  // one layer -- 250 -> 216 us, 614 -> 519 us -- and NOTHING in the step: the same layers run 142 us on average inside the model
-  // with or without it, 28.44 vs 28.64 ms per step.  Launched back to back from a queue that runs ahead of the GPU the
-  // workgroups of a launch do not start in phase in the first place; the loop's launch gaps made them.  Off by default.)
   const size_t lds = (size_t)WN_LDS_FLOATS(nt) * sizeof(float);
 #ifdef SR_WINO_TRACE
   static unsigned long long* trace_buf = nullptr;

@@ -59,13 +59,6 @@ constexpr int W4_NA = SR_W4_NA, W4_PD = SR_W4_PD;
 __device__ __forceinline__ void w4_prio_other() { if (SR_W4_PRIO) __builtin_amdgcn_s_setprio(SR_W4_PRIO); }
 __device__ __forceinline__ void w4_prio_mfma() { if (SR_W4_PRIO) __builtin_amdgcn_s_setprio(0); }                      // weight-fragment register sets / prefetch distance (frequency pairs)
 
-// Phase ablations (timing experiments only, results are wrong): -DSR_W4_ABL=<bits>  1: no transform, 2: no MFMA phase,
-// 4: no epilogue, 8: every weight fragment from one cached address, 16: no staging loads / stores, 32: no operand loads in
-// the MFMA phase (bare MFMAs).  0 in the product build.
-#ifndef SR_W4_ABL
-#define SR_W4_ABL 0
-#endif
-
 struct SrWino4Params {
   const float* in; int64_t in_sb; int in_sp;
   const float* wu;                   // packed U: [36][S][4 kq][Co_pad][4]
@@ -99,27 +92,6 @@ __device__ __forceinline__ __amdgpu_buffer_rsrc_t w4_rsrc(const void* base, int6
 }
 __device__ __forceinline__ w4_f4 w4_load(__amdgpu_buffer_rsrc_t r, unsigned voff, unsigned soff) {
   return __builtin_bit_cast(w4_f4, __builtin_amdgcn_raw_buffer_load_b128(r, (int)voff, (int)soff, 0));
-}
-// cache-policy probes for the wave-specialised kernel's streams (gfx940+ aux bits: 1 = sc0, 2 = nt, 16 = sc1); product: 0
-#ifndef SR_W4WS_DEPHASE_UNIT
-#define SR_W4WS_DEPHASE_UNIT 1
-#endif
-#ifndef SR_W4WS_AUX_PATCH
-#define SR_W4WS_AUX_PATCH 0
-#endif
-#ifndef SR_W4WS_AUX_RES
-#define SR_W4WS_AUX_RES 0
-#endif
-#ifndef SR_W4WS_AUX_OUT
-#define SR_W4WS_AUX_OUT 0
-#endif
-template <int AUX>
-__device__ __forceinline__ w4_f4 w4_load_aux(__amdgpu_buffer_rsrc_t r, unsigned voff, unsigned soff) {
-  return __builtin_bit_cast(w4_f4, __builtin_amdgcn_raw_buffer_load_b128(r, (int)voff, (int)soff, AUX));
-}
-template <int AUX>
-__device__ __forceinline__ void w4_store_aux(w4_f4 v, __amdgpu_buffer_rsrc_t r, unsigned voff) {
-  __builtin_amdgcn_raw_buffer_store_b128(__builtin_bit_cast(w4_u4, v), r, (int)voff, 0, AUX);
 }
 // (the delta rides in the LANE offset: a 16-byte buffer store with an SGPR offset operand followed by a VALU write to its
 // data registers stores the new contents on gfx950 -- sr_wino.h, r04)
@@ -264,7 +236,7 @@ __device__ __forceinline__ void w4_epilogue(const SrWino4Params& p, const W4Item
 // temporaries; the 6 x 6 patch is read twice -- LDS reads are not what the phase waits for)
 __device__ __forceinline__ void w4_transform(const float* t_rd, float* t_wr) {
 #pragma unroll
-  for (int half = 0; half < ((SR_W4_ABL & 1) ? 0 : 2); ++half) {
+  for (int half = 0; half < 2; ++half) {
     float tt[3][6];
 #pragma unroll
     for (int c = 0; c < 6; ++c) {
@@ -297,7 +269,6 @@ __device__ __forceinline__ void w4_transform(const float* t_rd, float* t_wr) {
 template <int NA = W4_NA, int PD = W4_PD>
 __device__ __forceinline__ void w4_u_prefetch(__amdgpu_buffer_rsrc_t rs_u, unsigned u_voff, unsigned u_slab, unsigned u_fstride,
                                               w4_f4 (&ua)[NA][2]) {
-  if (SR_W4_ABL & (2 | 32)) return;
 #pragma unroll
   for (int fp = 0; fp < PD; ++fp) {
     ua[fp][0] = w4_load(rs_u, u_voff, u_slab + (unsigned)(2 * fp) * u_fstride);
@@ -309,48 +280,20 @@ __device__ __forceinline__ void w4_u_prefetch(__amdgpu_buffer_rsrc_t rs_u, unsig
 // W4_PD pairs of weight fragments are already in ua[]
 // FIRST: the accumulators start at zero (an item's first slab): the first MFMA of every frequency takes the constant 0 as its C
 // operand instead of 144 registers that somebody had to clear.
-#ifndef SR_W4WS_YIELD
-#define SR_W4WS_YIELD 0
-#endif
-#ifndef SR_W4WS_YIELD_PERIOD
-#define SR_W4WS_YIELD_PERIOD 1
-#endif
-constexpr int W4WS_YIELD = SR_W4WS_YIELD;   // wait states the M waves idle behind every W4WS_YIELD_PERIOD-th MFMA (w4_mfma_tick)
-constexpr int W4WS_YIELD_PERIOD = SR_W4WS_YIELD_PERIOD;
-// YIELD > 0 (wave-specialised form): `s_nop YIELD - 1` behind every MFMA.  An fp32 MFMA holds the wave's issue for its 32 clocks and
-// the M wave re-arbitrates with its next MFMA at once: the T wave on the SIMD gets a slot only every second or third MFMA
-// (profiles/r06_w4ws_trace.txt: its 51-instruction column pass takes the whole 4.9-k-clock stream) and does the rest of its tick
-// AFTER the stream while the M waves idle at the barrier.  A few wait states per MFMA are issue slots the T wave takes; they
-// cost the M wave their full length, so only as many as the T wave's work needs.
-template <int N>
-__device__ __forceinline__ void w4_yield() {
-  if (N > 0) {
-    __builtin_amdgcn_sched_barrier(0);
-    asm volatile("s_nop %0" ::"n"(N > 16 ? 15 : (N > 0 ? N - 1 : 0)));
-    __builtin_amdgcn_sched_barrier(0);
-  }
-}
-template <bool FIRST = false, int NA = W4_NA, int PD = W4_PD, int YIELD = 0>
+template <bool FIRST = false, int NA = W4_NA, int PD = W4_PD>
 __device__ __forceinline__ void w4_mfma_tick(__amdgpu_buffer_rsrc_t rs_u, unsigned u_voff, unsigned u_slab, unsigned u_fstride,
-                                             const float* m_rd, w4_f4 (&ua)[NA][2], w4_f4 (&acc)[36], int lane) {
-  if (SR_W4_ABL & 2) return;
+                                             const float* m_rd, w4_f4 (&ua)[NA][2], w4_f4 (&acc)[36]) {
   w4_prio_mfma();
   w4_f4 vb[2][2];
-  if (SR_W4_ABL & 32) {
-#pragma unroll
-    for (int a = 0; a < NA; ++a) ua[a][0] = ua[a][1] = w4_f4{1.0f, 2.0f, 3.0f, (float)u_slab};
-    vb[0][0] = vb[0][1] = vb[1][0] = vb[1][1] = w4_f4{1.0f, 0.5f, 0.25f, (float)lane};
-  } else {
-    vb[0][0] = *reinterpret_cast<const w4_f4*>(m_rd);
-    vb[0][1] = *reinterpret_cast<const w4_f4*>(m_rd + 256);
-  }
+  vb[0][0] = *reinterpret_cast<const w4_f4*>(m_rd);
+  vb[0][1] = *reinterpret_cast<const w4_f4*>(m_rd + 256);
 #pragma unroll
   for (int fp = 0; fp < 18; ++fp) {
-    if (!(SR_W4_ABL & 32) && fp + PD < 18) {
+    if (fp + PD < 18) {
       ua[(fp + PD) % NA][0] = w4_load(rs_u, u_voff, u_slab + (unsigned)(2 * (fp + PD)) * u_fstride);
       ua[(fp + PD) % NA][1] = w4_load(rs_u, u_voff, u_slab + (unsigned)(2 * (fp + PD) + 1) * u_fstride);
     }
-    if (!(SR_W4_ABL & 32) && fp + 1 < 18) {
+    if (fp + 1 < 18) {
       vb[(fp + 1) & 1][0] = *reinterpret_cast<const w4_f4*>(m_rd + (2 * fp + 2) * 256);
       vb[(fp + 1) & 1][1] = *reinterpret_cast<const w4_f4*>(m_rd + (2 * fp + 3) * 256);
     }
@@ -358,9 +301,7 @@ __device__ __forceinline__ void w4_mfma_tick(__amdgpu_buffer_rsrc_t rs_u, unsign
     for (int e = 0; e < 4; ++e) {
       const w4_f4 zero = w4_f4{0.0f, 0.0f, 0.0f, 0.0f};
       acc[2 * fp] = __builtin_amdgcn_mfma_f32_16x16x4f32(ua[fp % NA][0][e], vb[fp & 1][0][e], (FIRST && e == 0) ? zero : acc[2 * fp], 0, 0, 0);
-      if ((8 * fp + 2 * e) % W4WS_YIELD_PERIOD == 0) w4_yield<YIELD>();
       acc[2 * fp + 1] = __builtin_amdgcn_mfma_f32_16x16x4f32(ua[fp % NA][1][e], vb[fp & 1][1][e], (FIRST && e == 0) ? zero : acc[2 * fp + 1], 0, 0, 0);
-      if ((8 * fp + 2 * e + 1) % W4WS_YIELD_PERIOD == 0) w4_yield<YIELD>();
       __builtin_amdgcn_sched_barrier(0);   // keep the two accumulators interleaved (left alone hipcc issues 4 dependent MFMAs in a row)
     }
   }
@@ -369,13 +310,6 @@ __device__ __forceinline__ void w4_mfma_tick(__amdgpu_buffer_rsrc_t rs_u, unsign
 
 __device__ __forceinline__ void w4_finish(const SrWino4Params& p, const W4Item& it, w4_f4 (&acc)[36], int wave, int m_kq,
                                           int m_j, int tid) {
-  if (SR_W4_ABL & 4) {   // keep the accumulators alive without an epilogue
-    w4_f4 sum = acc[0];
-#pragma unroll
-    for (int f = 1; f < 36; ++f) sum = sum + acc[f];
-    if (sum[0] + sum[1] + sum[2] + sum[3] == 1.2345e33f) p.out[tid] = sum[0];
-    return;
-  }
   const int cq = it.co0 + 16 * wave + 4 * m_kq;                       // first of this lane's 4 output channels
   const bool full = (it.oy0 + 16 <= p.H) & (it.ox0 + 16 <= p.W);      // uniform
   if (p.res != nullptr) {
@@ -403,8 +337,8 @@ __global__ __launch_bounds__(256, 2) void sr_wino4_kernel(SrWino4Params p) {
   const int m_sig = (0x1230 >> (m_j & 12)) & 3;
   const float* m_rd = lds + W4_RAW_FLOATS + m_j * 16 + 4 * (m_kq ^ m_sig);
   const unsigned u_voff = (unsigned)(m_kq * p.Co_pad + 16 * wave + m_j) * 16u;
-  const unsigned u_fstride = (SR_W4_ABL & 8) ? 0u : (unsigned)p.S * 4u * (unsigned)p.Co_pad * 16u;   // bytes between two frequencies
-  const unsigned u_sstride = (SR_W4_ABL & 8) ? 0u : 4u * (unsigned)p.Co_pad * 16u;                   // ... two slabs
+  const unsigned u_fstride = (unsigned)p.S * 4u * (unsigned)p.Co_pad * 16u;   // bytes between two frequencies
+  const unsigned u_sstride = 4u * (unsigned)p.Co_pad * 16u;                   // ... two slabs
   const int st_q = tid & 3, st_pp0 = tid >> 2;
   float* st_wr = lds + st_pp0 * W4_RS + 4 * st_q;
 
@@ -421,21 +355,20 @@ __global__ __launch_bounds__(256, 2) void sr_wino4_kernel(SrWino4Params p) {
     w4_f4 acc[36];
 #pragma unroll
     for (int f = 0; f < 36; ++f) acc[f] = w4_f4{0.0f, 0.0f, 0.0f, 0.0f};
-    const unsigned u_item = (SR_W4_ABL & 8) ? 0u : (unsigned)it.co0 * 16u;
+    const unsigned u_item = (unsigned)it.co0 * 16u;
     for (int s = 0; s < p.S; ++s) {
-      if (!(SR_W4_ABL & 16)) {   // this slab's patch registers -> LDS; then the next slab's (or the next item's first) loads
+      // this slab's patch registers -> LDS; then the next slab's (or the next item's first) loads
 #pragma unroll
-        for (int j = 0; j < W4_STAGE - 1; ++j) *reinterpret_cast<w4_f4*>(st_wr + j * 64 * W4_RS) = st[j];
-        if (tid < 16) *reinterpret_cast<w4_f4*>(st_wr + (W4_STAGE - 1) * 64 * W4_RS) = st[W4_STAGE - 1];
-        if (s + 1 < p.S) w4_stage(p, it, s + 1, st_q, st_pp0, st);
-        else if (has_next) w4_stage(p, nxt, 0, st_q, st_pp0, st);
-      }
+      for (int j = 0; j < W4_STAGE - 1; ++j) *reinterpret_cast<w4_f4*>(st_wr + j * 64 * W4_RS) = st[j];
+      if (tid < 16) *reinterpret_cast<w4_f4*>(st_wr + (W4_STAGE - 1) * 64 * W4_RS) = st[W4_STAGE - 1];
+      if (s + 1 < p.S) w4_stage(p, it, s + 1, st_q, st_pp0, st);
+      else if (has_next) w4_stage(p, nxt, 0, st_q, st_pp0, st);
       __syncthreads();   // raw visible; every wave is past the previous slab's V reads
       w4_transform(t_rd, t_wr);
       __syncthreads();   // V visible (and raw free for the next slab's store)
       w4_f4 ua[W4_NA][2];
       w4_u_prefetch(rs_u, u_voff, u_item + (unsigned)s * u_sstride, u_fstride, ua);
-      w4_mfma_tick(rs_u, u_voff, u_item + (unsigned)s * u_sstride, u_fstride, m_rd, ua, acc, lane);
+      w4_mfma_tick(rs_u, u_voff, u_item + (unsigned)s * u_sstride, u_fstride, m_rd, ua, acc);
     }
     w4_finish(p, it, acc, wave, m_kq, m_j, tid);
     if (!has_next) break;
@@ -472,8 +405,8 @@ __global__ __launch_bounds__(512, 2) void sr_wino4pp_kernel(SrWino4Params p) {
   const int m_sig = (0x1230 >> (m_j & 12)) & 3;
   const float* m_rd = lds + W4_RAW_FLOATS + m_j * 16 + 4 * (m_kq ^ m_sig);
   const unsigned u_voff = (unsigned)(m_kq * p.Co_pad + 16 * wave + m_j) * 16u;
-  const unsigned u_fstride = (SR_W4_ABL & 8) ? 0u : (unsigned)p.S * 4u * (unsigned)p.Co_pad * 16u;
-  const unsigned u_sstride = (SR_W4_ABL & 8) ? 0u : 4u * (unsigned)p.Co_pad * 16u;   // bytes between two slabs
+  const unsigned u_fstride = (unsigned)p.S * 4u * (unsigned)p.Co_pad * 16u;
+  const unsigned u_sstride = 4u * (unsigned)p.Co_pad * 16u;   // bytes between two slabs
   const int st_q = tid & 3, st_pp0 = tid >> 2;
   float* st_wr = lds + st_pp0 * W4_RS + 4 * st_q;
 
@@ -504,35 +437,33 @@ __global__ __launch_bounds__(512, 2) void sr_wino4pp_kernel(SrWino4Params p) {
     // writers are 4 waves and the readers other threads of the group: the tick barrier below comes AFTER T, so synchronise the
     // group here through a workgroup barrier that the other group matches with one of its own ticks)
     w4_stage(p, it, 0, st_q, st_pp0, st);
-    if (!(SR_W4_ABL & 16)) {
 #pragma unroll
-      for (int j = 0; j < W4_STAGE - 1; ++j) *reinterpret_cast<w4_f4*>(st_wr + j * 64 * W4_RS) = st[j];
-      if (tid < 16) *reinterpret_cast<w4_f4*>(st_wr + (W4_STAGE - 1) * 64 * W4_RS) = st[W4_STAGE - 1];
-    }
+    for (int j = 0; j < W4_STAGE - 1; ++j) *reinterpret_cast<w4_f4*>(st_wr + j * 64 * W4_RS) = st[j];
+    if (tid < 16) *reinterpret_cast<w4_f4*>(st_wr + (W4_STAGE - 1) * 64 * W4_RS) = st[W4_STAGE - 1];
     {
       const bool more = p.S > 1 || n_mine > 1;
-      if (!(SR_W4_ABL & 16) && more) {
+      if (more) {
         if (p.S > 1) w4_stage(p, it, 1, st_q, st_pp0, st);
         else w4_stage(p, w4_decode(p, work + stride), 0, st_q, st_pp0, st);
       }
     }
     __syncthreads(); ++bars;   // raw(slab 0) visible to the group
     w4_transform(t_rd, t_wr);
-    w4_u_prefetch(rs_u, u_voff, (SR_W4_ABL & 8) ? 0u : (unsigned)it.co0 * 16u, u_fstride, ua);
+    w4_u_prefetch(rs_u, u_voff, (unsigned)it.co0 * 16u, u_fstride, ua);
     __syncthreads(); ++bars;   // ---- end of the first T tick
 
     for (int done = 0; done < n_mine; ++done) {
       const bool has_next = done + 1 < n_mine;
       const W4Item nxt = w4_decode(p, has_next ? work + stride : work);
-      const unsigned u_item = (SR_W4_ABL & 8) ? 0u : (unsigned)it.co0 * 16u;
+      const unsigned u_item = (unsigned)it.co0 * 16u;
       for (int s = 0; s < p.S; ++s) {
         // ---- M tick: MFMAs of slab s; then the patch in st[] (slab s + 1 / the next item's slab 0) -> raw and the loads of
         // the patch after that
         W4_TR(1);
-        w4_mfma_tick(rs_u, u_voff, u_item + (unsigned)s * u_sstride, u_fstride, m_rd, ua, acc, lane);
+        w4_mfma_tick(rs_u, u_voff, u_item + (unsigned)s * u_sstride, u_fstride, m_rd, ua, acc);
         W4_TR(2);
         const bool last = s + 1 == p.S;
-        if (!(SR_W4_ABL & 16) && (!last || has_next)) {
+        if (!last || has_next) {
 #pragma unroll
           for (int j = 0; j < W4_STAGE - 1; ++j) *reinterpret_cast<w4_f4*>(st_wr + j * 64 * W4_RS) = st[j];
           if (tid < 16) *reinterpret_cast<w4_f4*>(st_wr + (W4_STAGE - 1) * 64 * W4_RS) = st[W4_STAGE - 1];
@@ -562,7 +493,7 @@ __global__ __launch_bounds__(512, 2) void sr_wino4pp_kernel(SrWino4Params p) {
       for (int f = 0; f < 36; ++f) acc[f] = w4_f4{0.0f, 0.0f, 0.0f, 0.0f};
       if (has_next) {
         w4_transform(t_rd, t_wr);
-        w4_u_prefetch(rs_u, u_voff, (SR_W4_ABL & 8) ? 0u : (unsigned)nxt.co0 * 16u, u_fstride, ua);
+        w4_u_prefetch(rs_u, u_voff, (unsigned)nxt.co0 * 16u, u_fstride, ua);
         W4_TR(8);
         __syncthreads(); ++bars;
       }
@@ -643,27 +574,7 @@ __device__ __forceinline__ void w4_at2(w4_f2 m0, w4_f2 m1, w4_f2 m2, w4_f2 m3, w
   s2 = w4_fma2(0.25f, p, 4.0f * u);
   s3 = w4_fma2(0.125f, q, w4_fma2(8.0f, v, m5));
 }
-#ifndef SR_W4WS_XCD
-#define SR_W4WS_XCD 1   // (A/B: 0 = items dealt round-robin to the workgroups)
-#endif
-#ifndef SR_W4WS_TUNE
-#define SR_W4WS_TUNE 0   // A/B builds: 4: scalar output transform (384 v_* instead of 240 v_pk_*: same time, r06)
-#endif
-__device__ __forceinline__ float w4_opaque(float x) { asm volatile("" : "+v"(x)); return x; }   // (keeps the SLP vectoriser from pairing)
 __device__ __forceinline__ void w4_at_pk(w4_f4& a0, w4_f4& a1, w4_f4& a2, w4_f4& a3, const w4_f4& a4, const w4_f4& a5) {
-  if (SR_W4_ABL & 64) { a0 = a0 + a4; a1 = a1 + a5; return; }   // (timing experiments: nearly no arithmetic)
-  if (SR_W4WS_TUNE & 4) {
-#pragma unroll
-    for (int e = 0; e < 4; ++e) {
-      const float m0 = a0[e], m1 = a1[e], m2 = a2[e], m3 = a3[e], m4 = a4[e], m5 = a5[e];
-      const float p = w4_opaque(m1 + m2), q = w4_opaque(m1 - m2), u = w4_opaque(m3 + m4), v = w4_opaque(m3 - m4);
-      a0[e] = w4_opaque(w4_opaque(m0 + p) + u);
-      a1[e] = w4_opaque(fmaf(0.5f, q, w4_opaque(2.0f * v)));
-      a2[e] = w4_opaque(fmaf(0.25f, p, w4_opaque(4.0f * u)));
-      a3[e] = w4_opaque(fmaf(0.125f, q, w4_opaque(fmaf(8.0f, v, m5))));
-    }
-    return;
-  }
   w4_f2 lo[4], hi[4];
   w4_at2(w4_f2{a0[0], a0[1]}, w4_f2{a1[0], a1[1]}, w4_f2{a2[0], a2[1]}, w4_f2{a3[0], a3[1]}, w4_f2{a4[0], a4[1]}, w4_f2{a5[0], a5[1]},
          lo[0], lo[1], lo[2], lo[3]);
@@ -712,7 +623,6 @@ __device__ __forceinline__ void w4_transform36_half(const float* t_rd, float* t_
 #define W4_TF_STAMP(i) do {} while (0)
 __device__ __forceinline__ void w4_transform36_half(const float* t_rd, float* t_wr, bool upper) {
 #endif
-  if (SR_W4_ABL & 1) return;
   w4_f2 T[3][6];
   if (!upper) {
 #pragma unroll
@@ -752,7 +662,6 @@ __device__ __forceinline__ void w4_transform36_half(const float* t_rd, float* t_
 // SOME path makes the compiler's s_waitcnt for the loads in flight wait for everything.
 __device__ __forceinline__ void w4ws_stage(const SrWino4Params& p, const W4Item& it, int s, bool valid, int st_q, int st_pp0,
                                            const unsigned (&st_off)[W4_STAGE], w4_f4 (&st)[W4_STAGE]) {
-  if (SR_W4_ABL & 16) return;
   const bool interior = (it.oy0 >= 1) & (it.ox0 >= 1) & (it.oy0 + 17 <= p.H) & (it.ox0 + 17 <= p.W);   // uniform
   const unsigned in_img_bytes = (unsigned)(((int64_t)(p.H * p.W - 1) * p.in_sp + p.Cin) * 4);
   const __amdgpu_buffer_rsrc_t rs_in = w4_rsrc(p.in + (int64_t)it.b * p.in_sb, in_img_bytes);
@@ -761,10 +670,10 @@ __device__ __forceinline__ void w4ws_stage(const SrWino4Params& p, const W4Item&
     const unsigned base = (unsigned)(((it.oy0 - 1) * p.W + (it.ox0 - 1)) * p.in_sp + 16 * s) * 4u;   // scalar offset operand
     if (valid && 16 * s + 16 <= p.Cin) {   // (uniform) every channel quad of the slab exists
 #pragma unroll
-      for (int j = 0; j < W4_STAGE; ++j) st[j] = w4_load_aux<SR_W4WS_AUX_PATCH>(rs_in, st_off[j], base);
+      for (int j = 0; j < W4_STAGE; ++j) st[j] = w4_load(rs_in, st_off[j], base);
     } else {
 #pragma unroll
-      for (int j = 0; j < W4_STAGE; ++j) st[j] = w4_load_aux<SR_W4WS_AUX_PATCH>(rs_in, chan_ok ? st_off[j] : W4_OOB, base);
+      for (int j = 0; j < W4_STAGE; ++j) st[j] = w4_load(rs_in, chan_ok ? st_off[j] : W4_OOB, base);
     }
   } else {
     const unsigned q_off = (unsigned)(16 * s + 4 * st_q) * 4u;
@@ -792,7 +701,6 @@ __global__ __launch_bounds__(512, 2) void sr_wino4ws_kernel(SrWino4Params p) {
   const int lane = tid & 63;
   const int wave = __builtin_amdgcn_readfirstlane(tid >> 6);
   // this workgroup's items: first, first + item_stride, ...; K = n S slabs in a row; slab k - 1 closes an item iff k % S == 0
-#if SR_W4WS_XCD
   // XCD-aware work order: workgroup b runs on XCD b % 8 (observed dispatch order; speed only) and every XCD has its own L2, so
   // each XCD walks a CONTIGUOUS eighth of the items (a band of region rows of one image): the 2-pixel halo a patch shares with its
   // neighbours is fetched through the fabric once per XCD instead of once per region (round-robin: 1.31 x the algorithmic bytes).
@@ -802,13 +710,6 @@ __global__ __launch_bounds__(512, 2) void sr_wino4ws_kernel(SrWino4Params p) {
   const int n_items = first < x_end ? (x_end - first + n_x - 1) / n_x : 0;
   const int item_stride = n_x;
   if (n_items == 0) return;   // (uniform: the whole workgroup, before any barrier)
-#else
-  const int n_items = ((int)p.total - (int)blockIdx.x + (int)gridDim.x - 1) / (int)gridDim.x;
-  const int first = (int)blockIdx.x, item_stride = (int)gridDim.x;
-#endif
-#ifdef SR_W4WS_DEPHASE   // (probe builds: workgroups start a fraction of a tick apart -- profiles/r06_w4ws_trace.txt section 11)
-  for (int i = (((int)blockIdx.x >> 3) * SR_W4WS_DEPHASE) & 63; i > 0; --i) __builtin_amdgcn_s_sleep(SR_W4WS_DEPHASE_UNIT);
-#endif
   const int K = n_items * p.S;
   const bool one_slab = p.S == 1;   // an item closes on EVERY tick: half 1 of a tile is read in the tick that writes half 0 of the next
   const W4Cursor step = w4_cursor(p, item_stride);
@@ -847,7 +748,6 @@ __global__ __launch_bounds__(512, 2) void sr_wino4ws_kernel(SrWino4Params p) {
     const char* const OUT = reinterpret_cast<const char*>(lds + W4_WS_OUT) + ((tid >> 4) * 64) * 4;   // pixel 0's record
     const int o_cx = 16 * (o_c ^ o_t0);                     // its 16-byte chunk; pixel i: chunk o_c ^ tile_i = (o_c ^ t0) ^ 2 i
     const float slope = sr_uniform(p.slope);
-    constexpr bool has_res = RES && !(SR_W4_ABL & 4);
     const unsigned out_img_bytes = (unsigned)(((int64_t)(p.H * p.W - 1) * p.out_sp + p.Cout) * 4);
     const unsigned res_img_bytes = (unsigned)(((int64_t)(p.H * p.W - 1) * p.res_sp + p.Cout) * 4);
 
@@ -863,7 +763,6 @@ __global__ __launch_bounds__(512, 2) void sr_wino4ws_kernel(SrWino4Params p) {
       if (++ld_s == p.S) { ld_s = 0; w4_cursor_advance(p, ld, step); }
     };
     auto store_patch = [&](int par) {
-      if (SR_W4_ABL & 16) return;
       float* wr = lds + par * W4_RAW_FLOATS + st_wr_off;
 #pragma unroll
       for (int j = 0; j < W4_STAGE - 1; ++j) *reinterpret_cast<w4_f4*>(wr + j * 64 * W4_RS) = st[j];
@@ -871,11 +770,10 @@ __global__ __launch_bounds__(512, 2) void sr_wino4ws_kernel(SrWino4Params p) {
     };
     // residual of the whole 16 x 16 x 64 tile of item `eit` + its bias quad (an empty buffer reads 0): 17 loads
     auto residual_loads = [&](const W4Item& eit) {
-      if (SR_W4_ABL & 4) return;
       const bool cq_ok = eit.co0 + 4 * o_c < p.Cout;
       bv = __builtin_bit_cast(w4_f4, __builtin_amdgcn_raw_buffer_load_b128(w4_rsrc(p.bias ? p.bias : p.wu, p.bias ? (int64_t)p.Cout * 4 : 0),
                                                                           (int)(cq_ok ? (unsigned)(eit.co0 + 4 * o_c) * 4u : W4_OOB), 0, 0));
-      if (!has_res) return;
+      if (!RES) return;
       const bool full = (eit.oy0 + 16 <= p.H) & (eit.ox0 + 16 <= p.W);   // uniform
       const __amdgpu_buffer_rsrc_t rs_res = w4_rsrc(p.res + (int64_t)eit.b * p.res_sb, res_img_bytes);
       const unsigned rbase = (unsigned)((eit.oy0 * p.W + eit.ox0) * p.res_sp + eit.co0) * 4u;   // scalar
@@ -886,21 +784,19 @@ __global__ __launch_bounds__(512, 2) void sr_wino4ws_kernel(SrWino4Params p) {
         for (int i = 0; i < 8; ++i) {
           const unsigned d = (unsigned)(((4 * (i >> 1) + 2 * h) * p.W + 8 * (i & 1)) * p.res_sp) * 4u;   // scalar
           if (full) {
-            rv[8 * h + i] = w4_load_aux<SR_W4WS_AUX_RES>(rs_res, rl, rbase + d);
+            rv[8 * h + i] = w4_load(rs_res, rl, rbase + d);
           } else {
             const bool ok = (eit.oy0 + 4 * (i >> 1) + 2 * h + o_kk < p.H) & (eit.ox0 + 4 * o_t0 + 8 * (i & 1) + o_l < p.W);
-            rv[8 * h + i] = w4_load_aux<SR_W4WS_AUX_RES>(rs_res, ok ? rl : W4_OOB, rbase + d);
+            rv[8 * h + i] = w4_load(rs_res, ok ? rl : W4_OOB, rbase + d);
           }
         }
     };
     auto read_half = [&](w4_f4 (&y)[8]) {
-      if (SR_W4_ABL & 4) return;
 #pragma unroll
       for (int i = 0; i < 8; ++i) y[i] = *reinterpret_cast<const w4_f4*>(OUT + i * 16 * 64 * 4 + (o_cx ^ (32 * i)));
     };
     // half h of the tile of item `eit`: + bias + residual, activation, stores
     auto output_half = [&](const W4Item& eit, int h, const w4_f4 (&y)[8]) {
-      if (SR_W4_ABL & 4) return;
       const bool cq_ok = eit.co0 + 4 * o_c < p.Cout;
       const bool full = (eit.oy0 + 16 <= p.H) & (eit.ox0 + 16 <= p.W);   // uniform
       const __amdgpu_buffer_rsrc_t rs_out = w4_rsrc(p.out + (int64_t)eit.b * p.out_sb, out_img_bytes);
@@ -910,7 +806,7 @@ __global__ __launch_bounds__(512, 2) void sr_wino4ws_kernel(SrWino4Params p) {
 #pragma unroll
       for (int i = 0; i < 8; ++i) {
         w4_f4 v = y[i] + bv;
-        if (has_res) v = v + rv[8 * h + i];
+        if (RES) v = v + rv[8 * h + i];
 #pragma unroll
         for (int e = 0; e < 4; ++e) o[4 * i + e] = v[e];
       }
@@ -927,14 +823,14 @@ __global__ __launch_bounds__(512, 2) void sr_wino4ws_kernel(SrWino4Params p) {
       if (full) {
 #pragma unroll
         for (int i = 0; i < 8; ++i)
-          w4_store_aux<SR_W4WS_AUX_OUT>(w4_f4{o[4 * i], o[4 * i + 1], o[4 * i + 2], o[4 * i + 3]}, rs_out,
-                                        ol + obase + (unsigned)(((4 * (i >> 1) + 2 * h) * p.W + 8 * (i & 1)) * p.out_sp) * 4u);
+          w4_store(w4_f4{o[4 * i], o[4 * i + 1], o[4 * i + 2], o[4 * i + 3]}, rs_out,
+                   ol + obase + (unsigned)(((4 * (i >> 1) + 2 * h) * p.W + 8 * (i & 1)) * p.out_sp) * 4u);
       } else {
 #pragma unroll
         for (int i = 0; i < 8; ++i) {
           const bool ok = (eit.oy0 + 4 * (i >> 1) + 2 * h + o_kk < p.H) & (eit.ox0 + 4 * o_t0 + 8 * (i & 1) + o_l < p.W);
           const unsigned voff = ol + obase + (unsigned)(((4 * (i >> 1) + 2 * h) * p.W + 8 * (i & 1)) * p.out_sp) * 4u;
-          w4_store_aux<SR_W4WS_AUX_OUT>(w4_f4{o[4 * i], o[4 * i + 1], o[4 * i + 2], o[4 * i + 3]}, rs_out, ok ? voff : W4_OOB);
+          w4_store(w4_f4{o[4 * i], o[4 * i + 1], o[4 * i + 2], o[4 * i + 3]}, rs_out, ok ? voff : W4_OOB);
         }
       }
     };
@@ -999,8 +895,8 @@ __global__ __launch_bounds__(512, 2) void sr_wino4ws_kernel(SrWino4Params p) {
     const int m_sig = (0x1230 >> (m_j & 12)) & 3;
     const int m_rd_off = W4_WS_RAW2 + m_j * 16 + 4 * (m_kq ^ m_sig);
     const unsigned u_voff = (unsigned)(m_kq * p.Co_pad + 16 * wave + m_j) * 16u;
-    const unsigned u_fstride = (SR_W4_ABL & 8) ? 0u : (unsigned)p.S * 4u * (unsigned)p.Co_pad * 16u;
-    const unsigned u_sstride = (SR_W4_ABL & 8) ? 0u : 4u * (unsigned)p.Co_pad * 16u;
+    const unsigned u_fstride = (unsigned)p.S * 4u * (unsigned)p.Co_pad * 16u;
+    const unsigned u_sstride = 4u * (unsigned)p.Co_pad * 16u;
     const __amdgpu_buffer_rsrc_t rs_u = w4_rsrc(p.wu, (int64_t)36 * p.S * 4 * p.Co_pad * 16);
     // this lane's 16-byte chunk (output channels 16 wave + 4 m_kq ...) of the 8 pixel records of its tile's half
     float* const OUT = lds + W4_WS_OUT + m_j * 8 * 64 + 4 * ((4 * wave + m_kq) ^ m_j);
@@ -1008,55 +904,46 @@ __global__ __launch_bounds__(512, 2) void sr_wino4ws_kernel(SrWino4Params p) {
     w4_f4 ua[W4WS_NA][2];
     W4Cursor cur = w4_cursor(p, first);
     int s = 0;
-    w4_u_prefetch<W4WS_NA, W4WS_PD>(rs_u, u_voff, (SR_W4_ABL & 8) ? 0u : (unsigned)(64 * cur.cb) * 16u, u_fstride, ua);
+    w4_u_prefetch<W4WS_NA, W4WS_PD>(rs_u, u_voff, (unsigned)(64 * cur.cb) * 16u, u_fstride, ua);
     __syncthreads();   // (raw[0] visible to the T waves)
     __syncthreads();   // ---- F: end of tick 0
     for (int k = 1; k <= K; ++k) {
       W4_TR(1);
-      const unsigned u_item = (SR_W4_ABL & 8) ? 0u : (unsigned)(64 * cur.cb) * 16u;
+      const unsigned u_item = (unsigned)(64 * cur.cb) * 16u;
       const float* vrd = lds + ((k - 1) & 1) * W4_V_FLOATS + m_rd_off;
-      if (s == 0) w4_mfma_tick<true, W4WS_NA, W4WS_PD, W4WS_YIELD>(rs_u, u_voff, u_item, u_fstride, vrd, ua, acc, lane);
-      else w4_mfma_tick<false, W4WS_NA, W4WS_PD, W4WS_YIELD>(rs_u, u_voff, u_item + (unsigned)s * u_sstride, u_fstride, vrd, ua, acc, lane);
+      if (s == 0) w4_mfma_tick<true, W4WS_NA, W4WS_PD>(rs_u, u_voff, u_item, u_fstride, vrd, ua, acc);
+      else w4_mfma_tick<false, W4WS_NA, W4WS_PD>(rs_u, u_voff, u_item + (unsigned)s * u_sstride, u_fstride, vrd, ua, acc);
       W4_TR(2);
       if (++s == p.S) {   // (uniform) slab k - 1 closed an item
         s = 0;
         w4_cursor_advance(p, cur, step);
-        if (k < K) w4_u_prefetch<W4WS_NA, W4WS_PD>(rs_u, u_voff, (SR_W4_ABL & 8) ? 0u : (unsigned)(64 * cur.cb) * 16u, u_fstride, ua);
-        if (SR_W4_ABL & 4) {
-          w4_f4 sum = acc[0];
+        if (k < K) w4_u_prefetch<W4WS_NA, W4WS_PD>(rs_u, u_voff, (unsigned)(64 * cur.cb) * 16u, u_fstride, ua);
+        // Y = A^T M A in place: columns, then output rows 0-1 -> LDS, [F], rows 2-3 while the T waves fetch half 0, [B2], -> LDS, [B3]
+        W4_TR(8);
 #pragma unroll
-          for (int f = 1; f < 36; ++f) sum = sum + acc[f];
-          if (sum[0] + sum[1] + sum[2] + sum[3] == 1.2345e33f) p.out[tid] = sum[0];
-          if (one_slab && k >= 2) __syncthreads();
-          __syncthreads(); __syncthreads(); __syncthreads();
-        } else {
-          // Y = A^T M A in place: columns, then output rows 0-1 -> LDS, [F], rows 2-3 while the T waves fetch half 0, [B2], -> LDS, [B3]
-          W4_TR(8);
+        for (int j = 0; j < 6; ++j) w4_at_pk(acc[j], acc[6 + j], acc[12 + j], acc[18 + j], acc[24 + j], acc[30 + j]);
 #pragma unroll
-          for (int j = 0; j < 6; ++j) w4_at_pk(acc[j], acc[6 + j], acc[12 + j], acc[18 + j], acc[24 + j], acc[30 + j]);
+        for (int r = 0; r < 2; ++r) w4_at_pk(acc[6 * r], acc[6 * r + 1], acc[6 * r + 2], acc[6 * r + 3], acc[6 * r + 4], acc[6 * r + 5]);
+        W4_TR(6);
+        if (one_slab && k >= 2) __syncthreads();   // B4: the T waves have read half 1 of the previous tile
 #pragma unroll
-          for (int r = 0; r < 2; ++r) w4_at_pk(acc[6 * r], acc[6 * r + 1], acc[6 * r + 2], acc[6 * r + 3], acc[6 * r + 4], acc[6 * r + 5]);
-          W4_TR(6);
-          if (one_slab && k >= 2) __syncthreads();   // B4: the T waves have read half 1 of the previous tile
+        for (int r = 0; r < 2; ++r)
 #pragma unroll
-          for (int r = 0; r < 2; ++r)
+          for (int l = 0; l < 4; ++l) *reinterpret_cast<w4_f4*>(OUT + (4 * r + l) * 64) = acc[6 * r + l];
+        W4_TR(7);
+        __syncthreads();   // ---- F: end of tick k (half 0 visible)
+        W4_TR(12);
 #pragma unroll
-            for (int l = 0; l < 4; ++l) if (!(SR_W4_ABL & 128) || acc[0][0] == 1.2345e33f) *reinterpret_cast<w4_f4*>(OUT + (4 * r + l) * 64) = acc[6 * r + l];
-          W4_TR(7);
-          __syncthreads();   // ---- F: end of tick k (half 0 visible)
-          W4_TR(12);
+        for (int r = 2; r < 4; ++r) w4_at_pk(acc[6 * r], acc[6 * r + 1], acc[6 * r + 2], acc[6 * r + 3], acc[6 * r + 4], acc[6 * r + 5]);
+        W4_TR(9);
+        __syncthreads();   // B2: the T waves hold half 0
+        W4_TR(10);
 #pragma unroll
-          for (int r = 2; r < 4; ++r) w4_at_pk(acc[6 * r], acc[6 * r + 1], acc[6 * r + 2], acc[6 * r + 3], acc[6 * r + 4], acc[6 * r + 5]);
-          W4_TR(9);
-          __syncthreads();   // B2: the T waves hold half 0
-          W4_TR(10);
+        for (int r = 2; r < 4; ++r)
 #pragma unroll
-          for (int r = 2; r < 4; ++r)
-#pragma unroll
-            for (int l = 0; l < 4; ++l) if (!(SR_W4_ABL & 128) || acc[0][0] == 1.2345e33f) *reinterpret_cast<w4_f4*>(OUT + (4 * (r - 2) + l) * 64) = acc[6 * r + l];
-          __syncthreads();   // B3: half 1 visible
-          W4_TR(11);
-        }
+          for (int l = 0; l < 4; ++l) *reinterpret_cast<w4_f4*>(OUT + (4 * (r - 2) + l) * 64) = acc[6 * r + l];
+        __syncthreads();   // B3: half 1 visible
+        W4_TR(11);
       } else {
         if (k < K) w4_u_prefetch<W4WS_NA, W4WS_PD>(rs_u, u_voff, u_item + (unsigned)s * u_sstride, u_fstride, ua);
         W4_TR(7);
@@ -1245,9 +1132,6 @@ static int w4_run(const float* in, int64_t in_batch_stride, int in_pix_stride, c
   p.slope = leaky_slope;
   if (variant == 3) {   // wave-specialised: 4 MFMA waves + 4 transform waves, one workgroup per CU
     int blocks = w4_num_cus();
-#ifdef SR_W4WS_MAXBLOCKS   // (probe builds: how much of an item's time is chip-wide contention -- profiles/r06_w4ws_trace.txt section 11)
-    if (blocks > SR_W4WS_MAXBLOCKS) blocks = SR_W4WS_MAXBLOCKS;
-#endif
     if (blocks > p.total) blocks = p.total;
     const bool generic_act = !((leaky_slope >= 0.0f && leaky_slope <= 1.0f) || (leaky_slope < 0.0f && leaky_slope > -1.5f));
     auto kernel = generic_act ? (residual ? sr_wino4ws_kernel<true, true> : sr_wino4ws_kernel<true, false>)

@@ -93,10 +93,6 @@ __global__ void sr_wino_pack_split_kernel(const float* __restrict__ w, unsigned*
 }
 
 #define WS_PIN(...) asm volatile("" : __VA_ARGS__)
-#ifndef WS_ABL
-#define WS_ABL 0   // phase ablation (tuning builds only; results are wrong): 1 no staging loads, 2 no residual loads / output
-#endif             // stores, 4 no MFMAs, 8 no weight loads, 16 no input transform
-
 #ifndef SR_WS_NT1_WGS
 #define SR_WS_NT1_WGS 3   // workgroups per CU of the 32-channel instantiation: 3 fit its 46 KB of LDS and 168 registers (3 spills); the
 #endif                    // latency-bound split kernel gains 9 - 18 % on the 60x80 / 30x40 layers from the third (2: 45.9 / 55.1 us, 3: 42.0 / 45.1)
@@ -178,7 +174,7 @@ __global__ __launch_bounds__(256, NT == 1 ? SR_WS_NT1_WGS : 2) void sr_wino_spli
     } else {
 #pragma unroll
       for (int it = 0; it < WN_STAGE_PER_THREAD; ++it)
-        stg[it] = (WS_ABL & 1) ? make_float4(1.f, 2.f, 3.f, 4.f) : wn_buf_load(rs_in, (unsigned)offs[it], so);
+        stg[it] = wn_buf_load(rs_in, (unsigned)offs[it], so);
     }
   };
   static_assert(WN_STAGE_PER_THREAD == 3 && 2 * 256 < WN_STAGE_ELEMS, "only the third slot of a thread can be a spare");
@@ -195,9 +191,7 @@ __global__ __launch_bounds__(256, NT == 1 ? SR_WS_NT1_WGS : 2) void sr_wino_spli
     const int xi = 4 * wave + (s >> 1), g = s & 1;
     const char* wrec = reinterpret_cast<const char*>(reinterpret_cast<const float4*>(p.wu) + (int64_t)(xi * p.G + 2 * ch + g) * rec);
 #pragma unroll
-    for (int n = 0; n < NT; ++n)
-      dst[n] = (WS_ABL & 8) ? ws_u4{0x3c003c00u, 0x3c003c00u, 0x3c003c00u, 0x3c003c00u}
-                            : *reinterpret_cast<const ws_u4*>(wrec + (wu_lane + 512u * n));
+    for (int n = 0; n < NT; ++n) dst[n] = *reinterpret_cast<const ws_u4*>(wrec + (wu_lane + 512u * n));
   };
   auto rv_fma = [&](const float4 da, const float4 db) {
     const wn_f2 sg = {t_sign, t_sign};
@@ -253,13 +247,11 @@ __global__ __launch_bounds__(256, NT == 1 ? SR_WS_NT1_WGS : 2) void sr_wino_spli
       // the pieces of frequencies 0 and 1 fly while the slab is transformed
 #pragma unroll
       for (int s = 0; s < 4; ++s) load_b(sl0 + ch, s, b_f[s]);
-      if (!(WS_ABL & 16) || FIRST) {
 #pragma unroll
-        for (int g = 0; g < 2; ++g) {
+      for (int g = 0; g < 2; ++g) {
 #pragma unroll
-          for (int c = 0; c < 4; ++c) wq[c] = rv_col(raw, g, c);
-          rv_row(wq, av[g]);
-        }
+        for (int c = 0; c < 4; ++c) wq[c] = rv_col(raw, g, c);
+        rv_row(wq, av[g]);
       }
 #pragma unroll
       for (int uc = 0; uc < 4; ++uc) {
@@ -275,16 +267,14 @@ __global__ __launch_bounds__(256, NT == 1 ? SR_WS_NT1_WGS : 2) void sr_wino_spli
           if (FIRST) {
             const f32x16 zero = {0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f};
             acc[uc][n] = S::mfma(ah, b_f[sh][n], zero);
-          } else if (!(WS_ABL & 4)) {
+          } else {
             acc[uc][n] = S::mfma(ah, b_f[sh][n], acc[uc][n]);
           }
         }
-        if (!(WS_ABL & 4)) {
 #pragma unroll
-          for (int n = 0; n < NT; ++n) acc[uc][n] = S::mfma(ah, b_f[sl][n], acc[uc][n]);
+        for (int n = 0; n < NT; ++n) acc[uc][n] = S::mfma(ah, b_f[sl][n], acc[uc][n]);
 #pragma unroll
-          for (int n = 0; n < NT; ++n) acc[uc][n] = S::mfma(al, b_f[sh][n], acc[uc][n]);
-        }
+        for (int n = 0; n < NT; ++n) acc[uc][n] = S::mfma(al, b_f[sh][n], acc[uc][n]);
         __builtin_amdgcn_sched_barrier(0);
         if (uc < 2) {   // this frequency's register sets are free once its MFMAs are issued: frequency uc + 2 takes them
           load_b(sl0 + ch, 2 * uc + 4, b_f[sh]);
@@ -358,8 +348,7 @@ __global__ __launch_bounds__(256, NT == 1 ? SR_WS_NT1_WGS : 2) void sr_wino_spli
           for (int it = 0; it < UNITS; ++it)
 #pragma unroll
             for (int q = 0; q < 4; ++q)
-              rv[it][q] = (WS_ABL & 2) ? make_float4(0.f, 0.f, 0.f, 0.f)
-                                       : wn_buf_load(rs_res, lane_off(v_res, it, q), s_res0 + d_pix(it, q) * rsp4);
+              rv[it][q] = wn_buf_load(rs_res, lane_off(v_res, it, q), s_res0 + d_pix(it, q) * rsp4);
         }
         const float4 bv = wn_buf_load(rs_bias, (FULL || okc) ? 16u * cg : WN_OOB, (unsigned)co0 * 4u);
 #pragma unroll
@@ -409,9 +398,8 @@ __global__ __launch_bounds__(256, NT == 1 ? SR_WS_NT1_WGS : 2) void sr_wino_spli
           if (!fast_leaky) sr_activate_group(o16, slope);
 #pragma unroll
           for (int q = 0; q < 4; ++q)
-            if (!(WS_ABL & 2) || o16[4 * q] == 1.2345e33f)
-              wn_buf_store(make_float4(o16[4 * q], o16[4 * q + 1], o16[4 * q + 2], o16[4 * q + 3]), rs_out,
-                           lane_off(v_out, it, q), s_out0 + d_pix(it, q) * osp4);
+            wn_buf_store(make_float4(o16[4 * q], o16[4 * q + 1], o16[4 * q + 2], o16[4 * q + 3]), rs_out,
+                         lane_off(v_out, it, q), s_out0 + d_pix(it, q) * osp4);
         }
       };
       if (full) { if (resp) epilogue(std::true_type{}, std::true_type{}); else epilogue(std::true_type{}, std::false_type{}); }

@@ -62,10 +62,9 @@ def test_gradients_match_oracle_ragged_three_views():
         assert_close(grads[key], ref[key], what=key + " vs oracle")
 
 
-def test_matrix_core_backward_equals_valu_backward_and_handles_15_views(monkeypatch):
-    """The MFMA backward (default) against the r01 VALU kernel (SR_MLP_BWD_VALU is read once per process, so the VALU
-    result comes from the oracle instead) at 7 views, and at 15 views / 410 MLP inputs (BASELINE.json configs[4]), which
-    the VALU kernel could not run (Cin <= 256)."""
+def test_matrix_core_backward_matches_oracle_from_2_to_15_views():
+    """The MFMA backward against the oracle at 2 and 7 views, and at 15 views / 410 MLP inputs (BASELINE.json
+    configs[4]): the widest MLP input the kernel takes (Cin <= 416)."""
     for K, D, h, w in ((7, 3, 10, 21), (15, 2, 9, 14), (2, 4, 8, 8)):
         case = dict(model="hero", B=1, K=K, C=16, D=D, h=h, w=w, seed=20 + K)
         g = torch.Generator(device="cpu").manual_seed(K)
