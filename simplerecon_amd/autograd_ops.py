@@ -16,7 +16,7 @@ import torch
 from torch import nn
 
 from . import _lib
-from .ops import _is_nhwc_view, _pack, _strides, _workspace, as_nhwc, empty_nhwc
+from .ops import _is_nhwc_view, _pack, _strides, _timed, _workspace, as_nhwc, empty_nhwc
 
 
 # torch.autocast compatibility (the reference trains under 16-bit autocast, options.py:100-101, train.py:132): every
@@ -266,23 +266,34 @@ def _conv_raw(x, weight, bias, stride, residual=None, slope=None, pads=None):
     st = _lib.stream_ptr(x.device)
     with _lib.on_device(x.device):
         wp = _pack("wino" if use_wino else "conv", wd)
-        isb, isp = _strides(x)
-        osb, osp = _strides(out)
-        if residual is not None:
-            residual = as_nhwc(residual, "residual")
-        rsb, rsp = _strides(residual) if residual is not None else (0, 0)
-        bd = bias.detach().contiguous() if bias is not None else None
-        sl = C.c_float(-1.0 if slope is None else float(slope))
-        if use_wino:
-            rc = lib.sr_conv3x3_wino_nhwc_fwd(_lib.ptr(x), isb, isp, _lib.ptr(wp), _lib.ptr(bd), _lib.ptr(residual), rsb,
-                                              rsp, _lib.ptr(out), osb, osp, b, h, w, ci, co, sl, st)
-        elif pads is not None:
-            rc = lib.sr_conv2d_padded_nhwc_fwd(_lib.ptr(x), isb, isp, _lib.ptr(wp), _lib.ptr(bd), _lib.ptr(residual), rsb,
-                                               rsp, _lib.ptr(out), osb, osp, b, h, w, ci, co, k, stride, pt, pl, pb, pr, sl,
-                                               st)
+    isb, isp = _strides(x)
+    osb, osp = _strides(out)
+    if residual is not None:
+        residual = as_nhwc(residual, "residual")
+    rsb, rsp = _strides(residual) if residual is not None else (0, 0)
+    bd = bias.detach().contiguous() if bias is not None else None
+    sl = C.c_float(-1.0 if slope is None else float(slope))
+    vin = x.data_ptr() % 16 == 0 and isp % 4 == 0 and isb % 4 == 0
+
+    def record():   # ops.PROFILE: the kernel this launch ran (the data gradient's launches are told apart by it in tests)
+        if use_wino:   # (asked with aligned_out = 0: this entry point has no workspace, so its plan never splits K)
+            name = lib.sr_wino_kernel_name(b, h, w, ci, co, int(vin and ci % 4 == 0), 0).decode()
+            vout = vin and ci % 4 == 0 and co % 4 == 0 and out.data_ptr() % 16 == 0 and \
+                (bd is None or bd.data_ptr() % 16 == 0) and \
+                (residual is None or (residual.data_ptr() % 16 == 0 and rsp % 4 == 0 and rsb % 4 == 0))
+            if vout:
+                name = name.replace(", true, false>", ", true, true>")
         else:
-            rc = lib.sr_conv2d_nhwc_fwd(_lib.ptr(x), isb, isp, _lib.ptr(wp), _lib.ptr(bd), _lib.ptr(residual), rsb, rsp,
-                                        _lib.ptr(out), osb, osp, b, h, w, ci, co, k, stride, sl, st)
+            name = lib.sr_conv_kernel_name(b, h, w, ci, co, k, stride, int(vin)).decode()
+        return name, 2.0 * b * ho * wo * co * ci * k * k, (b, ci, h, w, co, k, stride, ho, wo, residual is not None), None
+    head = (_lib.ptr(x), isb, isp, _lib.ptr(wp), _lib.ptr(bd), _lib.ptr(residual), rsb, rsp, _lib.ptr(out), osb, osp, b, h, w,
+            ci, co)
+    if use_wino:
+        rc = _timed(x.device, record, lib.sr_conv3x3_wino_nhwc_fwd, *head, sl, st)
+    elif pads is not None:
+        rc = _timed(x.device, record, lib.sr_conv2d_padded_nhwc_fwd, *head, k, stride, pt, pl, pb, pr, sl, st)
+    else:
+        rc = _timed(x.device, record, lib.sr_conv2d_nhwc_fwd, *head, k, stride, sl, st)
     _lib.check(rc, "conv forward")
     return out
 

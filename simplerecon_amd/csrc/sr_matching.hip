@@ -163,8 +163,11 @@ __global__ __launch_bounds__(256, 2) void sr_stem_kernel(SrStemParams p) {
 // map).  One thread per (output pixel, 4 channels).  Interior pixels read their 5x5 window once (25 float4 loads,
 // vertical max then horizontal max); border pixels take the generic reflected path.
 __device__ __forceinline__ int sr_reflect(int i, int n) { return i < 0 ? -i : (i >= n ? 2 * n - 2 - i : i); }
+// NaN wins, like ATen's max_pool2d (and like sr_maxblurpool_bwd_nhwc, which routes the gradient to the NaN): fmaxf drops a
+// NaN operand, which made a NaN in the input vanish from the forward output
+__device__ __forceinline__ float sr_nanmax(float a, float b) { return (a > b || a != a) ? a : b; }
 __device__ __forceinline__ float4 sr_max4(float4 a, float4 b) {
-  return make_float4(fmaxf(a.x, b.x), fmaxf(a.y, b.y), fmaxf(a.z, b.z), fmaxf(a.w, b.w));
+  return make_float4(sr_nanmax(a.x, b.x), sr_nanmax(a.y, b.y), sr_nanmax(a.z, b.z), sr_nanmax(a.w, b.w));
 }
 __device__ __forceinline__ float4 sr_axpy4(float s, float4 a, float4 acc) {
   return make_float4(acc.x + s * a.x, acc.y + s * a.y, acc.z + s * a.z, acc.w + s * a.w);
