@@ -355,6 +355,26 @@ def on_device(device):
     return torch.cuda.device(device)
 
 
+_SCALARS = (int, float, type(None))   # (isinstance against torch.Tensor goes through its metaclass: three times the cost)
+
+
+def call(name, device, *args, allow=()):
+    """lib().<name>(*args, stream) with `device` current and torch's current stream on it as the trailing `void* stream`:
+    ints, floats and None (NULL) go in as they are (`argtypes` converts them), anything else is a tensor and goes in as its
+    device address.  A non-zero code raises HipLibraryError naming `name`, unless it is in `allow`: then it is returned.  For
+    entry points that launch; pure queries (workspace sizes, plans, kernel names) are plain lib() calls.  ops._launch and
+    what goes through ops._timed (the PROFILE bracket) call the library directly: batch-1 inference is host-bound on its
+    ~250 conv launches per frame, and this frame costs half a microsecond per call."""
+    ctx = on_device(device)
+    if ctx is not _NULL_CONTEXT:   # (another device: the same call with it current; no `with` frame on the usual path)
+        with ctx:
+            return call(name, device, *args, allow=allow)
+    rc = getattr(lib(), name)(*[a if isinstance(a, _SCALARS) else a.data_ptr() for a in args], stream_ptr(device))
+    if rc != 0 and rc not in allow:
+        check(rc, name)
+    return rc
+
+
 def refuse_autograd(*tensors):
     if torch.is_grad_enabled() and any(isinstance(t, torch.Tensor) and t.requires_grad for t in tensors):
         raise NotImplementedError(

@@ -9,14 +9,13 @@ torch.autograd is the tape (plumbing); every arithmetic step, forward and backwa
 Gradients are pinned to the reference's own autograd (tests/golden/grad_block_*.npz, grad_cv_encoder_narrow.npz,
 grad_decoder_narrow.npz).  Not covered yet: the two encoders (no BatchNorm / InstanceNorm backward) -- DepthModel treats
 their outputs as constants."""
-import ctypes as C
 import os
 
 import torch
 from torch import nn
 
 from . import _lib
-from .ops import _is_nhwc_view, _pack, _strides, _timed, _workspace, as_nhwc, empty_nhwc
+from .ops import _act_code, _conv_direct, _conv_wino, _is_nhwc_view, _pack, _strides, _workspace, as_nhwc, empty_nhwc
 
 
 # torch.autocast compatibility (the reference trains under 16-bit autocast, options.py:100-101, train.py:132): every
@@ -204,10 +203,14 @@ def _dense_nhwc(t):
     return t
 
 
+def _aligned8(t):
+    """None, or a 16-bit channels-last view whose pixel rows all start 8-byte aligned (four channels per access)."""
+    return t is None or (t.data_ptr() % 8 == 0 and all(s % 4 == 0 for s in _strides(t)))
+
+
 def _conv_raw_io(x, weight, bias, stride, residual, slope, pads):
     """_conv_raw on fp16 / bf16 activations: 16-bit kernel I/O where the kernel has it (3x3 / stride 1 through Winograd,
     1x1 / stride 1 through the pointwise GEMM), boundary conversion around the fp32 kernel otherwise."""
-    lib = _lib.lib()
     dt = x.dtype
     x = _nhwc_any(x, "conv input")
     b, ci, h, w = x.shape
@@ -217,37 +220,27 @@ def _conv_raw_io(x, weight, bias, stride, residual, slope, pads):
     if residual is not None:
         residual = _nhwc_any(residual if residual.dtype == dt else residual.to(dt), "residual")
     wino = pads is None and stride == 1 and k == 3 and b > 0 and ci % 4 == 0 and co % 4 == 0 and \
-        bool(lib.sr_conv_prefers_wino(b, h, w, ci, co, k, stride))
+        bool(_lib.lib().sr_conv_prefers_wino(b, h, w, ci, co, k, stride))
     pw = pads is None and stride == 1 and k == 1 and b > 0 and ci % 4 == 0
-    aligned = x.data_ptr() % 8 == 0 and _strides(x)[1] % 4 == 0 and _strides(x)[0] % 4 == 0 and \
-        (residual is None or (residual.data_ptr() % 8 == 0 and _strides(residual)[1] % 4 == 0 and _strides(residual)[0] % 4 == 0))
-    if not ((wino or pw) and aligned):
+    if not ((wino or pw) and _aligned8(x) and _aligned8(residual)):
         y = _conv_raw(x.float(), weight, bias, stride, residual.float() if residual is not None else None, slope, pads)
         return y.to(dt)
     out = torch.empty((b, co, h, w), dtype=dt, device=x.device, memory_format=torch.channels_last)
-    wd = weight.detach().float().contiguous()
-    st = _lib.stream_ptr(x.device)
-    isb, isp = _strides(x)
-    osb, osp = _strides(out)
-    rsb, rsp = _strides(residual) if residual is not None else (0, 0)
+    wp = _pack("wino" if wino else "conv", weight.detach().float().contiguous())
     bd = bias.detach().float().contiguous() if bias is not None else None
-    sl = C.c_float(-1.0 if slope is None else float(slope))
-    with _lib.on_device(x.device):
-        if wino:
-            wp = _pack("wino", wd)
-            rc = lib.sr_conv3x3_wino_io_nhwc_fwd(_lib.ptr(x), isb, isp, _lib.ptr(wp), _lib.ptr(bd), _lib.ptr(residual), rsb, rsp,
-                                                 _lib.ptr(out), osb, osp, b, h, w, ci, co, sl, _IO_CODE[dt], st)
-        else:
-            wp = _pack("conv", wd)
-            rc = lib.sr_pw_conv_io_nhwc_fwd(_lib.ptr(x), isb, isp, _lib.ptr(wp), _lib.ptr(bd), _lib.ptr(residual), rsb, rsp,
-                                            _lib.ptr(out), osb, osp, b, h * w, ci, co, sl, _IO_CODE[dt], st)
-    _lib.check(rc, "conv forward (16-bit I/O)")
+    rsb, rsp = _strides(residual) if residual is not None else (0, 0)
+    head = (x, *_strides(x), wp, bd, residual, rsb, rsp, out, *_strides(out), b)
+    if wino:
+        _lib.call("sr_conv3x3_wino_io_nhwc_fwd", x.device, *head, h, w, ci, co, _act_code(slope, None), _IO_CODE[dt])
+    else:
+        _lib.call("sr_pw_conv_io_nhwc_fwd", x.device, *head, h * w, ci, co, _act_code(slope, None), _IO_CODE[dt])
     return out
 
 
 def _conv_raw(x, weight, bias, stride, residual=None, slope=None, pads=None):
-    """act(conv(x, weight) + bias [+ residual]) on the inference kernels with a weight TENSOR [Co, Ci, k, k]
-    (packed on the fly; padding k // 2, or explicit (top, left, bottom, right) zero `pads`)."""
+    """act(conv(x, weight) + bias [+ residual]) on the inference launchers of ops with a weight TENSOR [Co, Ci, k, k]
+    (packed on the fly; padding k // 2, or explicit (top, left, bottom, right) zero `pads`).  Winograd F(2x2) where the
+    library prefers it, else the direct kernel; never F(4x4), the pointwise GEMM or split-K."""
     if x.dtype in _IO_CODE:
         return _conv_raw_io(x, weight, bias, stride, residual, slope, pads)
     lib = _lib.lib()
@@ -261,40 +254,18 @@ def _conv_raw(x, weight, bias, stride, residual=None, slope=None, pads=None):
     out = empty_nhwc(b, co, ho, wo, x.device)
     if b == 0:
         return out
-    wd = weight.detach().contiguous()
     use_wino = pads is None and stride == 1 and k == 3 and bool(lib.sr_conv_prefers_wino(b, h, w, ci, co, k, stride))
-    st = _lib.stream_ptr(x.device)
-    with _lib.on_device(x.device):
-        wp = _pack("wino" if use_wino else "conv", wd)
-    isb, isp = _strides(x)
-    osb, osp = _strides(out)
+    wp = _pack("wino" if use_wino else "conv", weight.detach().contiguous())
     if residual is not None:
         residual = as_nhwc(residual, "residual")
-    rsb, rsp = _strides(residual) if residual is not None else (0, 0)
     bd = bias.detach().contiguous() if bias is not None else None
-    sl = C.c_float(-1.0 if slope is None else float(slope))
-    vin = x.data_ptr() % 16 == 0 and isp % 4 == 0 and isb % 4 == 0
-
-    def record():   # ops.PROFILE: the kernel this launch ran (the data gradient's launches are told apart by it in tests)
-        if use_wino:   # (asked with aligned_out = 0: this entry point has no workspace, so its plan never splits K)
-            name = lib.sr_wino_kernel_name(b, h, w, ci, co, int(vin and ci % 4 == 0), 0).decode()
-            vout = vin and ci % 4 == 0 and co % 4 == 0 and out.data_ptr() % 16 == 0 and \
-                (bd is None or bd.data_ptr() % 16 == 0) and \
-                (residual is None or (residual.data_ptr() % 16 == 0 and rsp % 4 == 0 and rsb % 4 == 0))
-            if vout:
-                name = name.replace(", true, false>", ", true, true>")
-        else:
-            name = lib.sr_conv_kernel_name(b, h, w, ci, co, k, stride, int(vin)).decode()
-        return name, 2.0 * b * ho * wo * co * ci * k * k, (b, ci, h, w, co, k, stride, ho, wo, residual is not None), None
-    head = (_lib.ptr(x), isb, isp, _lib.ptr(wp), _lib.ptr(bd), _lib.ptr(residual), rsb, rsp, _lib.ptr(out), osb, osp, b, h, w,
-            ci, co)
+    strides = (*_strides(x), *_strides(out), *(_strides(residual) if residual is not None else (0, 0)))
+    # (the shape also goes into ops.PROFILE with the kernel the launch ran: the data gradient's launches are told apart by it)
+    shape = (b, ci, h, w, co, k, stride, ho, wo, residual is not None)
     if use_wino:
-        rc = _timed(x.device, record, lib.sr_conv3x3_wino_nhwc_fwd, *head, sl, st)
-    elif pads is not None:
-        rc = _timed(x.device, record, lib.sr_conv2d_padded_nhwc_fwd, *head, k, stride, pt, pl, pb, pr, sl, st)
+        _conv_wino(lib, x, wp, bd, residual, out, strides, shape, _act_code(slope, None), workspace=False, fallback=False)
     else:
-        rc = _timed(x.device, record, lib.sr_conv2d_nhwc_fwd, *head, k, stride, sl, st)
-    _lib.check(rc, "conv forward")
+        _conv_direct(lib, x, wp, bd, residual, out, strides, shape, _act_code(slope, None), pads, False, workspace=False)
     return out
 
 
@@ -343,7 +314,6 @@ class _ConvBiasAct(torch.autograd.Function):
         s = ctx.stride
         ho, wo = g.shape[2], g.shape[3]
         g = _dense_nhwc(g if g.dtype == torch.float32 else g.float())
-        st = _lib.stream_ptr(dev)
         need_x, need_w, need_b, need_r = ctx.needs_input_grad[:4]
         want_b = ctx.has_bias and need_b
         fused = FUSED_ACT_BIAS and co % 4 == 0 and b > 0 and (ctx.slope is not None or want_b)
@@ -357,14 +327,12 @@ class _ConvBiasAct(torch.autograd.Function):
                 ws = _workspace(dev, "bias_grad", nws) if want_b else None
                 if want_b:
                     d_b = torch.empty((co,), dtype=torch.float32, device=dev)
-                _lib.check(lib.sr_act_bwd_bias_nhwc(_lib.ptr(g), _lib.ptr(_dense_nhwc(out)) if ctx.slope is not None else None,
-                                                    _lib.ptr(gp) if ctx.slope is not None else None, _lib.ptr(d_b), px, co,
-                                                    C.c_float(float(ctx.slope) if ctx.slope is not None else 0.0),
-                                                    _lib.ptr(ws), nws, st), "sr_act_bwd_bias_nhwc")
+                _lib.call("sr_act_bwd_bias_nhwc", dev, g, _dense_nhwc(out) if ctx.slope is not None else None,
+                          gp if ctx.slope is not None else None, d_b, px, co,
+                          float(ctx.slope) if ctx.slope is not None else 0.0, ws, nws)
             elif ctx.slope is not None:
                 gp = torch.empty_like(g)
-                _lib.check(lib.sr_act_bwd(_lib.ptr(g), _lib.ptr(_dense_nhwc(out)), _lib.ptr(gp), g.numel(),
-                                          C.c_float(float(ctx.slope)), st), "sr_act_bwd")
+                _lib.call("sr_act_bwd", dev, g, _dense_nhwc(out), gp, g.numel(), float(ctx.slope))
             else:
                 gp = g
             d_x = d_w = None
@@ -377,31 +345,26 @@ class _ConvBiasAct(torch.autograd.Function):
                 if pads is None:
                     nws = lib.sr_conv_wgrad_workspace_bytes(b, h, w, ci, co, k, s)
                     ws = _workspace(dev, "wgrad", nws)
-                    _lib.check(lib.sr_conv_wgrad_nhwc(_lib.ptr(x), xsb, xsp, _lib.ptr(gp), gsb, gsp, _lib.ptr(d_w), b, h, w,
-                                                      ci, co, k, s, _lib.ptr(ws), nws, st), "sr_conv_wgrad_nhwc")
+                    _lib.call("sr_conv_wgrad_nhwc", dev, x, xsb, xsp, gp, gsb, gsp, d_w, b, h, w, ci, co, k, s, ws, nws)
                 else:
                     nws = lib.sr_conv_wgrad_padded_workspace_bytes(b, ho, wo, ci, co, k)
                     ws = _workspace(dev, "wgrad", nws)
-                    _lib.check(lib.sr_conv_wgrad_padded_nhwc(_lib.ptr(x), xsb, xsp, _lib.ptr(gp), gsb, gsp, _lib.ptr(d_w), b,
-                                                             h, w, ci, co, k, s, pads[0], pads[1], ho, wo, _lib.ptr(ws), nws,
-                                                             st), "sr_conv_wgrad_padded_nhwc")
+                    _lib.call("sr_conv_wgrad_padded_nhwc", dev, x, xsb, xsp, gp, gsb, gsp, d_w, b, h, w, ci, co, k, s,
+                              pads[0], pads[1], ho, wo, ws, nws)
             elif need_w:
                 d_w = torch.zeros(weight.shape, dtype=torch.float32, device=dev)
             if want_b and d_b is None:
                 d_b = torch.empty((co,), dtype=torch.float32, device=dev)
-                _lib.check(lib.sr_bias_grad_nhwc(_lib.ptr(gp), gsb, gsp, _lib.ptr(d_b), b, ho, wo, co, st),
-                           "sr_bias_grad_nhwc")
+                _lib.call("sr_bias_grad_nhwc", dev, gp, gsb, gsp, d_b, b, ho, wo, co)
             if need_x:
                 wt = torch.empty((ci, co, k, k), dtype=torch.float32, device=dev)
-                _lib.check(lib.sr_conv_flip_transpose_weights(_lib.ptr(weight.detach().contiguous()), co, ci, k,
-                                                              _lib.ptr(wt), st), "sr_conv_flip_transpose_weights")
+                _lib.call("sr_conv_flip_transpose_weights", dev, weight.detach().contiguous(), co, ci, k, wt)
                 if s == 1:
                     src = gp
                 else:  # stride 2: dL/dx = conv_s1(zero-stuffed dL/dy, flip(W)^T) on the input's grid
                     src = empty_nhwc(b, co, h, w, dev)
                     if b > 0:
-                        _lib.check(lib.sr_zero_stuff2x_nhwc(_lib.ptr(gp), gsb, gsp, _lib.ptr(src), b, ho, wo, h, w, co, st),
-                                   "sr_zero_stuff2x_nhwc")
+                        _lib.call("sr_zero_stuff2x_nhwc", dev, gp, gsb, gsp, src, b, ho, wo, h, w, co)
                 if pads is None:
                     d_x = _conv_raw(src, wt, None, 1)
                 elif s == 1:   # full correlation: pads k-1-p on the opposite roles
@@ -437,10 +400,7 @@ class _Upsample2x(torch.autograd.Function):
         if b > 0:
             gsb, gsp = _strides(g)
             osb, osp = _strides(out)
-            with _lib.on_device(g.device):
-                rc = _lib.lib().sr_upsample2x_bwd_nhwc(_lib.ptr(g), gsb, gsp, _lib.ptr(out), osb, osp, b, h, w, c,
-                                                       _lib.stream_ptr(g.device))
-            _lib.check(rc, "sr_upsample2x_bwd_nhwc")
+            _lib.call("sr_upsample2x_bwd_nhwc", g.device, g, gsb, gsp, out, osb, osp, b, h, w, c)
         return out
 
 
@@ -465,9 +425,7 @@ class _Exp(torch.autograd.Function):
             g = g.contiguous()
             y = y.contiguous()
         out = torch.empty_like(y)
-        with _lib.on_device(y.device):
-            rc = _lib.lib().sr_mul_fwd(_lib.ptr(g), _lib.ptr(y), _lib.ptr(out), y.numel(), _lib.stream_ptr(y.device))
-        _lib.check(rc, "sr_mul_fwd")
+        _lib.call("sr_mul_fwd", y.device, g, y, out, y.numel())
         return out
 
 

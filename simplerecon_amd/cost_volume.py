@@ -15,8 +15,6 @@ grad -- like any torch module: the dot-product `CostVolumeManager` w.r.t. the ma
 (`_DotVolumeFunction`), the metadata-MLP `FeatureVolumeManager` w.r.t. the matching features and the six MLP tensors
 (`_MlpVolumeFunction`).  `manager.differentiable = False` opts out (inputs that require grad are then refused).
 """
-import ctypes as C
-
 import torch
 from torch import Tensor, nn
 
@@ -78,15 +76,11 @@ class _DotVolumeFunction(torch.autograd.Function):
         ws = torch.empty(lib.sr_volume_workspace_bytes(b, k, c, h, w), dtype=torch.uint8, device=dev)
         nscratch = lib.sr_dot_volume_bwd_scratch_bytes(b, k, c, h, w) if need_src else 0
         scratch = torch.empty(nscratch // 4, dtype=torch.float32, device=dev) if need_src else None
-        st = _lib.stream_ptr(dev)
         with _lib.on_device(dev):
             # the forward's workspace may have been reused since: rebuild the geometry records + channels-last sources
-            _lib.check(lib.sr_volume_prepare(_lib.ptr(src), _lib.ptr(Ks), _lib.ptr(T), None, b, k, c, h, w, _lib.ptr(ws),
-                                             ws.numel(), st), "sr_volume_prepare")
-            rc = lib.sr_dot_volume_bwd(_lib.ptr(g), g.stride(0), g.stride(1), g.stride(3), _lib.ptr(cur), _lib.ptr(invK),
-                                       _lib.ptr(planes), *planes.stride(), b, k, c, h, w, d, _lib.ptr(d_cur),
-                                       _lib.ptr(d_src), _lib.ptr(ws), ws.numel(), _lib.ptr(scratch), nscratch, st)
-        _lib.check(rc, "sr_dot_volume_bwd")
+            _lib.call("sr_volume_prepare", dev, src, Ks, T, None, b, k, c, h, w, ws, ws.numel())
+            _lib.call("sr_dot_volume_bwd", dev, g, g.stride(0), g.stride(1), g.stride(3), cur, invK, planes, *planes.stride(),
+                      b, k, c, h, w, d, d_cur, d_src, ws, ws.numel(), scratch, nscratch)
         return None, d_cur, d_src, None, None, None, None
 
 
@@ -128,17 +122,11 @@ class _MlpVolumeFunction(torch.autograd.Function):
             ws = torch.empty(lib.sr_volume_workspace_bytes(b, k, c, h, w), dtype=torch.uint8, device=dev)
             scratch = torch.empty(lib.sr_mlp_volume_bwd_scratch_bytes(b, k, c, h, w, hidden), dtype=torch.uint8,
                                   device=dev)
-            st = _lib.stream_ptr(dev)
             with _lib.on_device(dev):
-                _lib.check(lib.sr_volume_prepare(_lib.ptr(src), _lib.ptr(Ks), _lib.ptr(T), _lib.ptr(Tp), b, k, c, h, w,
-                                                 _lib.ptr(ws), ws.numel(), st), "sr_volume_prepare")
-                rc = lib.sr_mlp_volume_bwd(_lib.ptr(g), g.stride(0), g.stride(1), g.stride(3), _lib.ptr(cur),
-                                           _lib.ptr(invK), _lib.ptr(planes), *planes.stride(),
-                                           *[_lib.ptr(t.detach()) for t in (W1, b1, W2, b2, W3)], C.c_float(0.01), b, k, c,
-                                           h, w, d, hidden, _lib.ptr(d_cur), _lib.ptr(d_src),
-                                           *[_lib.ptr(t) for t in grads], _lib.ptr(ws), ws.numel(), _lib.ptr(scratch),
-                                           scratch.numel(), st)
-            _lib.check(rc, "sr_mlp_volume_bwd")
+                _lib.call("sr_volume_prepare", dev, src, Ks, T, Tp, b, k, c, h, w, ws, ws.numel())
+                _lib.call("sr_mlp_volume_bwd", dev, g, g.stride(0), g.stride(1), g.stride(3), cur, invK, planes,
+                          *planes.stride(), W1, b1, W2, b2, W3, 0.01, b, k, c, h, w, d, hidden, d_cur, d_src, *grads, ws,
+                          ws.numel(), scratch, scratch.numel())
         need = ctx.needs_input_grad
         out = [None, None, d_cur if need[2] else None, d_src if need[3] else None, None, None, None, None, None]
         out += [gr if need[9 + i] else None for i, gr in enumerate(grads)]
@@ -277,12 +265,8 @@ class CostVolumeManager(nn.Module):
         nws = lib.sr_volume_workspace_bytes(b, k, c, h, w)
         ws = self._get_workspace(nws, dev)
         sb, sd, sp = self._volume_strides(vol)
-        with _lib.on_device(dev):
-            rc = lib.sr_dot_volume_fwd(
-                _lib.ptr(cur), _lib.ptr(src), _lib.ptr(Ks), _lib.ptr(T), _lib.ptr(invK), _lib.ptr(planes),
-                *planes.stride(), b, k, c, h, w, self.num_depth_bins, _lib.ptr(vol), sb, sd, sp,
-                _lib.ptr(lowest), C.c_void_p(0), _lib.ptr(ws), ws.numel(), _lib.stream_ptr(dev))
-        _lib.check(rc, "sr_dot_volume_fwd")
+        _lib.call("sr_dot_volume_fwd", dev, cur, src, Ks, T, invK, planes, *planes.stride(), b, k, c, h, w,
+                  self.num_depth_bins, vol, sb, sd, sp, lowest, None, ws, ws.numel())
         return vol, lowest
 
     def _warp(self, src_feats, src_extrinsics, src_Ks, cur_invK, planes, want_pix):
@@ -304,13 +288,9 @@ class CostVolumeManager(nn.Module):
             return world, depths, warped, mask, pix
         lib = _lib.lib()
         ws = self._get_workspace(lib.sr_volume_workspace_bytes(b, k, c, h, w), dev)
-        with _lib.on_device(dev):
-            rc = lib.sr_warp_features_fwd(
-                _lib.ptr(src_feats.contiguous()), _lib.ptr(src_Ks.contiguous()), _lib.ptr(src_extrinsics.contiguous()),
-                _lib.ptr(cur_invK.contiguous()), _lib.ptr(planes), *planes.stride(), b, k, c, h, w, dp,
-                _lib.ptr(world), _lib.ptr(depths), _lib.ptr(warped), _lib.ptr(mask), _lib.ptr(pix), _lib.ptr(ws),
-                ws.numel(), _lib.stream_ptr(dev))
-        _lib.check(rc, "sr_warp_features_fwd")
+        _lib.call("sr_warp_features_fwd", dev, src_feats.contiguous(), src_Ks.contiguous(), src_extrinsics.contiguous(),
+                  cur_invK.contiguous(), planes, *planes.stride(), b, k, c, h, w, dp, world, depths, warped, mask, pix, ws,
+                  ws.numel())
         return world, depths, warped, mask, pix
 
     def warp_features(self, src_feats, src_extrinsics, src_Ks, cur_invK, depth_plane_b1hw, batch_size,
@@ -436,7 +416,7 @@ class FeatureVolumeManager(CostVolumeManager):
                 dev, record, lib.sr_mlp_volume_fwd,
                 _lib.ptr(cur), _lib.ptr(src), _lib.ptr(Ks), _lib.ptr(T), _lib.ptr(Tp), _lib.ptr(invK),
                 _lib.ptr(planes), *planes.stride(), *[_lib.ptr(t) for t in params], hidden,
-                C.c_float(0.01),  # nn.LeakyReLU default slope (reference networks.py:139)
+                0.01,  # nn.LeakyReLU default slope (reference networks.py:139)
                 b, k, c, h, w, d, _lib.ptr(vol), sb, sd, sp, _lib.ptr(lowest),
                 _lib.ptr(mask), int(reserve_cus), _lib.ptr(ws), ws.numel(), _lib.stream_ptr(dev))
         _lib.check(rc, "sr_mlp_volume_fwd")

@@ -6,8 +6,6 @@ returns a small device vector (the loss and the counts / means its backward need
 adds the final scalars.  Nothing here synchronises the host.  Gradients flow to the predictions only: gt depth,
 masks, poses and intrinsics are data, and asking for their gradient raises.  Everything is fp32; under autocast the
 losses still run in fp32 (the reference runs their matmuls in fp16 there)."""
-import ctypes as C
-
 import torch
 from torch import nn
 
@@ -52,10 +50,6 @@ def _ws(nbytes, device, what):
     return torch.empty(int(nbytes), dtype=torch.uint8, device=device)
 
 
-def _call(name, *args):
-    _lib.check(getattr(_lib.lib(), name)(*args), name)
-
-
 def _bhw(t):
     """[B,1,h,w] or [B,h,w] -> (B, h, w)."""
     if t.dim() == 4 and t.shape[1] != 1:
@@ -71,9 +65,7 @@ class _Normals(torch.autograd.Function):
         dev = depth.device
         ws = _ws(_lib.lib().sr_normals_workspace_bytes(B, h, w), dev, "normals")
         out = torch.empty((B, 3, h, w), dtype=torch.float32, device=dev)
-        with _lib.on_device(dev):
-            _call("sr_normals_fwd", _lib.ptr(depth), _lib.ptr(invK), B, h, w, _lib.ptr(out), _lib.ptr(ws), ws.numel(),
-                  _lib.stream_ptr(dev))
+        _lib.call("sr_normals_fwd", dev, depth, invK, B, h, w, out, ws, ws.numel())
         ctx.save_for_backward(depth, invK)
         return out
 
@@ -85,9 +77,7 @@ class _Normals(torch.autograd.Function):
         g = g.contiguous()
         ws = _ws(_lib.lib().sr_normals_workspace_bytes(B, h, w), dev, "normals")
         gd = torch.empty_like(depth)
-        with _lib.on_device(dev):
-            _call("sr_normals_bwd", _lib.ptr(g), _lib.ptr(depth), _lib.ptr(invK), B, h, w, _lib.ptr(gd), _lib.ptr(ws),
-                  ws.numel(), _lib.stream_ptr(dev))
+        _lib.call("sr_normals_bwd", dev, g, depth, invK, B, h, w, gd, ws, ws.numel())
         return gd, None
 
 
@@ -107,9 +97,7 @@ class _NormalsLoss(torch.autograd.Function):
         dev = npred.device
         ws = _ws(_lib.lib().sr_normals_loss_workspace_bytes(B, h, w), dev, "normals loss")
         out = torch.empty(2, dtype=torch.float32, device=dev)
-        with _lib.on_device(dev):
-            _call("sr_normals_loss_fwd", _lib.ptr(ngt), _lib.ptr(npred), B, h, w, _lib.ptr(out), _lib.ptr(ws),
-                  ws.numel(), _lib.stream_ptr(dev))
+        _lib.call("sr_normals_loss_fwd", dev, ngt, npred, B, h, w, out, ws, ws.numel())
         ctx.save_for_backward(ngt, npred, out)
         return out
 
@@ -119,9 +107,7 @@ class _NormalsLoss(torch.autograd.Function):
         B, _, h, w = npred.shape
         g = g.contiguous()
         gp = torch.empty_like(npred)
-        with _lib.on_device(npred.device):
-            _call("sr_normals_loss_bwd", _lib.ptr(g), _lib.ptr(stats), _lib.ptr(ngt), _lib.ptr(npred), B, h, w,
-                  _lib.ptr(gp), _lib.stream_ptr(npred.device))
+        _lib.call("sr_normals_loss_bwd", npred.device, g, stats, ngt, npred, B, h, w, gp)
         return None, gp
 
 
@@ -144,9 +130,7 @@ class _GradLoss(torch.autograd.Function):
         dev = pred.device
         ws = _ws(_lib.lib().sr_grad_loss_workspace_bytes(B, h, w), dev, "gradient loss")
         out = torch.empty(5, dtype=torch.float32, device=dev)
-        with _lib.on_device(dev):
-            _call("sr_grad_loss_fwd", _lib.ptr(gt), _lib.ptr(pred), B, h, w, _lib.ptr(out), _lib.ptr(ws), ws.numel(),
-                  _lib.stream_ptr(dev))
+        _lib.call("sr_grad_loss_fwd", dev, gt, pred, B, h, w, out, ws, ws.numel())
         ctx.save_for_backward(gt, pred, out)
         ctx.ws = ws   # the backward reads the pyramid the forward left here
         return out
@@ -158,9 +142,7 @@ class _GradLoss(torch.autograd.Function):
         g = g.contiguous()
         gp = torch.empty_like(pred)
         ws = ctx.ws
-        with _lib.on_device(pred.device):
-            _call("sr_grad_loss_bwd", _lib.ptr(g), _lib.ptr(stats), _lib.ptr(gt), _lib.ptr(pred), B, h, w,
-                  _lib.ptr(gp), _lib.ptr(ws), ws.numel(), _lib.stream_ptr(pred.device))
+        _lib.call("sr_grad_loss_bwd", pred.device, g, stats, gt, pred, B, h, w, gp, ws, ws.numel())
         return None, gp
 
 
@@ -210,10 +192,8 @@ class _MVLoss(torch.autograd.Function):
         dev = pred.device
         ws = _ws(_lib.lib().sr_mv_loss_workspace_bytes(B, K, h, w), dev, "multi-view loss")
         out = torch.empty(1 + 2 * K, dtype=torch.float32, device=dev)
-        with _lib.on_device(dev):
-            _call("sr_mv_loss_fwd", _lib.ptr(pred), _lib.ptr(gt), _lib.ptr(src), _lib.ptr(invK), _lib.ptr(srcK),
-                  _lib.ptr(wTc), _lib.ptr(cTw), B, K, h, w, C.c_float(PROJECT_EPS), _lib.ptr(out), None, None,
-                  _lib.ptr(ws), ws.numel(), _lib.stream_ptr(dev))
+        _lib.call("sr_mv_loss_fwd", dev, pred, gt, src, invK, srcK, wTc, cTw, B, K, h, w, PROJECT_EPS, out, None, None, ws,
+                  ws.numel())
         ctx.save_for_backward(pred, gt, src, invK, srcK, wTc, cTw, out)
         ctx.K = K
         return out
@@ -224,10 +204,8 @@ class _MVLoss(torch.autograd.Function):
         B, h, w = _bhw(pred)
         g = g.contiguous()
         gp = torch.empty_like(pred)
-        with _lib.on_device(pred.device):
-            _call("sr_mv_loss_bwd", _lib.ptr(g), _lib.ptr(stats), _lib.ptr(pred), _lib.ptr(gt), _lib.ptr(src),
-                  _lib.ptr(invK), _lib.ptr(srcK), _lib.ptr(wTc), _lib.ptr(cTw), B, ctx.K, h, w, C.c_float(PROJECT_EPS),
-                  _lib.ptr(gp), _lib.stream_ptr(pred.device))
+        _lib.call("sr_mv_loss_bwd", pred.device, g, stats, pred, gt, src, invK, srcK, wTc, cTw, B, ctx.K, h, w, PROJECT_EPS,
+                  gp)
         return gp, None, None, None, None, None, None, None
 
 
@@ -249,10 +227,8 @@ class MVDepthLoss(nn.Module):
         out = torch.empty(1 + 2 * K, dtype=torch.float32, device=dev)
         valid = torch.empty((B, K, h, w), dtype=torch.uint8, device=dev)
         sampled = torch.empty((B, K, h, w), dtype=torch.float32, device=dev)
-        with _lib.on_device(dev):
-            _call("sr_mv_loss_fwd", _lib.ptr(gt), _lib.ptr(gt), _lib.ptr(src), _lib.ptr(invK), _lib.ptr(srcK),
-                  _lib.ptr(wTc), _lib.ptr(cTw), B, K, h, w, C.c_float(PROJECT_EPS), _lib.ptr(out), _lib.ptr(valid),
-                  _lib.ptr(sampled), _lib.ptr(ws), ws.numel(), _lib.stream_ptr(dev))
+        _lib.call("sr_mv_loss_fwd", dev, gt, gt, src, invK, srcK, wTc, cTw, B, K, h, w, PROJECT_EPS, out, valid, sampled, ws,
+                  ws.numel())
         if K == 1:
             return valid.view(torch.bool), sampled
         return valid.view(torch.bool).view(B, K, 1, h, w), sampled.view(B, K, 1, h, w)
@@ -292,12 +268,11 @@ class _DepthTerms(torch.autograd.Function):
         logs = [l0, l1, l2, l3]
         dims = []
         for t in logs[1:]:
-            dims += [_lib.ptr(t), t.shape[-2] if t is not None else 0, t.shape[-1] if t is not None else 0]
+            dims += [t, t.shape[-2] if t is not None else 0, t.shape[-1] if t is not None else 0]
         ws = _ws(_lib.lib().sr_depth_terms_workspace_bytes(B, h, w), dev, "depth terms")
         out = torch.empty(8, dtype=torch.float32, device=dev)
-        with _lib.on_device(dev):
-            _call("sr_depth_terms_fwd", _lib.ptr(gt), _lib.ptr(mask), _lib.ptr(pred), _lib.ptr(l0), *dims, B, h, w,
-                  C.c_float(si_lambda), int(gt_is_log), _lib.ptr(out), _lib.ptr(ws), ws.numel(), _lib.stream_ptr(dev))
+        _lib.call("sr_depth_terms_fwd", dev, gt, mask, pred, l0, *dims, B, h, w, si_lambda, int(gt_is_log), out, ws,
+                  ws.numel())
         ctx.save_for_backward(gt, mask, pred, out, *[t if t is not None else torch.empty(0) for t in logs])
         ctx.present = [t is not None for t in logs]
         ctx.si_lambda, ctx.gt_is_log = si_lambda, gt_is_log
@@ -314,11 +289,9 @@ class _DepthTerms(torch.autograd.Function):
         glogs = [torch.empty_like(t) if t is not None else None for t in logs]
         dims = []
         for t in logs[1:]:
-            dims += [_lib.ptr(t), t.shape[-2] if t is not None else 0, t.shape[-1] if t is not None else 0]
-        with _lib.on_device(dev):
-            _call("sr_depth_terms_bwd", _lib.ptr(g), _lib.ptr(stats), _lib.ptr(gt), _lib.ptr(mask), _lib.ptr(pred),
-                  _lib.ptr(logs[0]), *dims, B, h, w, C.c_float(ctx.si_lambda), int(ctx.gt_is_log), _lib.ptr(gpred),
-                  *[_lib.ptr(t) for t in glogs], _lib.stream_ptr(dev))
+            dims += [t, t.shape[-2] if t is not None else 0, t.shape[-1] if t is not None else 0]
+        _lib.call("sr_depth_terms_bwd", dev, g, stats, gt, mask, pred, logs[0], *dims, B, h, w, ctx.si_lambda,
+                  int(ctx.gt_is_log), gpred, *glogs)
         return (None, None, gpred, None, None, *glogs)
 
 

@@ -54,30 +54,27 @@ class _TargetGrid:
         n = int(target.shape[0])
         b = (C.c_double * 6)(*[float(x) for x in box])
         cell, dims, entries = C.c_double(), (C.c_int * 3)(), C.c_int64()
-        _lib.check(lib.sr_nn_grid_plan(n, C.addressof(b), int(max_cells), C.addressof(cell), C.addressof(dims),
-                                       C.addressof(entries)), "sr_nn_grid_plan")
+        rc = lib.sr_nn_grid_plan(n, C.addressof(b), int(max_cells), C.addressof(cell), C.addressof(dims), C.addressof(entries))
+        if rc != 0:   # (a host-side query: no launch, no stream)
+            raise _lib.HipLibraryError(f"sr_nn_grid_plan failed: error {rc}")
         self.n = n
         self.origin = [float(x) for x in box[:3]]
         self.cell = cell.value
         self.dims = [int(d) for d in dims]
         self.entries = int(entries.value)
         dev = target.device
-        self.stream = _lib.stream_ptr(dev)
         keys = self.keys(target)
         skeys, order = torch.sort(keys, stable=True)
         self.sorted = torch.empty((n, 4), dtype=torch.float32, device=dev)
         self.start = torch.empty(self.entries, dtype=torch.int32, device=dev)
-        _lib.check(lib.sr_nn_build(_lib.ptr(target), n, _lib.ptr(skeys), _lib.ptr(order), self.entries,
-                                   _lib.ptr(self.sorted), _lib.ptr(self.start), self.stream), "sr_nn_build")
+        _lib.call("sr_nn_build", dev, target, n, skeys, order, self.entries, self.sorted, self.start)
 
     def _grid_args(self):
-        d = C.c_double
-        return [d(self.origin[0]), d(self.origin[1]), d(self.origin[2]), d(self.cell)] + self.dims
+        return [*self.origin, self.cell, *self.dims]
 
     def keys(self, pts):
         keys = torch.empty(int(pts.shape[0]), dtype=torch.int32, device=pts.device)
-        _lib.check(_lib.lib().sr_nn_keys(_lib.ptr(pts), int(pts.shape[0]), *self._grid_args(), _lib.ptr(keys),
-                                         self.stream), "sr_nn_keys")
+        _lib.call("sr_nn_keys", pts.device, pts, int(pts.shape[0]), *self._grid_args(), keys)
         return keys
 
     def query(self, q, want_d2=False, want_dist=True, want_index=False):
@@ -87,9 +84,8 @@ class _TargetGrid:
         idx = torch.empty(M, dtype=torch.int32, device=dev) if want_index else None
         if M:
             _, order = torch.sort(self.keys(q))   # neighbouring queries in neighbouring lanes; results do not depend on it
-            _lib.check(_lib.lib().sr_nn_query(_lib.ptr(q), M, _lib.ptr(order), _lib.ptr(self.sorted), self.n,
-                                              _lib.ptr(self.start), self.entries, *self._grid_args(), _lib.ptr(d2),
-                                              _lib.ptr(dist), _lib.ptr(idx), self.stream), "sr_nn_query")
+            _lib.call("sr_nn_query", dev, q, M, order, self.sorted, self.n, self.start, self.entries, *self._grid_args(), d2,
+                      dist, idx)
         return d2, dist, idx
 
 
@@ -101,7 +97,7 @@ def _nearest(query, target, want_d2=False, want_dist=True, want_index=False, max
         raise ValueError("nearest neighbours need at least one target point")
     if q.device != t.device:
         raise ValueError(f"query on {q.device}, target on {t.device}")
-    with torch.cuda.device(t.device):
+    with _lib.on_device(t.device):
         if target_box is None:
             boxes = _boxes(t, q) if q.shape[0] else _boxes(t)
             target_box = boxes[0]
@@ -142,13 +138,11 @@ def _sample(mesh, n_points, seed=0, device=None):
     if seed < 0 or seed >= 2 ** 64:
         raise ValueError(f"seed must be in [0, 2^64), got {seed}")
     lib = _lib.lib()
-    with torch.cuda.device(dev):
-        stream = _lib.stream_ptr(dev)
+    with _lib.on_device(dev):
         nbytes = lib.sr_sample_surface_workspace_bytes(F)
         scratch = torch.empty(max(nbytes // 8, 1), dtype=torch.float64, device=dev)
         cdf = torch.empty(F, dtype=torch.float64, device=dev)
-        _lib.check(lib.sr_sample_surface_cdf(_lib.ptr(v), V, _lib.ptr(f), F, _lib.ptr(cdf), _lib.ptr(scratch), nbytes,
-                                             stream), "sr_sample_surface_cdf")
+        _lib.call("sr_sample_surface_cdf", dev, v, V, f, F, cdf, scratch, nbytes)
         lo, hi, total = torch.stack([f.min().double(), f.max().double(), cdf[-1]]).cpu().tolist()   # one sync
         if lo < 0 or hi >= V:
             raise ValueError(f"sample_surface: face indices outside [0, {V}) (min {int(lo)}, max {int(hi)})")
@@ -156,8 +150,7 @@ def _sample(mesh, n_points, seed=0, device=None):
             raise ValueError(f"sample_surface: the mesh's total area is {total} (zero or non-finite)")
         pts = torch.empty((n, 3), dtype=torch.float32, device=dev)
         face = torch.empty(n, dtype=torch.int32, device=dev)
-        _lib.check(lib.sr_sample_surface(_lib.ptr(v), V, _lib.ptr(f), F, _lib.ptr(cdf), n, C.c_uint64(int(seed)),
-                                         _lib.ptr(pts), _lib.ptr(face), stream), "sr_sample_surface")
+        _lib.call("sr_sample_surface", dev, v, V, f, F, cdf, n, int(seed), pts, face)
     return pts, face
 
 
@@ -229,14 +222,13 @@ def mesh_metrics(pred, gt, threshold=0.05, sampling="vertices", down_sample=0.02
     if n == 0:
         raise ValueError("mesh_metrics: the ground truth has no points")
     lib = _lib.lib()
-    with torch.cuda.device(device):
+    with _lib.on_device(device):
         boxes = _boxes(g, p) if m else _boxes(g)
         _, d_pg, _ = _TargetGrid(g, boxes[0]).query(p)
         d_gp = _TargetGrid(p, boxes[1]).query(g)[1] if m else None
         nbytes = lib.sr_mesh_metrics_workspace_bytes(m, n)
         scratch = torch.empty(max(nbytes // 8, 1), dtype=torch.float64, device=device)
         out = torch.empty(8, dtype=torch.float64, device=device)
-        _lib.check(lib.sr_mesh_metrics(_lib.ptr(d_pg), m, _lib.ptr(d_gp), n, C.c_float(thr), _lib.ptr(out),
-                                       _lib.ptr(scratch), nbytes, _lib.stream_ptr(device)), "sr_mesh_metrics")
+        _lib.call("sr_mesh_metrics", device, d_pg, m, d_gp, n, thr, out, scratch, nbytes)
         vals = out.cpu().tolist()
     return {k: vals[i] for i, k in enumerate(METRIC_KEYS)}

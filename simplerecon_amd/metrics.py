@@ -62,12 +62,8 @@ def _run(gt, pred, mask, min_depth, B, H, W, h, w, resample, mult_a, pooled):
     ws = torch.empty(int(nbytes), dtype=torch.uint8, device=dev)
     buf = torch.empty(B * 13 + (12 if pooled else 0), dtype=torch.float32, device=dev)
     block, counts = split_block(buf, B)
-    with _lib.on_device(dev):
-        rc = _lib.lib().sr_depth_metrics(_lib.ptr(gt), _lib.ptr(pred), _lib.ptr(mask) if mask is not None else None,
-                                         float(min_depth), B, H, W, h, w, resample, 1 if mult_a else 0,
-                                         _lib.ptr(block), _lib.ptr(counts), _lib.ptr(buf[B * 13:]) if pooled else None,
-                                         _lib.ptr(ws), ws.numel(), _lib.stream_ptr(dev))
-    _lib.check(rc, "sr_depth_metrics")
+    _lib.call("sr_depth_metrics", dev, gt, pred, mask, float(min_depth), B, H, W, h, w,
+              resample, 1 if mult_a else 0, block, counts, buf[B * 13:] if pooled else None, ws, ws.numel())
     return buf
 
 
@@ -241,8 +237,5 @@ def _gather(pred_b1hw, H, W):
     pred = _f32("pred_b1hw", pred_b1hw)
     B, h, w = _bhw("pred_b1hw", pred)
     out = torch.empty((B, H, W), dtype=torch.float32, device=pred.device)
-    with _lib.on_device(pred.device):
-        rc = _lib.lib().sr_depth_metrics_gather(_lib.ptr(pred), B, H, W, h, w, RESAMPLE_NEAREST, _lib.ptr(out),
-                                                _lib.stream_ptr(pred.device))
-    _lib.check(rc, "sr_depth_metrics_gather")
+    _lib.call("sr_depth_metrics_gather", pred.device, pred, B, H, W, h, w, RESAMPLE_NEAREST, out)
     return out

@@ -65,12 +65,9 @@ _PACK_DIMS = {"conv": 3, "wino": 2, "wino4": 2, "stem": 1, "conv3x3_c16": 2}
 
 def _pack(kind, w):
     """The library's `kind` packing of the contiguous fp32 weight `w` ([Co, Ci, k, k]) into a new tensor (uncached)."""
-    lib = _lib.lib()
     dims = w.shape[:_PACK_DIMS[kind]]
-    packed = torch.empty(getattr(lib, f"sr_{kind}_packed_weight_floats")(*dims), dtype=torch.float32, device=w.device)
-    with _lib.on_device(w.device):
-        rc = getattr(lib, f"sr_{kind}_pack_weights")(_lib.ptr(w), *dims, _lib.ptr(packed), _lib.stream_ptr(w.device))
-    _lib.check(rc, f"sr_{kind}_pack_weights")
+    packed = torch.empty(getattr(_lib.lib(), f"sr_{kind}_packed_weight_floats")(*dims), dtype=torch.float32, device=w.device)
+    _lib.call(f"sr_{kind}_pack_weights", w.device, w, *dims, packed)
     return packed
 
 
@@ -226,12 +223,8 @@ def linear(x, lin: nn.Linear, leaky=None):
         return out.view(*x.shape[:-1], cout)
     wp = _cached(lin, "linear", _state_key(lin, None), _pack_linear, lin)
     bias = lin.bias.detach() if lin.bias is not None else None
-    lib = _lib.lib()
-    with _lib.on_device(x.device):
-        rc = lib.sr_conv2d_nhwc_fwd(_lib.ptr(x2), m * cin, cin, _lib.ptr(wp), _lib.ptr(bias), None, 0, 0,
-                                    _lib.ptr(out), m * cout, cout, 1, 1, m, cin, cout, 1, 1,
-                                    C.c_float(-1.0 if leaky is None else float(leaky)), _lib.stream_ptr(x.device))
-    _lib.check(rc, "sr_conv2d_nhwc_fwd (linear)")
+    _lib.call("sr_conv2d_nhwc_fwd", x.device, x2, m * cin, cin, wp, bias, None, 0, 0, out, m * cout, cout, 1, 1, m, cin, cout,
+              1, 1, -1.0 if leaky is None else float(leaky))
     return out.view(*x.shape[:-1], cout)
 
 
@@ -337,12 +330,12 @@ def conv2d(x, conv: nn.Conv2d, residual=None, leaky=None, out=None, bn=None, act
         _lib.require_device_f32("gate", gate)
         if k != 1 or s != 1 or tuple(gate.shape) != (b, ci) or not gate.is_contiguous():
             raise ValueError(f"`gate` needs a 1x1 / stride-1 conv and a contiguous [{b}, {ci}] tensor")
-    slope = C.c_float(_act_code(leaky, act))
+    slope = _act_code(leaky, act)
     strides = (isb, isp, osb, osp, rsb, rsp)
     if k == 1 and s == 1 and not padded and not replicate and (USE_PW_1X1 or gate is not None) and ci % 4 == 0 \
             and _aligned16(x, isb, isp):
         shape = (b, ci, h, w, co, k, s, ho, wo, residual is not None)
-        if _conv_pointwise(lib, x, conv, bn, residual, out, gate, strides, shape, slope) == 0:
+        if _conv_pointwise(lib, x, *packed_weight(conv, bn), residual, out, gate, strides, shape, slope) == 0:
             return out
         # SR_ERR_UNSUPPORTED (a per-image byte range past 2^31): the implicit-GEMM kernel below, whose addressing is 64-bit
     if gate is not None:
@@ -360,14 +353,15 @@ def conv2d(x, conv: nn.Conv2d, residual=None, leaky=None, out=None, bn=None, act
     shape = (b, ci, h, w, co, k, s, ho, wo, residual is not None)
     w4_form = _shape_query(lib, "sr_conv_prefers_wino4", b, h, w, ci, co, WINO4_MODE, dev=x.device.index) \
         if (use_wino and WINO4_MODE and not split) else 0   # 0: F(2x2); 1 / 3: the kernel form the rule picks
-    if w4_form and _conv_wino4(lib, x, conv, bn, residual, out, strides, shape, slope, WINO4_VARIANT or w4_form) == 0:
+    if w4_form and _conv_wino4(lib, x, *packed_wino4_weight(conv, bn), residual, out, strides, shape, slope,
+                               WINO4_VARIANT or w4_form) == 0:
         return out
     if use_wino:
         # pack and launch must see ONE split mode.  A plain acquire / release -- a context manager object per call
         # costs a microsecond on a launch path that is host-bound at batch 1
         _lib.SPLIT_GUARD.acquire()
         try:
-            if _conv_wino(lib, x, conv, bn, residual, out, strides, shape, slope) == 0:
+            if _conv_wino(lib, x, *packed_wino_weight(conv, bn), residual, out, strides, shape, slope) == 0:
                 return out
         finally:
             _lib.SPLIT_GUARD.release()
@@ -375,12 +369,10 @@ def conv2d(x, conv: nn.Conv2d, residual=None, leaky=None, out=None, bn=None, act
         # offsets): the implicit-GEMM kernel serves the shape with 64-bit addressing, as it did before r04
         wp, bias = packed_weight(conv, bn)
         isb, isp, osb, osp, rsb, rsp = strides
-        with _lib.on_device(x.device):
-            rc = lib.sr_conv2d_nhwc_fwd(_lib.ptr(x), isb, isp, _lib.ptr(wp), _lib.ptr(bias), _lib.ptr(residual), rsb, rsp,
-                                        _lib.ptr(out), osb, osp, b, h, w, ci, co, k, s, slope, _lib.stream_ptr(x.device))
-        _lib.check(rc, "sr_conv2d_nhwc_fwd")
+        _lib.call("sr_conv2d_nhwc_fwd", x.device, x, isb, isp, wp, bias, residual, rsb, rsp, out, osb, osp, b, h, w, ci, co,
+                  k, s, slope)
         return out
-    _conv_direct(lib, x, conv, bn, residual, out, strides, shape, slope, pads if padded else None, replicate)
+    _conv_direct(lib, x, *packed_weight(conv, bn), residual, out, strides, shape, slope, pads if padded else None, replicate)
     return out
 
 
@@ -424,11 +416,10 @@ def _launch(x, shape, entry, fallback, describe, fn, *args):
     return rc
 
 
-def _conv_pointwise(lib, x, conv, bn, residual, out, gate, strides, shape, slope):
+def _conv_pointwise(lib, x, wp, bias, residual, out, gate, strides, shape, slope):
     """1x1 / stride-1: the pointwise GEMM kernels of csrc/sr_pw.hip (the LDS-tiled one on large batch-dense maps)."""
     isb, isp, osb, osp, rsb, rsp = strides
     b, ci, h, w, co = shape[:5]
-    wp, bias = packed_weight(conv, bn)
     m = b * h * w
     dense = b == 1 or (isb == h * w * isp and osb == h * w * osp and (residual is None or rsb == h * w * rsp))
     gflag = "true" if gate is not None else "false"
@@ -463,12 +454,11 @@ def _conv_pointwise(lib, x, conv, bn, residual, out, gate, strides, shape, slope
                    h * w, ci, co, slope, _lib.stream_ptr(x.device))
 
 
-def _conv_wino4(lib, x, conv, bn, residual, out, strides, shape, slope, variant):
+def _conv_wino4(lib, x, wp, bias, residual, out, strides, shape, slope, variant):
     """3x3 / stride 1: F(4x4, 3x3) Winograd (csrc/sr_wino4.hip) in kernel form `variant`; SR_ERR_UNSUPPORTED without
     launching when a tensor or the bias is not 16-byte aligned."""
     isb, isp, osb, osp, rsb, rsp = strides
     b, ci, h, w, co = shape[:5]
-    wp, bias = packed_wino4_weight(conv, bn)
     if not (_aligned16(x, isb, isp) and _aligned16(out, osb, osp) and _aligned16(residual, rsb, rsp)
             and (bias is None or bias.data_ptr() % 16 == 0)):
         return _lib.ERR_UNSUPPORTED
@@ -482,35 +472,41 @@ def _conv_wino4(lib, x, conv, bn, residual, out, strides, shape, slope, variant)
                    co, slope, variant, _lib.stream_ptr(x.device))
 
 
-def _conv_wino(lib, x, conv, bn, residual, out, strides, shape, slope):
-    """3x3 / stride 1: F(2x2, 3x3) Winograd (csrc/sr_wino.hip, or the fenced split-precision variant of SR_WINO_SPLIT)."""
+def _conv_wino(lib, x, wp, bias, residual, out, strides, shape, slope, workspace=True, fallback=True):
+    """3x3 / stride 1: F(2x2, 3x3) Winograd (csrc/sr_wino.hip, or the fenced split-precision variant of SR_WINO_SPLIT) on the
+    Winograd-packed weight `wp`.  workspace=False: no split-K scratch is handed over, so the launcher never splits K (the
+    training path); fallback=False: SR_ERR_UNSUPPORTED raises like any other error (no direct-kernel launch stands behind)."""
     isb, isp, osb, osp, rsb, rsp = strides
     b, ci, h, w, co = shape[:5]
     split = wino_split_mode()
-    wp, bias = packed_wino_weight(conv, bn)
-    nbytes = _shape_query(lib, "sr_wino_splitk_workspace_bytes", b, h, w, ci, co, dev=x.device.index)   # 0 unless it splits K
+    # 0 unless it splits K
+    nbytes = _shape_query(lib, "sr_wino_splitk_workspace_bytes", b, h, w, ci, co, dev=x.device.index) if workspace else 0
     ws = _workspace(x.device, "wino_splitk", nbytes) if nbytes else None
 
     def describe():
         vin = bool(_aligned16(x, isb, isp) and ci % 4 == 0)
         vout = vin and co % 4 == 0 and _aligned16(out, osb, osp) and _aligned16(residual, rsb, rsp) and \
             (bias is None or bias.data_ptr() % 16 == 0)
-        name = lib.sr_wino_kernel_name(b, h, w, ci, co, int(vin), int(vout)).decode()
+        # (without a workspace the launcher's plan is the one that may not split K: the name is asked with aligned_out = 0,
+        # which answers for that plan, and the vector epilogue's template argument is put back)
+        name = lib.sr_wino_kernel_name(b, h, w, ci, co, int(vin), int(vout and workspace)).decode()
+        if vout and not workspace:
+            name = name.replace(", true, false>", ", true, true>")
         if split:   # (the fenced variant: sr_wino_split_kernel<NT, FMT>)
             name = name.replace("sr_wino_kernel<", "sr_wino_split_kernel<").replace(
                 ", true, true>", f", {1 if split == 'bf16' else 2}>")
         regions = ((h + 7) // 8) * ((w + 15) // 16)   # multiplies issued: 16 per 2x2 tile and (ci, co) pair, padded
         return name, 2.0 * b * regions * 32 * 16 * ((ci + 15) // 16 * 16) * ((co + 31) // 32 * 32)
-    return _launch(x, shape, "sr_conv3x3_wino_nhwc_fwd", not split, describe, lib.sr_conv3x3_wino_splitk_nhwc_fwd,
+    return _launch(x, shape, "sr_conv3x3_wino_nhwc_fwd", fallback and not split, describe, lib.sr_conv3x3_wino_splitk_nhwc_fwd,
                    _lib.ptr(x), isb, isp, _lib.ptr(wp), _lib.ptr(bias), _lib.ptr(residual), rsb, rsp, _lib.ptr(out), osb, osp,
                    b, h, w, ci, co, slope, _lib.ptr(ws), nbytes, _lib.stream_ptr(x.device))
 
 
-def _conv_direct(lib, x, conv, bn, residual, out, strides, shape, slope, pads, replicate):
-    """Implicit-GEMM direct convolution (csrc/sr_conv.hip): explicit zero `pads`, replicate or symmetric zero padding."""
+def _conv_direct(lib, x, wp, bias, residual, out, strides, shape, slope, pads, replicate, workspace=True):
+    """Implicit-GEMM direct convolution (csrc/sr_conv.hip) on the packed weight `wp`: explicit zero `pads`, replicate or
+    symmetric zero padding.  workspace=False: no split-K scratch, so the launcher never splits K (the training path)."""
     isb, isp, osb, osp, rsb, rsp = strides
     b, ci, h, w, co, k, s = shape[:7]
-    wp, bias = packed_weight(conv, bn)
     args = (_lib.ptr(x), isb, isp, _lib.ptr(wp), _lib.ptr(bias), _lib.ptr(residual), rsb, rsp, _lib.ptr(out), osb, osp,
             b, h, w, ci, co, k, s)
     describe = lambda: (lib.sr_conv_kernel_name(b, h, w, ci, co, k, s, int(_aligned16(x, isb, isp))).decode(), None)
@@ -520,7 +516,8 @@ def _conv_direct(lib, x, conv, bn, residual, out, strides, shape, slope, pads, r
         return launch(lib.sr_conv2d_padded_nhwc_fwd, *pads, slope)
     if replicate:
         return launch(lib.sr_conv2d_replicate_nhwc_fwd, slope)
-    nbytes = _shape_query(lib, "sr_conv_splitk_workspace_bytes", b, h, w, ci, co, k, s, dev=x.device.index)   # 0 unless it may split K
+    # 0 unless it may split K
+    nbytes = _shape_query(lib, "sr_conv_splitk_workspace_bytes", b, h, w, ci, co, k, s, dev=x.device.index) if workspace else 0
     ws = _workspace(x.device, "conv_splitk", nbytes) if nbytes else None
     return launch(lib.sr_conv2d_splitk_nhwc_fwd, slope, _lib.ptr(ws), nbytes)
 
@@ -549,10 +546,7 @@ def upsample2x(x, out=None):
         return out
     isb, isp = _strides(x)
     osb, osp = _strides(out)
-    with _lib.on_device(x.device):
-        rc = _lib.lib().sr_upsample2x_nhwc_fwd(_lib.ptr(x), isb, isp, _lib.ptr(out), osb, osp, b, h, w, c,
-                                               _lib.stream_ptr(x.device))
-    _lib.check(rc, "sr_upsample2x_nhwc_fwd")
+    _lib.call("sr_upsample2x_nhwc_fwd", x.device, x, isb, isp, out, osb, osp, b, h, w, c)
     return out
 
 
@@ -562,9 +556,7 @@ def exp(x):
     if not (x.is_contiguous() or x.is_contiguous(memory_format=torch.channels_last)):
         x = x.contiguous()
     out = torch.empty_like(x)
-    with _lib.on_device(x.device):
-        rc = _lib.lib().sr_exp_fwd(_lib.ptr(x), _lib.ptr(out), x.numel(), _lib.stream_ptr(x.device))
-    _lib.check(rc, "sr_exp_fwd")
+    _lib.call("sr_exp_fwd", x.device, x, out, x.numel())
     return out
 
 
@@ -635,7 +627,7 @@ def stem7x7(image, conv: nn.Conv2d, bn=None, leaky=0.0, out=None):
     record = lambda: ("sr_stem_kernel", 2.0 * b * ho * wo * 64 * 147, (b, 3, h, w, 64, 7, 2),
                       2.0 * b * ((ho + 15) // 16) * ((wo + 15) // 16) * 256 * 64 * 148)
     rc = _timed(image.device, record, _lib.lib().sr_stem7x7_fwd, _lib.ptr(image), sb, sc, sy, sx, _lib.ptr(wp),
-                _lib.ptr(scale), _lib.ptr(shift), C.c_float(-1.0 if leaky is None else float(leaky)), _lib.ptr(out), osb,
+                _lib.ptr(scale), _lib.ptr(shift), -1.0 if leaky is None else float(leaky), _lib.ptr(out), osb,
                 osp, b, h, w, 64, _lib.stream_ptr(image.device))
     _lib.check(rc, "sr_stem7x7_fwd")
     return out
@@ -657,10 +649,7 @@ def maxblurpool(x, out=None):
         return out
     isb, isp = _strides(x)
     osb, osp = _strides(out)
-    with _lib.on_device(x.device):
-        rc = _lib.lib().sr_maxblurpool_nhwc_fwd(_lib.ptr(x), isb, isp, _lib.ptr(out), osb, osp, b, h, w, c,
-                                                _lib.stream_ptr(x.device))
-    _lib.check(rc, "sr_maxblurpool_nhwc_fwd")
+    _lib.call("sr_maxblurpool_nhwc_fwd", x.device, x, isb, isp, out, osb, osp, b, h, w, c)
     return out
 
 
@@ -676,11 +665,8 @@ def instance_norm(x, eps=1e-5, leaky=None, inplace=False):
     ws = _workspace(x.device, "inorm", nbytes)
     isb, isp = _strides(x)
     osb, osp = _strides(out)
-    with _lib.on_device(x.device):
-        rc = lib.sr_instance_norm_nhwc_fwd(_lib.ptr(x), isb, isp, _lib.ptr(out), osb, osp, b, h, w, c,
-                                           C.c_float(eps), C.c_float(-1.0 if leaky is None else float(leaky)),
-                                           _lib.ptr(ws), ws.numel() * 4, _lib.stream_ptr(x.device))
-    _lib.check(rc, "sr_instance_norm_nhwc_fwd")
+    _lib.call("sr_instance_norm_nhwc_fwd", x.device, x, isb, isp, out, osb, osp, b, h, w, c, eps,
+              -1.0 if leaky is None else float(leaky), ws, ws.numel() * 4)
     return out
 
 
@@ -694,10 +680,7 @@ def instance_norm_stats(x, eps=1e-5):
     lib = _lib.lib()
     ws = _workspace(x.device, "inorm", lib.sr_instance_norm_workspace_bytes(b, h, w, c))
     isb, isp = _strides(x)
-    with _lib.on_device(x.device):
-        rc = lib.sr_instance_norm_stats_nhwc(_lib.ptr(x), isb, isp, b, h, w, c, C.c_float(eps), _lib.ptr(stats),
-                                             _lib.ptr(ws), ws.numel() * 4, _lib.stream_ptr(x.device))
-    _lib.check(rc, "sr_instance_norm_stats_nhwc")
+    _lib.call("sr_instance_norm_stats_nhwc", x.device, x, isb, isp, b, h, w, c, eps, stats, ws, ws.numel() * 4)
     return stats
 
 
@@ -724,7 +707,7 @@ def conv1x1_stats(x, conv: nn.Conv2d, eps=1e-5):
     record = lambda: ("sr_conv1x1_stats_kernel", 2.0 * b * h * w * co * ci, (b, ci, h, w, co, 1, 1),
                       2.0 * b * ((h * w + 63) // 64) * 64 * co * ci)
     rc = _timed(x.device, record, lib.sr_conv1x1_stats_nhwc_fwd, _lib.ptr(x), isb, isp, _lib.ptr(weight), _lib.ptr(bias),
-                _lib.ptr(out), osb, osp, b, h, w, ci, co, C.c_float(eps), _lib.ptr(stats), _lib.ptr(ws), ws.numel() * 4,
+                _lib.ptr(out), osb, osp, b, h, w, ci, co, eps, _lib.ptr(stats), _lib.ptr(ws), ws.numel() * 4,
                 _lib.stream_ptr(x.device))
     _lib.check(rc, "sr_conv1x1_stats_nhwc_fwd")
     return out, stats
@@ -756,9 +739,9 @@ def conv3x3_c16(x, conv: nn.Conv2d, in_stats=None, in_leaky=None, leaky=None):
     record = lambda: ("sr_t16_kernel", 2.0 * b * h * w * co * ci * 9, (b, ci, h, w, co, 3, 1),
                       2.0 * b * ((h + 7) // 8) * ((w + 15) // 16) * 128 * 16 * ci * 9)
     rc = _timed(x.device, record, _lib.lib().sr_conv3x3_c16_nhwc_fwd, _lib.ptr(x), isb, isp, _lib.ptr(in_stats),
-                C.c_float(-1.0 if in_leaky is None else float(in_leaky)), _lib.ptr(wp), _lib.ptr(bias), _lib.ptr(out), osb,
+                -1.0 if in_leaky is None else float(in_leaky), _lib.ptr(wp), _lib.ptr(bias), _lib.ptr(out), osb,
                 osp, b, h, w, ci, co, int(conv.padding_mode == "replicate"),
-                C.c_float(-1.0 if leaky is None else float(leaky)), _lib.stream_ptr(x.device))
+                -1.0 if leaky is None else float(leaky), _lib.stream_ptr(x.device))
     _lib.check(rc, "sr_conv3x3_c16_nhwc_fwd")
     return out
 
@@ -804,11 +787,8 @@ def dwconv3x3(x, conv: nn.Conv2d, bn=None, leaky=None, act=None, tf_same=False, 
     if b > 0:
         isb, isp = _strides(x)
         osb, osp = _strides(out)
-        with _lib.on_device(x.device):
-            rc = lib.sr_dwconv3x3_nhwc_fwd(_lib.ptr(x), isb, isp, _lib.ptr(w9c), _lib.ptr(bias), _lib.ptr(out), osb,
-                                           osp, _lib.ptr(pool), b, h, w, c, s, *pads,
-                                           C.c_float(_act_code(leaky, act)), _lib.stream_ptr(x.device))
-        _lib.check(rc, "sr_dwconv3x3_nhwc_fwd")
+        _lib.call("sr_dwconv3x3_nhwc_fwd", x.device, x, isb, isp, w9c, bias, out, osb, osp, pool, b, h, w, c, s, *pads,
+                  _act_code(leaky, act))
     return (out, pool) if want_pool else out
 
 
@@ -830,11 +810,8 @@ def se_gate(pool_partial, pixels, conv_reduce: nn.Conv2d, conv_expand: nn.Conv2d
     b2 = conv_expand.bias.detach() if conv_expand.bias is not None else None
     for t in (w1, w2):
         _lib.require_device_f32("squeeze-excite weight", t)
-    with _lib.on_device(gate.device):
-        rc = _lib.lib().sr_se_gate_fwd(_lib.ptr(pool_partial.contiguous()), bands, pixels, _lib.ptr(w1.contiguous()),
-                                       _lib.ptr(b1), _lib.ptr(w2.contiguous()), _lib.ptr(b2), _lib.ptr(gate), b, c, rd,
-                                       _lib.stream_ptr(gate.device))
-    _lib.check(rc, "sr_se_gate_fwd")
+    _lib.call("sr_se_gate_fwd", gate.device, pool_partial.contiguous(), bands, pixels, w1.contiguous(), b1, w2.contiguous(),
+              b2, gate, b, c, rd)
     return gate
 
 
@@ -862,11 +839,8 @@ def rgb_stem3x3s2(image, conv: nn.Conv2d, bn=None, act=None, leaky=None, tf_same
         return out
     sb, sc, sy, sx = image.stride()
     osb, osp = _strides(out)
-    with _lib.on_device(image.device):
-        rc = _lib.lib().sr_rgb_stem3x3s2_fwd(_lib.ptr(image), sb, sc, sy, sx, _lib.ptr(w27), _lib.ptr(bias), _lib.ptr(out), osb,
-                                             osp, b, h, w, conv.out_channels, pads[0], pads[1], ho, wo,
-                                             C.c_float(_act_code(leaky, act)), _lib.stream_ptr(image.device))
-    _lib.check(rc, "sr_rgb_stem3x3s2_fwd")
+    _lib.call("sr_rgb_stem3x3s2_fwd", image.device, image, sb, sc, sy, sx, w27, bias, out, osb, osp, b, h, w,
+              conv.out_channels, pads[0], pads[1], ho, wo, _act_code(leaky, act))
     return out
 
 
@@ -889,11 +863,7 @@ def se_gates(pool_partial, pixels, conv_reduce: nn.Conv2d, conv_expand: nn.Conv2
         w1, w2 = w1.contiguous(), w2.contiguous()
     b1 = conv_reduce.bias.detach() if conv_reduce.bias is not None else None
     b2 = conv_expand.bias.detach() if conv_expand.bias is not None else None
-    with _lib.on_device(gate.device):
-        rc = _lib.lib().sr_se_gate2_fwd(_lib.ptr(pool_partial), bands, pixels, _lib.ptr(w1), _lib.ptr(b1), _lib.ptr(w2),
-                                        _lib.ptr(b2), _lib.ptr(hidden), _lib.ptr(gate), b, c, rd,
-                                        _lib.stream_ptr(gate.device))
-    _lib.check(rc, "sr_se_gate2_fwd")
+    _lib.call("sr_se_gate2_fwd", gate.device, pool_partial, bands, pixels, w1, b1, w2, b2, hidden, gate, b, c, rd)
     return gate
 
 
@@ -919,12 +889,8 @@ def se_scale_(x, pool_partial, conv_reduce: nn.Conv2d, conv_expand: nn.Conv2d, w
     b1 = conv_reduce.bias.detach() if conv_reduce.bias is not None else None
     b2 = conv_expand.bias.detach() if conv_expand.bias is not None else None
     sb, sp = _strides(x)
-    with _lib.on_device(x.device):
-        rc = _lib.lib().sr_se_scale_nhwc_fwd(_lib.ptr(pool_partial), pool_partial.shape[1], _lib.ptr(w1), _lib.ptr(b1),
-                                             _lib.ptr(w2), _lib.ptr(b2), _lib.ptr(hidden), _lib.ptr(x), sb, sp,
-                                             _lib.ptr(x), sb, sp, _lib.ptr(gate), b, h, w, c, rd,
-                                             _lib.stream_ptr(x.device))
-    _lib.check(rc, "sr_se_scale_nhwc_fwd")
+    _lib.call("sr_se_scale_nhwc_fwd", x.device, pool_partial, pool_partial.shape[1], w1, b1, w2, b2, hidden, x, sb, sp, x, sb,
+              sp, gate, b, h, w, c, rd)
     return (x, gate) if want_gate else x
 
 
@@ -940,10 +906,7 @@ def scale_channels_(x, gate):
     if b == 0:
         return x
     sb, sp = _strides(x)
-    with _lib.on_device(x.device):
-        rc = _lib.lib().sr_scale_channels_nhwc_fwd(_lib.ptr(x), sb, sp, _lib.ptr(gate), _lib.ptr(x), sb, sp, b, h, w, c,
-                                                   _lib.stream_ptr(x.device))
-    _lib.check(rc, "sr_scale_channels_nhwc_fwd")
+    _lib.call("sr_scale_channels_nhwc_fwd", x.device, x, sb, sp, gate, x, sb, sp, b, h, w, c)
     return x
 
 
@@ -959,8 +922,5 @@ def add_(y, x):
         return y
     ysb, ysp = _strides(y)
     xsb, xsp = _strides(x)
-    with _lib.on_device(y.device):
-        rc = _lib.lib().sr_add_nhwc_fwd(_lib.ptr(y), ysb, ysp, _lib.ptr(x), xsb, xsp, _lib.ptr(y), ysb, ysp, b, h, w, c,
-                                        _lib.stream_ptr(y.device))
-    _lib.check(rc, "sr_add_nhwc_fwd")
+    _lib.call("sr_add_nhwc_fwd", y.device, y, ysb, ysp, x, xsb, xsp, y, ysb, ysp, b, h, w, c)
     return y

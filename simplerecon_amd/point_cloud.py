@@ -7,7 +7,6 @@ include/simplerecon_hip.h, section "point-cloud fusion".
     PointCloudFuser                                pc_fusion.py's per-batch steps, fusion, downsampling and export
 
 There is no CPU path: without a GPU every entry point raises HipLibraryError."""
-import ctypes as C
 from typing import Optional
 
 import numpy as np
@@ -52,9 +51,7 @@ class PointCloud:
         pts = pts.contiguous()
         cols = None if self.colors is None else self.colors.contiguous()
         dev = pts.device
-        lib = _lib.lib()
-        with torch.cuda.device(dev):
-            stream = _lib.stream_ptr(dev)
+        with _lib.on_device(dev):
             p64 = pts.double()
             ext = torch.stack([p64.amin(0), p64.amax(0)]).cpu().numpy()
             if not np.isfinite(ext).all():
@@ -65,9 +62,7 @@ class PointCloud:
                 raise ValueError(f"voxel_down_sample: {extent.astype(np.int64).tolist()} voxels per axis; keys hold "
                                  f"fewer than 2^21 per axis (use a larger voxel_size)")
             keys = torch.empty(M, dtype=torch.int64, device=dev)
-            d = C.c_double
-            _lib.check(lib.sr_pc_voxel_keys(_lib.ptr(pts), M, d(min_bound[0]), d(min_bound[1]), d(min_bound[2]), d(vs),
-                                            _lib.ptr(keys), stream), "sr_pc_voxel_keys")
+            _lib.call("sr_pc_voxel_keys", dev, pts, M, *min_bound, vs, keys)
             skeys, order = torch.sort(keys, stable=True)
             _, counts = torch.unique_consecutive(skeys, return_counts=True)
             S = int(counts.shape[0])
@@ -75,8 +70,7 @@ class PointCloud:
             torch.cumsum(counts, 0, out=seg[1:])
             out_pts = torch.empty((S, 3), dtype=torch.float32, device=dev)
             out_cols = None if cols is None else torch.empty((S, 3), dtype=torch.uint8, device=dev)
-            _lib.check(lib.sr_pc_voxel_mean(_lib.ptr(pts), _lib.ptr(cols), M, _lib.ptr(order), _lib.ptr(seg), S,
-                                            _lib.ptr(out_pts), _lib.ptr(out_cols), stream), "sr_pc_voxel_mean")
+            _lib.call("sr_pc_voxel_mean", dev, pts, cols, M, order, seg, S, out_pts, out_cols)
         return PointCloud(out_pts, out_cols)
 
     def write_ply(self, path):
@@ -157,16 +151,13 @@ def _fuse(depths, images, cam_T_world, K, z_thresh, n_consistent_thresh, ref_beg
     per_frame = h * w * _FRAME_BYTES_PER_PIXEL
     chunk = chunk_frames or max(1, min(ref_count, int(scratch_bytes) // per_frame))
     chunk = max(1, min(chunk, (2 ** 31 - 1) // (h * w * 12)))
-    lib = _lib.lib()
     pts_out, rgb_out, valid_out = [], [], []
-    with torch.cuda.device(dev):
-        stream = _lib.stream_ptr(dev)
+    with _lib.on_device(dev):
         for b in range(ref_begin, ref_begin + ref_count, chunk):
             c = min(chunk, ref_begin + ref_count - b)
             points = torch.empty((c, h, w, 3), dtype=torch.float32, device=dev)
             counts = torch.empty((c, h, w), dtype=torch.int32, device=dev)
-            _lib.check(lib.sr_pc_consistency(_lib.ptr(D), _lib.ptr(consts), N, h, w, b, c, C.c_float(zt),
-                                             _lib.ptr(points), _lib.ptr(counts), stream), "sr_pc_consistency")
+            _lib.call("sr_pc_consistency", dev, D, consts, N, h, w, b, c, zt, points, counts)
             keep = counts >= int(n_consistent_thresh)
             pts_out.append(points[keep])
             if imgs is not None:

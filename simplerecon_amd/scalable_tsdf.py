@@ -18,7 +18,6 @@ number of new blocks.  `extract_mesh` reads the vertex and face totals once.
     mesh = vol.extract_mesh()                                             # TriangleMesh with colors
 
 There is no CPU fallback: inputs must live on the GPU."""
-import ctypes as C
 
 import numpy as np
 import torch
@@ -146,7 +145,7 @@ class ScalableTSDFVolume:
             raise ValueError(f"depth maps up to 32768 x 32768, got {h} x {w}")
         if B == 0 or h == 0 or w == 0:
             return
-        with torch.cuda.device(self.device):
+        with _lib.on_device(self.device):
             depth = depth_b1hw.to(self.device)[:, 0].float()
             depth = torch.where(depth > self.max_depth, torch.zeros_like(depth), depth).contiguous()
             K = K_b44.to(self.device).float()
@@ -179,17 +178,13 @@ class ScalableTSDFVolume:
 
     def _integrate_chunk(self, depth, K, T, color):
         b, h, w = depth.shape
-        lib = _lib.lib()
-        stream = _lib.stream_ptr(self.device)
         frames_inv, frames = self._frames(K, T)
         S = ((h + 3) // 4) * ((w + 3) // 4)
         cand = torch.empty(b * S * 8, dtype=torch.int64, device=self.device)
-        _lib.check(lib.sr_stsdf_touch(_lib.ptr(depth), b, h, w, _lib.ptr(frames_inv), C.c_double(self.sdf_trunc),
-                                      C.c_double(self.unit), _lib.ptr(cand), stream), "sr_stsdf_touch")
+        _lib.call("sr_stsdf_touch", self.device, depth, b, h, w, frames_inv, self.sdf_trunc, self.unit, cand)
         ukeys, inverse = torch.unique(cand, sorted=True, return_inverse=True)
         masks = torch.zeros(ukeys.numel(), dtype=torch.int64, device=self.device)
-        _lib.check(lib.sr_stsdf_block_masks(_lib.ptr(cand), _lib.ptr(inverse), cand.numel(), S * 8, _lib.ptr(masks),
-                                            stream), "sr_stsdf_block_masks")
+        _lib.call("sr_stsdf_block_masks", self.device, cand, inverse, cand.numel(), S * 8, masks)
         n = self.num_blocks
         valid = ukeys != KEY_NONE
         if n:
@@ -204,10 +199,8 @@ class ScalableTSDFVolume:
         self._grow(n + n_new)
         new_slot = n + torch.cumsum(new, 0) - 1
         slots = torch.where(found, old_slot, torch.where(new, new_slot, torch.full_like(new_slot, -1))).contiguous()
-        rc = lib.sr_stsdf_integrate(_lib.ptr(self._pool), self.capacity, _lib.ptr(ukeys), _lib.ptr(slots),
-                                    _lib.ptr(masks), ukeys.numel(), _lib.ptr(frames), _lib.ptr(depth), _lib.ptr(color),
-                                    b, h, w, C.c_float(self.voxel_length), C.c_float(self.sdf_trunc), stream)
-        _lib.check(rc, "sr_stsdf_integrate")
+        _lib.call("sr_stsdf_integrate", self.device, self._pool, self.capacity, ukeys, slots, masks, ukeys.numel(), frames,
+                  depth, color, b, h, w, self.voxel_length, self.sdf_trunc)
         if n_new:
             keys = torch.cat([self._keys, ukeys[new]])
             slots_all = torch.cat([self._slots, slots[new]])
@@ -226,12 +219,9 @@ class ScalableTSDFVolume:
                              torch.zeros((0, 3), dtype=torch.float32, device=dev))
         if n == 0:
             return empty
-        lib = _lib.lib()
-        with torch.cuda.device(dev):
-            stream = _lib.stream_ptr(dev)
+        with _lib.on_device(dev):
             counts = torch.empty((2, n), dtype=torch.int32, device=dev)
-            _lib.check(lib.sr_stsdf_mesh_count(_lib.ptr(self._pool), self.capacity, _lib.ptr(self._keys),
-                                               _lib.ptr(self._slots), n, _lib.ptr(counts), stream), "sr_stsdf_mesh_count")
+            _lib.call("sr_stsdf_mesh_count", dev, self._pool, self.capacity, self._keys, self._slots, n, counts)
             c64 = counts.long()
             incl = torch.cumsum(c64, 1)
             offsets = (incl - c64).contiguous()
@@ -244,10 +234,8 @@ class ScalableTSDFVolume:
             verts = torch.empty((nv, 3), dtype=torch.float32, device=dev)
             colors = torch.empty((nv, 3), dtype=torch.float32, device=dev)
             faces = torch.empty((nf, 3), dtype=torch.int32, device=dev)
-            rc = lib.sr_stsdf_mesh_emit(_lib.ptr(self._pool), self.capacity, _lib.ptr(self._keys), _lib.ptr(self._slots),
-                                        n, C.c_float(self.voxel_length), _lib.ptr(offsets), nv, nf, _lib.ptr(vtab),
-                                        _lib.ptr(verts), _lib.ptr(colors), _lib.ptr(faces), stream)
-            _lib.check(rc, "sr_stsdf_mesh_emit")
+            _lib.call("sr_stsdf_mesh_emit", dev, self._pool, self.capacity, self._keys, self._slots, n, self.voxel_length,
+                      offsets, nv, nf, vtab, verts, colors, faces)
         return TriangleMesh(verts, faces, None, colors)
 
 

@@ -8,8 +8,6 @@ convolutions -- autograd_ops._ConvBiasAct with explicit pads).  In training the 
 (+ activation) are separate operators because batch statistics need the raw conv output; inference keeps the folded,
 fused kernels.  Gradients are pinned to the reference's own autograd (tests/golden/grad_matching_encoder_*.npz) and, for
 the third-party EfficientNetV2-S, to the ATen restatement of its public definition (tests/effnet_torch.py)."""
-import ctypes as C
-
 import torch
 from torch import nn
 
@@ -28,10 +26,7 @@ def _dense(t, name="tensor"):
 def _add_flat_(a, b):
     """a += b for two dense fp32 tensors of the same size (numel % 4 == 0), on the HIP add kernel."""
     n = a.numel()
-    with _lib.on_device(a.device):
-        rc = _lib.lib().sr_add_nhwc_fwd(_lib.ptr(a), n, 4, _lib.ptr(b), n, 4, _lib.ptr(a), n, 4, 1, 1, n // 4, 4,
-                                        _lib.stream_ptr(a.device))
-    _lib.check(rc, "sr_add_nhwc_fwd")
+    _lib.call("sr_add_nhwc_fwd", a.device, a, n, 4, b, n, 4, a, n, 4, 1, 1, n // 4, 4)
     return a
 
 
@@ -60,16 +55,13 @@ class _NormAct(torch.autograd.Function):
             osb, osp = _strides(out)
             nws = lib.sr_norm_workspace_bytes(b, h * w, c, int(per_image))
             ws = _workspace(dev, "norm", nws)
-            st = _lib.stream_ptr(dev)
             with _lib.on_device(dev):
                 if train_stats:
-                    _lib.check(lib.sr_norm_stats_nhwc(_lib.ptr(x), xsb, xsp, b, h * w, c, int(per_image), _lib.ptr(mean),
-                                                      _lib.ptr(var), _lib.ptr(ws), nws, st), "sr_norm_stats_nhwc")
+                    _lib.call("sr_norm_stats_nhwc", dev, x, xsb, xsp, b, h * w, c, int(per_image), mean, var, ws, nws)
                 gd = gamma.detach().contiguous() if gamma is not None else None
                 bd = beta.detach().contiguous() if beta is not None else None
-                _lib.check(lib.sr_norm_act_fwd_nhwc(_lib.ptr(x), xsb, xsp, _lib.ptr(mean), _lib.ptr(var), C.c_float(eps),
-                                                    _lib.ptr(gd), _lib.ptr(bd), C.c_float(act), int(per_image),
-                                                    _lib.ptr(out), osb, osp, b, h * w, c, st), "sr_norm_act_fwd_nhwc")
+                _lib.call("sr_norm_act_fwd_nhwc", dev, x, xsb, xsp, mean, var, eps, gd, bd, act, int(per_image), out, osb,
+                          osp, b, h * w, c)
         _stash(ctx, x, gamma, beta, mean, var)
         ctx.cfg = (eps, act, per_image, train_stats)
         ctx.mark_non_differentiable(mean, var)
@@ -99,12 +91,8 @@ class _NormAct(torch.autograd.Function):
         ws = _workspace(dev, "norm", nws)
         gd = gamma.detach().contiguous() if gamma is not None else None
         bd = beta.detach().contiguous() if beta is not None else None
-        with _lib.on_device(dev):
-            rc = lib.sr_norm_act_bwd_nhwc(_lib.ptr(g), gsb, gsp, _lib.ptr(x), xsb, xsp, _lib.ptr(mean), _lib.ptr(var),
-                                          C.c_float(eps), _lib.ptr(gd), _lib.ptr(bd), C.c_float(act), int(per_image),
-                                          int(train_stats), _lib.ptr(dx), dsb, dsp, _lib.ptr(d_gamma), _lib.ptr(d_beta), b,
-                                          h * w, c, _lib.ptr(ws), nws, _lib.stream_ptr(dev))
-        _lib.check(rc, "sr_norm_act_bwd_nhwc")
+        _lib.call("sr_norm_act_bwd_nhwc", dev, g, gsb, gsp, x, xsb, xsp, mean, var, eps, gd, bd, act, int(per_image),
+                  int(train_stats), dx, dsb, dsp, d_gamma, d_beta, b, h * w, c, ws, nws)
         return dx, d_gamma, d_beta, None, None, None, None, None, None
 
 
@@ -156,10 +144,8 @@ class _MaxBlurPool(torch.autograd.Function):
             return dx
         nws = lib.sr_maxblurpool_bwd_workspace_bytes(b, h, w, c)
         ws = _workspace(x.device, "maxblurpool_bwd", nws)
-        with _lib.on_device(x.device):
-            rc = lib.sr_maxblurpool_bwd_nhwc(_lib.ptr(g), *_strides(g), _lib.ptr(x), *_strides(x), _lib.ptr(dx),
-                                             *_strides(dx), b, h, w, c, _lib.ptr(ws), nws, _lib.stream_ptr(x.device))
-        _lib.check(rc, "sr_maxblurpool_bwd_nhwc")
+        _lib.call("sr_maxblurpool_bwd_nhwc", x.device, g, *_strides(g), x, *_strides(x), dx, *_strides(dx), b, h, w, c, ws,
+                  nws)
         return dx
 
 
@@ -175,10 +161,7 @@ class _ReplicatePad(torch.autograd.Function):
         b, c, h, w = x.shape
         y = empty_nhwc(b, c, h + 2 * pad, w + 2 * pad, x.device)
         if b > 0:
-            with _lib.on_device(x.device):
-                rc = _lib.lib().sr_replicate_pad_nhwc_fwd(_lib.ptr(x), *_strides(x), _lib.ptr(y), b, h, w, c, pad,
-                                                          _lib.stream_ptr(x.device))
-            _lib.check(rc, "sr_replicate_pad_nhwc_fwd")
+            _lib.call("sr_replicate_pad_nhwc_fwd", x.device, x, *_strides(x), y, b, h, w, c, pad)
         ctx.shape, ctx.pad = (b, c, h, w), pad
         return y
 
@@ -189,10 +172,7 @@ class _ReplicatePad(torch.autograd.Function):
         g = _dense(g)
         dx = empty_nhwc(b, c, h, w, g.device)
         if b > 0:
-            with _lib.on_device(g.device):
-                rc = _lib.lib().sr_replicate_pad_nhwc_bwd(_lib.ptr(g), _lib.ptr(dx), b, h, w, c, ctx.pad,
-                                                          _lib.stream_ptr(g.device))
-            _lib.check(rc, "sr_replicate_pad_nhwc_bwd")
+            _lib.call("sr_replicate_pad_nhwc_bwd", g.device, g, dx, b, h, w, c, ctx.pad)
         return dx, None
 
 
@@ -226,7 +206,6 @@ class _Stem7x7(torch.autograd.Function):
             return None, None, None
         if b == 0:
             return None, torch.zeros((64, 3, 7, 7), dtype=torch.float32, device=dev), None
-        st = _lib.stream_ptr(dev)
         # unfold a few images at a time into ONE reused buffer of <= 256 MB: [n, Ho, Wo, 160] floats (49 MB per 640x480
         # image); the weight-gradient partials of the chunks are added in chunk order
         per = max(1, min(b, (1 << 28) // max(ho * wo * kp * 4, 1)))
@@ -238,15 +217,14 @@ class _Stem7x7(torch.autograd.Function):
                 col = col_buf[:n]
                 img = image[i0:i0 + n]
                 sb, sc, sy, sx = img.stride()
-                _lib.check(lib.sr_im2col7x7s2_nhwc(_lib.ptr(img), sb, sc, sy, sx, _lib.ptr(col), n, h, w, kp, st),
-                           "sr_im2col7x7s2_nhwc")
+                _lib.call("sr_im2col7x7s2_nhwc", dev, img, sb, sc, sy, sx, col, n, h, w, kp)
                 gi = g[i0:i0 + n]
                 gsb, gsp = _strides(gi)
                 dw = torch.empty((64, kp), dtype=torch.float32, device=dev)
                 nws = lib.sr_conv_wgrad_workspace_bytes(n, ho, wo, kp, 64, 1, 1)
                 ws = _workspace(dev, "wgrad", nws)
-                _lib.check(lib.sr_conv_wgrad_nhwc(_lib.ptr(col), ho * wo * kp, kp, _lib.ptr(gi), gsb, gsp, _lib.ptr(dw), n, ho,
-                                                  wo, kp, 64, 1, 1, _lib.ptr(ws), nws, st), "sr_conv_wgrad_nhwc")
+                _lib.call("sr_conv_wgrad_nhwc", dev, col, ho * wo * kp, kp, gi, gsb, gsp, dw, n, ho, wo, kp, 64, 1, 1, ws,
+                          nws)
                 acc = dw if acc is None else _add_flat_(acc, dw)
         d_w = acc[:, :147].reshape(64, 3, 7, 7).contiguous()
         return None, d_w, None
@@ -309,11 +287,8 @@ class _DwConv3x3(torch.autograd.Function):
         nws = lib.sr_dwconv3x3_bwd_workspace_bytes(b, ho, wo, c)
         ws = _workspace(dev, "dw_bwd", nws)
         wd = weight.detach().reshape(c, 9).contiguous()
-        with _lib.on_device(dev):
-            rc = lib.sr_dwconv3x3_bwd_nhwc(_lib.ptr(g), *_strides(g), _lib.ptr(x), *_strides(x), _lib.ptr(wd), _lib.ptr(dx),
-                                           _lib.ptr(dw), b, h, w, c, s, pads[0], pads[1], ho, wo, _lib.ptr(ws), nws,
-                                           _lib.stream_ptr(dev))
-        _lib.check(rc, "sr_dwconv3x3_bwd_nhwc")
+        _lib.call("sr_dwconv3x3_bwd_nhwc", dev, g, *_strides(g), x, *_strides(x), wd, dx, dw, b, h, w, c, s, pads[0], pads[1],
+                  ho, wo, ws, nws)
         return dx, dw, None, None
 
 
@@ -343,18 +318,11 @@ class _SqueezeExcite(torch.autograd.Function):
         if b > 0:
             nws = lib.sr_norm_workspace_bytes(b, h * w, c, 1)
             ws = _workspace(dev, "norm", nws)
-            st = _lib.stream_ptr(dev)
             with _lib.on_device(dev):
-                _lib.check(lib.sr_rowsum_nhwc(_lib.ptr(x), *_strides(x), None, 0, 0, b, h * w, c, C.c_float(1.0 / (h * w)),
-                                              _lib.ptr(pooled), _lib.ptr(ws), nws, st), "sr_rowsum_nhwc")
-                _lib.check(lib.sr_small_linear_fwd(_lib.ptr(pooled), _lib.ptr(w1d), _lib.ptr(b1.detach().contiguous()),
-                                                   _lib.ptr(pre1), _lib.ptr(hid), b, c, rd, C.c_float(ACT_SILU), st),
-                           "sr_small_linear_fwd")
-                _lib.check(lib.sr_small_linear_fwd(_lib.ptr(hid), _lib.ptr(w2d), _lib.ptr(b2.detach().contiguous()),
-                                                   _lib.ptr(pre2), _lib.ptr(gate), b, rd, c, C.c_float(ACT_SIGMOID), st),
-                           "sr_small_linear_fwd")
-                _lib.check(lib.sr_scale_channels_nhwc_fwd(_lib.ptr(x), *_strides(x), _lib.ptr(gate), _lib.ptr(y), *_strides(y),
-                                                          b, h, w, c, st), "sr_scale_channels_nhwc_fwd")
+                _lib.call("sr_rowsum_nhwc", dev, x, *_strides(x), None, 0, 0, b, h * w, c, 1.0 / (h * w), pooled, ws, nws)
+                _lib.call("sr_small_linear_fwd", dev, pooled, w1d, b1.detach().contiguous(), pre1, hid, b, c, rd, ACT_SILU)
+                _lib.call("sr_small_linear_fwd", dev, hid, w2d, b2.detach().contiguous(), pre2, gate, b, rd, c, ACT_SIGMOID)
+                _lib.call("sr_scale_channels_nhwc_fwd", dev, x, *_strides(x), gate, y, *_strides(y), b, h, w, c)
         _stash(ctx, x, w1d, w2d, pooled, pre1, hid, pre2, gate)
         ctx.shapes = (tuple(w1.shape), tuple(w2.shape))
         return y
@@ -378,18 +346,11 @@ class _SqueezeExcite(torch.autograd.Function):
             return dx, dw1.zero_().reshape(ctx.shapes[0]), db1.zero_(), dw2.zero_().reshape(ctx.shapes[1]), db2.zero_()
         nws = lib.sr_norm_workspace_bytes(b, h * w, c, 1)
         ws = _workspace(dev, "norm", nws)
-        st = _lib.stream_ptr(dev)
         with _lib.on_device(dev):
-            _lib.check(lib.sr_rowsum_nhwc(_lib.ptr(x), *_strides(x), _lib.ptr(g), *_strides(g), b, h * w, c, C.c_float(1.0),
-                                          _lib.ptr(dgate), _lib.ptr(ws), nws, st), "sr_rowsum_nhwc")
-            _lib.check(lib.sr_small_linear_bwd(_lib.ptr(dgate), _lib.ptr(pre2), _lib.ptr(hid), _lib.ptr(w2d), _lib.ptr(dhid),
-                                               _lib.ptr(dw2), _lib.ptr(db2), b, rd, c, C.c_float(ACT_SIGMOID), st),
-                       "sr_small_linear_bwd")
-            _lib.check(lib.sr_small_linear_bwd(_lib.ptr(dhid), _lib.ptr(pre1), _lib.ptr(pooled), _lib.ptr(w1d), _lib.ptr(dpool),
-                                               _lib.ptr(dw1), _lib.ptr(db1), b, c, rd, C.c_float(ACT_SILU), st),
-                       "sr_small_linear_bwd")
-            _lib.check(lib.sr_scale_bwd_nhwc(_lib.ptr(g), *_strides(g), _lib.ptr(gate), _lib.ptr(dpool),
-                                             C.c_float(1.0 / (h * w)), _lib.ptr(dx), b, h * w, c, st), "sr_scale_bwd_nhwc")
+            _lib.call("sr_rowsum_nhwc", dev, x, *_strides(x), g, *_strides(g), b, h * w, c, 1.0, dgate, ws, nws)
+            _lib.call("sr_small_linear_bwd", dev, dgate, pre2, hid, w2d, dhid, dw2, db2, b, rd, c, ACT_SIGMOID)
+            _lib.call("sr_small_linear_bwd", dev, dhid, pre1, pooled, w1d, dpool, dw1, db1, b, c, rd, ACT_SILU)
+            _lib.call("sr_scale_bwd_nhwc", dev, g, *_strides(g), gate, dpool, 1.0 / (h * w), dx, b, h * w, c)
         return dx, dw1.reshape(ctx.shapes[0]), db1, dw2.reshape(ctx.shapes[1]), db2
 
 
@@ -413,10 +374,7 @@ class _AddAct(torch.autograd.Function):
         out = torch.empty_like(a)
         pre = torch.empty_like(a) if act != ACT_NONE else None
         if a.numel() > 0:
-            with _lib.on_device(a.device):
-                rc = _lib.lib().sr_add_act_fwd(_lib.ptr(a), _lib.ptr(b), _lib.ptr(pre), _lib.ptr(out), a.numel(), C.c_float(act),
-                                               _lib.stream_ptr(a.device))
-            _lib.check(rc, "sr_add_act_fwd")
+            _lib.call("sr_add_act_fwd", a.device, a, b, pre, out, a.numel(), act)
         ctx.act = act
         if pre is not None:
             _stash(ctx, pre)
@@ -431,10 +389,7 @@ class _AddAct(torch.autograd.Function):
         g = _dense(g)
         gz = torch.empty_like(pre)
         if pre.numel() > 0:
-            with _lib.on_device(pre.device):
-                rc = _lib.lib().sr_act_in_bwd(_lib.ptr(g), _lib.ptr(pre), _lib.ptr(gz), pre.numel(), C.c_float(ctx.act),
-                                              _lib.stream_ptr(pre.device))
-            _lib.check(rc, "sr_act_in_bwd")
+            _lib.call("sr_act_in_bwd", pre.device, g, pre, gz, pre.numel(), ctx.act)
         return gz, gz, None
 
 

@@ -17,7 +17,6 @@ The reference's other fuser, `depth_fuser="open3d"` (sparse, unbounded, with col
 `scalable_tsdf.Open3DFuser`.  Not provided: `to_mesh` (its contract is a trimesh.Trimesh).  There is no CPU fallback:
 tensors must live on the GPU.
 """
-import ctypes as C
 import os
 from typing import Optional, Tuple
 
@@ -94,14 +93,11 @@ def marching_cubes(tsdf_values: torch.Tensor, level=0.0, origin=(0.0, 0.0, 0.0),
     vals = vals.contiguous()
     dev = vals.device
     lib = _lib.lib()
-    f = C.c_float
-    with torch.cuda.device(dev):
-        stream = _lib.stream_ptr(dev)
+    with _lib.on_device(dev):
         cbytes = lib.sr_mesh_count_scratch_bytes(X, Y, Z)
         cscratch = torch.empty(cbytes, dtype=torch.uint8, device=dev)
         totals = torch.empty(3, dtype=torch.int64, device=dev)
-        _lib.check(lib.sr_mesh_count(_lib.ptr(vals), X, Y, Z, f(level), _lib.ptr(cscratch), cbytes, _lib.ptr(totals),
-                                     stream), "sr_mesh_count")
+        _lib.call("sr_mesh_count", dev, vals, X, Y, Z, float(level), cscratch, cbytes, totals)
         active, nv, nf = (int(x) for x in totals.tolist())
         if nv >= 2 ** 31 or nf >= 2 ** 31:
             raise _lib.HipLibraryError(f"mesh of {nv} vertices / {nf} faces: int32 face indices cannot address it")
@@ -111,10 +107,8 @@ def marching_cubes(tsdf_values: torch.Tensor, level=0.0, origin=(0.0, 0.0, 0.0),
         normals = torch.empty((nv, 3), dtype=torch.float32, device=dev) if compute_normals else None
         faces = torch.empty((nf, 3), dtype=torch.int32, device=dev)
         ox, oy, oz = (float(o) for o in origin)
-        rc = lib.sr_mesh_emit(_lib.ptr(vals), X, Y, Z, f(level), f(ox), f(oy), f(oz), f(scale), _lib.ptr(cscratch), cbytes,
-                              _lib.ptr(lscratch), lbytes, active, nv, nf, _lib.ptr(verts), _lib.ptr(normals),
-                              _lib.ptr(faces), stream)
-        _lib.check(rc, "sr_mesh_emit")
+        _lib.call("sr_mesh_emit", dev, vals, X, Y, Z, float(level), ox, oy, oz, float(scale), cscratch, cbytes, lscratch,
+                  lbytes, active, nv, nf, verts, normals, faces)
         # the scratch buffers go back to torch's caching allocator, which orders their reuse on this stream
     return TriangleMesh(verts, faces, normals)
 
@@ -303,15 +297,9 @@ class TSDFFuser:
             ox = oy = oz = 0.0
         if b == 0:
             return
-        lib = _lib.lib()
-        f = C.c_float
-        with torch.cuda.device(dev):
-            rc = lib.sr_tsdf_integrate_fwd(
-                _lib.ptr(vol.tsdf_values), _lib.ptr(vol.tsdf_weights), _lib.ptr(coords), X, Y, Z, f(ox), f(oy), f(oz),
-                f(vol.voxel_size), _lib.ptr(depth), _lib.ptr(mask), _lib.ptr(K), _lib.ptr(T), b, h, w,
-                f(self.min_depth), f(self.max_depth), f(self.max_depth - self.min_depth), f(self.truncation),
-                f(self.maxW), _lib.stream_ptr(dev))
-        _lib.check(rc, "sr_tsdf_integrate_fwd")
+        _lib.call("sr_tsdf_integrate_fwd", dev, vol.tsdf_values, vol.tsdf_weights, coords, X, Y, Z, ox, oy, oz,
+                  float(vol.voxel_size), depth, mask, K, T, b, h, w, float(self.min_depth), float(self.max_depth),
+                  float(self.max_depth - self.min_depth), float(self.truncation), float(self.maxW))
 
 
 class OurFuser:

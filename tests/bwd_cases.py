@@ -53,7 +53,8 @@ def bias_grad_chunks(pixels):
 # ------------------------------------------------------------------------------------------- A. convolutions ----
 # prop: the structural property the row is listed for, a predicate on wgrad_plan's numbers (and the case).
 # dx:   prefix of the kernel the DATA gradient runs (autograd_ops._conv_raw on the flipped weight; recorded in ops.PROFILE).
-#       _conv_raw calls the library's plain entry points: F(2x2) Winograd (no K split) where sr_conv_prefers_wino says so and
+#       _conv_raw calls ops' Winograd / direct launchers without a split-K workspace (sr_conv3x3_wino_splitk_nhwc_fwd /
+#       sr_conv2d_splitk_nhwc_fwd with workspace = NULL): F(2x2) Winograd (no K split) where sr_conv_prefers_wino says so and
 #       the padding is symmetric, the direct implicit-GEMM kernel otherwise -- 1x1 and explicit pads included.  The F(4x4),
 #       split-K and pointwise-GEMM kernels belong to ops.conv2d's dispatcher (inference) and are NOT reached from training.
 def _c(name, B, ci, co, k, s, H, W, prop, dx, kind=None, bias=True, res=False, slope=None, slice_=False):

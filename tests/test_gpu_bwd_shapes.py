@@ -11,7 +11,8 @@ Kinks: where the float64 pre-activation of a ReLU / LeakyReLU is within 1e-4 of 
 (both sides then see a zero upstream gradient where the derivative is ambiguous in fp32); the zeroed share is asserted
 <= 2e-3.  Deterministic kernels (all but the atomics bias gradient) are run twice and compared bit for bit.
 
-What the data gradient runs: autograd_ops._conv_raw calls the library's plain entry points, so d_x is F(2x2) Winograd
+What the data gradient runs: autograd_ops._conv_raw calls ops' Winograd / direct launchers without a split-K workspace
+(sr_conv3x3_wino_splitk_nhwc_fwd / sr_conv2d_splitk_nhwc_fwd with workspace = NULL), so d_x is F(2x2) Winograd
 (without K split) or the direct implicit-GEMM kernel -- never F(4x4), split-K Winograd or the pointwise GEMM, which belong
 to ops.conv2d's inference dispatcher.  The cases assert the kernel that really ran.
 
