@@ -849,6 +849,72 @@ int sr_stsdf_mesh_emit(const float* pool, int64_t capacity, const int64_t* keys,
                        float voxel_length, const int64_t* block_offsets, int64_t num_vertices, int64_t num_faces,
                        int32_t* vertex_table, float* vertices, float* colors, int32_t* faces, void* stream);
 
+/* ------------------------------------------------------------- mesh rasteriser ----
+ *
+ * Depth and face-id renders of one triangle mesh into B pinhole views (geometry only: no shading), and the per-face
+ * visibility they give.  tests/raster_oracle.py is the float64 ray caster the renders are checked against.
+ *
+ * Inputs: vertices [V,3] fp32, faces [F,3] int32, K [B][16] and cam_T_world [B][16] fp32 row-major 4x4 (of K: fx =
+ * K[0][0], fy = K[1][1], cx = K[0][2], cy = K[1][2]; skew is not supported), H, W <= SR_RASTER_MAX_SIDE, znear > 0,
+ * pixel_offset o in [-1, 1].  Pixel (u, v) samples the ray ((u + o - cx) / fx, (v + o - cy) / fy, 1): o = 0 is this
+ * project's backprojection convention, o = 0.5 OpenGL's pixel centres.
+ *
+ * Per (view, face), in fp64 from the fp32 inputs:
+ *  - X = R x + t per vertex.  The face is dropped when an index is outside [0, V), when n = (X1 - X0) x (X2 - X0) is
+ *    zero or not finite, or when the plane passes through the camera centre.  n is normalised, c = n . X0; the face
+ *    is front-facing when c < 0 (n points at the camera centre; TriangleMesh's winding, counter-clockwise seen from
+ *    free space).  SR_RASTER_CULL_BACK drops the others.
+ *  - The triangle is clipped at z = znear / 2 (one triangle may become two; a cut point is always computed from the
+ *    vertex in front to the vertex behind, so two faces sharing an edge share the point).  The clip only keeps the
+ *    projection finite: the pixel test z >= znear below decides what is seen.
+ *  - Projection x = fx X / Z + cx - o, y likewise: pixel centres are the integers.  The bounding box is clamped to the
+ *    image; a box without a pixel centre, or a projected area of zero, drops the triangle.
+ *  - Coverage: a pixel belongs to the triangle when it lies inside or on its three edges.  An edge's value is computed
+ *    from its two end points in an order that depends on the points alone, so the two faces on a shared edge see
+ *    exactly opposite values: a pixel is never missed by both.
+ *  - Depth, fp32: z = c / ((n_x r_x + n_y r_y) + n_z) with r the pixel's ray above -- the camera-space plane along
+ *    the ray, not interpolated screen-space z.  A pixel is hit when znear <= z < inf.
+ * Each hit does atomicMin on the pixel's key (bits of z) << 32 | face: the image does not depend on the launch
+ * order and equal depths go to the lowest face id.  Boxes of at most 256 pixels are walked by one lane of the setup
+ * kernel; larger ones become records, are cut into tiles of 16 x 4 pixels, and one wave serves each (record, tile) --
+ * no thread loops over more than 256 pixels.
+ *
+ * Use: sr_raster_small (sets keys [B,H,W] to empty and counters [2] to 0, draws the small triangles, counts the
+ * large ones in counters[0]) -> if any: sr_raster_large_setup (records [capacity][SR_RASTER_RECORD_BYTES], 8-byte
+ * aligned, and tile_counts [capacity] int32, capacity >= counters[0]; slots are taken from counters[1]) -> the
+ * caller's inclusive prefix sum of tile_counts as int64 (tile_ends; its last entry is num_items) -> sr_raster_large
+ * -> sr_raster_resolve (depth [n] fp32, 0 where empty; face [n] int32, -1 where empty; either may be NULL).
+ *
+ * Visibility.  sr_raster_visibility_mask sets bit b of masks[f] (uint64 [F], zeroed by the caller before the first
+ * call) for every pixel of view b < B <= SR_RASTER_MASK_VIEWS that face f won.  sr_raster_visibility_count adds each
+ * mask's bit count to counts [F] int32 (zeroed by the caller before the first call), clears the mask, and writes
+ * visible[f] = counts[f] >= min_views (uint8, optional): more than 64 views go through in groups.
+ *
+ * Integer atomics only: every output is the same bits on every run.  The library allocates nothing and no call
+ * synchronises with the host.  Refused (SR_ERR_INVALID_ARGUMENT): NULL required pointers, counts or sizes outside
+ * their range (SR_RASTER_MAX_THREADS, SR_RASTER_MAX_PAIRS: render more views in several calls), an unknown cull mode, a misaligned record buffer. */
+#define SR_RASTER_CULL_NONE 0
+#define SR_RASTER_CULL_BACK 1
+#define SR_RASTER_MAX_SIDE 32768
+#define SR_RASTER_RECORD_BYTES 80
+#define SR_RASTER_MASK_VIEWS 64
+#define SR_RASTER_MAX_THREADS 0xffffff00ll /* per launch: B * H * W, B * F and 64 * num_items stay at or below it */
+#define SR_RASTER_MAX_PAIRS (1ll << 30)    /* B * F: the int32 counters hold two triangles per (view, face) */
+int sr_raster_small(const float* vertices, int64_t num_vertices, const int32_t* faces, int64_t num_faces, const float* K,
+                    const float* cam_T_world, int B, int H, int W, float znear, float pixel_offset, int cull,
+                    uint64_t* keys, int32_t* counters, void* stream);
+int sr_raster_large_setup(const float* vertices, int64_t num_vertices, const int32_t* faces, int64_t num_faces,
+                          const float* K, const float* cam_T_world, int B, int H, int W, float znear, float pixel_offset,
+                          int cull, int64_t capacity, int32_t* counters, void* records, int32_t* tile_counts,
+                          void* stream);
+int sr_raster_large(const void* records, const int64_t* tile_ends, int64_t num_large, int64_t num_items, const float* K,
+                    int B, int H, int W, float znear, float pixel_offset, uint64_t* keys, void* stream);
+int sr_raster_resolve(const uint64_t* keys, int64_t n, float* depth, int32_t* face, void* stream);
+int sr_raster_visibility_mask(const int32_t* face_bhw, int B, int64_t pixels_per_view, int64_t num_faces,
+                              uint64_t* masks, void* stream);
+int sr_raster_visibility_count(uint64_t* masks, int64_t num_faces, int32_t* counts, int min_views, uint8_t* visible,
+                               void* stream);
+
 /* ------------------------------------------------------ backward (training) -------------
  *
  * Backward of sr_dot_volume_sweep (reference: autograd through CostVolumeManager.build_cost_volume,

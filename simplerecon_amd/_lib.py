@@ -191,6 +191,12 @@ SIGNATURES = {
     "sr_stsdf_integrate": (_i, [_p, _i64, _p, _p, _p, _i64, _p, _p, _p, _i, _i, _i, _f, _f, _p]),
     "sr_stsdf_mesh_count": (_i, [_p, _i64, _p, _p, _i64, _p, _p]),
     "sr_stsdf_mesh_emit": (_i, [_p, _i64, _p, _p, _i64, _f, _p, _i64, _i64, _p, _p, _p, _p, _p]),
+    "sr_raster_small": (_i, [_p, _i64, _p, _i64, _p, _p, _i, _i, _i, _f, _f, _i, _p, _p, _p]),
+    "sr_raster_large_setup": (_i, [_p, _i64, _p, _i64, _p, _p, _i, _i, _i, _f, _f, _i, _i64, _p, _p, _p, _p]),
+    "sr_raster_large": (_i, [_p, _p, _i64, _i64, _p, _i, _i, _i, _f, _f, _p, _p]),
+    "sr_raster_resolve": (_i, [_p, _i64, _p, _p, _p]),
+    "sr_raster_visibility_mask": (_i, [_p, _i, _i64, _i64, _p, _p]),
+    "sr_raster_visibility_count": (_i, [_p, _i64, _p, _i, _p, _p]),
 }
 
 
