@@ -915,6 +915,55 @@ int sr_raster_visibility_mask(const int32_t* face_bhw, int B, int64_t pixels_per
 int sr_raster_visibility_count(uint64_t* masks, int64_t num_faces, int32_t* counts, int min_views, uint8_t* visible,
                                void* stream);
 
+/* ------------------------------------------------------------- frame preparation ----
+ *
+ * What the reference's data loader does to a decoded frame (datasets/generic_mvs_dataset.py get_frame,
+ * utils/generic_utils.py read_image_file): Pillow's Image.resize of the 8-bit colour image, to_tensor + ImageNet
+ * normalisation, and the nearest resize of the 16-bit depth map with its validity masks -- reproduced bit for bit.
+ * simplerecon_amd/frames.py builds the tables on the host (the only place the Pillow rules below are coded);
+ * tests/frames_oracle.py restates the kernels in numpy.
+ *
+ * Colour resize, 8 bits per channel, `in` uint8 [B,h,w,C] interleaved, C in 1..4, every channel on its own (an RGBA
+ * image is NOT premultiplied: Pillow's result for CMYK / RGBX, not for RGBA).  Pillow runs a horizontal pass, rounds
+ * it to uint8, then runs a vertical pass; a pass whose size does not change is skipped (here: an identity table,
+ * one tap of weight 2^22, which copies).  Per output index i of a pass, with scale = in / out, fs = max(scale, 1),
+ * support = filter support * fs and centre = (i + 0.5) * scale: taps first = int(centre - support + 0.5) clamped at 0
+ * to last = int(centre + support + 0.5) clamped at `in`; weight of tap x = filter((x - centre + 0.5) / fs), normalised
+ * by their sum in double, then k = int(w * 2^22 +- 0.5) (sign of w).  Output = clamp((2^21 + sum k * v) >> 22, 0, 255)
+ * in wrapping 32-bit integers.
+ * A table holds out * (2 + taps) int32: per output index [first, count, k_0 .. k_(taps-1)], count <= taps, unused
+ * weights 0.  The kernels trust it: first >= 0 and first + count <= in for every entry.
+ *
+ * sr_frames_resize writes `out` uint8 [B,H,W,C] (f32_out = 0), or fp32 planes [B,C,H,W] = lut[c][value] (f32_out = 1;
+ * lut [C][256]: ((v / 255) - mean_c) / std_c as torch's CPU kernels round it, computed by the caller), columns
+ * mirrored when flip.  lds_rows > 0: ONE launch -- a workgroup owns SR_FRAMES_TILE_H output rows x
+ * SR_FRAMES_TILE_W output columns, resamples horizontally the input rows they tap into LDS (uint8 [lds_rows]
+ * [SR_FRAMES_TILE_W * C]) and vertically from there; lds_rows must be at least the largest number of input rows any
+ * SR_FRAMES_TILE_H consecutive output rows tap (last tap of the last row - first tap of the first), and
+ * sr_frames_resize_fits_lds(C, x_taps, lds_rows, f32_out) must hold (tables and rows within SR_FRAMES_LDS_BYTES).
+ * lds_rows = 0: two launches through `tmp` uint8 [B,h,W,C] (very large downscale factors).  Both give the same bytes.
+ *
+ * sr_frames_depth: `in` [B,h,w] uint16 (in_is_int32 = 0) or int32 with values 0..65535; ysrc [H] / xsrc [W] int32
+ * source indices (Pillow's nearest: floor((i + 0.5) * in / out) in double; the identity for the native size),
+ * trusted to lie inside the input.  d = float(v) * scale in fp32; valid = (d > min_valid) & (d < max_valid) with both
+ * bounds rounded to fp32, as torch compares an fp32 tensor with a Python scalar.  Writes depth [B,1,H,W] (NaN where
+ * invalid), mask (1.0 / 0.0) and mask_b (uint8 1 / 0), columns mirrored when flip.
+ *
+ * All offsets are 64-bit.  SR_ERR_UNSUPPORTED: a side above SR_FRAMES_MAX_SIDE, B above SR_FRAMES_MAX_BATCH, C outside
+ * 1..4, an lds_rows that does not fit.  No call allocates or synchronises with the host. */
+#define SR_FRAMES_TILE_W 128
+#define SR_FRAMES_TILE_H 16
+#define SR_FRAMES_LDS_BYTES 49152
+#define SR_FRAMES_MAX_SIDE 32768
+#define SR_FRAMES_MAX_BATCH 65535
+int sr_frames_resize_fits_lds(int C, int x_taps, int lds_rows, int f32_out);
+int sr_frames_resize(const uint8_t* in, int B, int h, int w, int C, const int32_t* xtab, int x_taps, const int32_t* ytab,
+                     int y_taps, int lds_rows, const float* lut, void* out, int f32_out, int H, int W, int flip,
+                     uint8_t* tmp, void* stream);
+int sr_frames_depth(const void* in, int in_is_int32, int B, int h, int w, const int32_t* ysrc, const int32_t* xsrc, int H,
+                    int W, float scale, float min_valid, float max_valid, int flip, float* depth, float* mask,
+                    uint8_t* mask_b, void* stream);
+
 /* ------------------------------------------------------ backward (training) -------------
  *
  * Backward of sr_dot_volume_sweep (reference: autograd through CostVolumeManager.build_cost_volume,

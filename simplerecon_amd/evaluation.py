@@ -9,7 +9,8 @@ reference's score files and, optionally, fuse the depths into a TSDF and export 
 A frame is what a dataset's __getitem__ returns: dicts with the reference's keys (image_b3hw, full_res_depth_b1hw,
 K_full_depth_b44, cam_T_world_b44, world_T_cam_b44, K_s1_b44, invK_s1_b44, ... for the current frame; the source frames'
 images, poses and intrinsics stacked along a first dimension), without a batch dimension.  `batch_size` frames are
-collated into one batch, as test.py's DataLoader does (drop_last=False)."""
+collated into one batch, as test.py's DataLoader does (drop_last=False).  frames.FramePreparer.tuple makes such frames
+from decoded images."""
 import os
 
 import torch
