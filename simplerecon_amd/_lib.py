@@ -321,6 +321,33 @@ def require_device_f32(name, t, allow_none=False):
         raise TypeError(f"{name} must be float32 (the reference runs inference in fp32), got {t.dtype}")
 
 
+def device_f32(name, t, why=None):
+    """`t` as a contiguous fp32 device tensor, or the refusal.  With `why` (the reason the dtype message gives, such as
+    "the losses run in fp32") the dtype is looked at first: a half / double input is refused as such on any machine."""
+    if why is not None and isinstance(t, torch.Tensor) and t.dtype != torch.float32:
+        raise TypeError(f"{name} must be float32 ({why}), got {t.dtype}")
+    require_device_f32(name, t)
+    return t.contiguous()
+
+
+def data_f32(name, t, role, why=None):
+    """device_f32 for an input that is data, not a parameter (gt maps, intrinsics, poses): no gradient is produced, so
+    asking for one raises, naming the `role`; returns the tensor detached."""
+    t = device_f32(name, t, why)
+    if torch.is_grad_enabled() and t.requires_grad:
+        raise HipLibraryError(f"{name} requires a gradient: {role}")
+    return t.detach()
+
+
+def map_bhw(name, t):
+    """[B,1,h,w] or [B,h,w] -> (B, h, w)."""
+    if t.dim() == 4 and t.shape[1] == 1:
+        return t.shape[0], t.shape[2], t.shape[3]
+    if t.dim() == 3:
+        return tuple(t.shape)
+    raise ValueError(f"{name}: expected a [B,1,h,w] or [B,h,w] map, got {tuple(t.shape)}")
+
+
 def ptr(t):
     """Device address of a tensor for a `void*` / `float*` argument (a plain int: ctypes converts it; None = NULL)."""
     return t.data_ptr() if t is not None else None

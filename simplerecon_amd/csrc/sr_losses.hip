@@ -15,6 +15,7 @@
 // fp64 and writes the loss scalars (and the counts / means the backward needs) to device memory: no float atomics, no
 // host synchronisation, and two runs give the same bits.
 #include "sr_common.h"
+#include "sr_block.h"
 
 #pragma clang fp contract(off)
 
@@ -31,18 +32,6 @@ constexpr int kGradFields = 8;      // (sum, count) per level
 constexpr int kDepthFields = 11;    // ms0..ms3, count, abs, inv, inv count, log l1, sum d, sum d^2
 constexpr int kMVFields = 2 * SR_LOSS_MAX_SOURCES;   // (sum, count) per source
 
-__device__ __forceinline__ float wave_sum(float v) {
-#pragma unroll
-  for (int o = SR_WAVE / 2; o > 0; o >>= 1) v += __shfl_xor(v, o);
-  return v;
-}
-
-__device__ __forceinline__ double wave_sum_d(double v) {
-#pragma unroll
-  for (int o = SR_WAVE / 2; o > 0; o >>= 1) v += __shfl_xor(v, o);
-  return v;
-}
-
 // Every thread of the block calls this with its NF values (zero for idle threads); the block's sums land in
 // partials[block * NF + f], each in the same order on every run.
 template <int NF>
@@ -51,7 +40,7 @@ __device__ __forceinline__ void store_partials(const float (&v)[NF], float* __re
   const int lane = threadIdx.x & (SR_WAVE - 1), wv = threadIdx.x / SR_WAVE;
 #pragma unroll
   for (int f = 0; f < NF; ++f) {
-    const float s = wave_sum(v[f]);
+    const float s = sr_wave_sum(v[f]);
     if (lane == 0) red[wv][f] = s;
   }
   __syncthreads();
@@ -96,7 +85,7 @@ __global__ __launch_bounds__(kT) void sr_loss_finalize_kernel(FinParams p) {
   for (int f = 0; f < p.nf; ++f) {
     double s = 0.0;
     for (int64_t i = threadIdx.x; i < p.nblocks; i += kT) s += (double)p.partials[i * p.stride + f];
-    s = wave_sum_d(s);
+    s = sr_wave_sum(s);
     if (lane == 0) red[wv] = s;
     __syncthreads();
     if (threadIdx.x == 0) {
@@ -684,15 +673,6 @@ struct DepthParams {
   float* glg[4];
 };
 
-// F.interpolate(mode="nearest") source index (ATen's nearest_idx, fp32 scale)
-__device__ __forceinline__ int nn_src(int dst, int in, int out) {
-  if (in == out) return dst;
-  if (out == 2 * in) return dst >> 1;
-  const float scale = (float)in / (float)out;
-  const int s = (int)floorf((float)dst * scale);
-  return s < in - 1 ? s : in - 1;
-}
-
 __global__ __launch_bounds__(kT) void sr_depth_terms_kernel(DepthParams p) {
   const int hw = p.h * p.w;
   const int pix = blockIdx.x * kT + threadIdx.x;
@@ -708,7 +688,7 @@ __global__ __launch_bounds__(kT) void sr_depth_terms_kernel(DepthParams p) {
 #pragma unroll
     for (int i = 0; i < 4; ++i) {
       if (!(p.present >> i & 1)) continue;
-      const int sy = nn_src(y, p.hs[i], p.h), sx = nn_src(x, p.ws[i], p.w);
+      const int sy = sr_nearest_src(y, p.hs[i], p.h), sx = sr_nearest_src(x, p.ws[i], p.w);
       v[i] = __builtin_fabsf(lgt - p.lg[i][((int64_t)b * p.hs[i] + sy) * p.ws[i] + sx]);
     }
     v[4] = 1.0f;
@@ -758,15 +738,15 @@ __global__ __launch_bounds__(kT) void sr_depth_terms_bwd_kernel(DepthParams p) {
   const float lv = L[co];
   // the fine rows / columns whose nearest source is (cy, cx): a contiguous range, the mapping being monotone
   int y0 = (int)((int64_t)cy * p.h / hi);
-  while (y0 > 0 && nn_src(y0 - 1, hi, p.h) >= cy) --y0;
-  while (y0 < p.h && nn_src(y0, hi, p.h) < cy) ++y0;
+  while (y0 > 0 && sr_nearest_src(y0 - 1, hi, p.h) >= cy) --y0;
+  while (y0 < p.h && sr_nearest_src(y0, hi, p.h) < cy) ++y0;
   int x0 = (int)((int64_t)cx * p.w / wi);
-  while (x0 > 0 && nn_src(x0 - 1, wi, p.w) >= cx) --x0;
-  while (x0 < p.w && nn_src(x0, wi, p.w) < cx) ++x0;
+  while (x0 > 0 && sr_nearest_src(x0 - 1, wi, p.w) >= cx) --x0;
+  while (x0 < p.w && sr_nearest_src(x0, wi, p.w) < cx) ++x0;
   float ms = 0.0f, si = 0.0f, l1 = 0.0f;
   const float md = p.stats[7], siv = p.stats[4];
-  for (int y = y0; y < p.h && nn_src(y, hi, p.h) == cy; ++y) {
-    for (int x = x0; x < p.w && nn_src(x, wi, p.w) == cx; ++x) {
+  for (int y = y0; y < p.h && sr_nearest_src(y, hi, p.h) == cy; ++y) {
+    for (int x = x0; x < p.w && sr_nearest_src(x, wi, p.w) == cx; ++x) {
       const int64_t o = (int64_t)b * hw + y * p.w + x;
       if (!p.mask[o]) continue;
       const float lgt = p.gt_is_log ? p.gt[o] : logf(p.gt[o]);

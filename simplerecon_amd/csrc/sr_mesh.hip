@@ -15,6 +15,7 @@
 #include <hip/hip_fp16.h>
 
 #include "sr_common.h"
+#include "sr_block.h"
 #include "sr_mc.h"
 
 // edge parameters, positions and the asymptotic decider are separate fp32 operations, as in the numpy rules
@@ -117,39 +118,19 @@ __device__ __forceinline__ void group_info(const Params& p, int64_t g, int& act,
   }
 }
 
-// Exclusive scan of three counters over the workgroup; returns the workgroup totals.
-__device__ __forceinline__ int3 block_scan3(int3 v, int3& excl) {
-  __shared__ int3 s[kThreads];
-  const int t = threadIdx.x;
-  s[t] = v;
-  __syncthreads();
-#pragma unroll 1
-  for (int d = 1; d < kThreads; d <<= 1) {
-    int3 o = make_int3(0, 0, 0);
-    if (t >= d) o = s[t - d];
-    __syncthreads();
-    if (t >= d) { s[t].x += o.x; s[t].y += o.y; s[t].z += o.z; }
-    __syncthreads();
-  }
-  const int3 incl = s[t];
-  excl = make_int3(incl.x - v.x, incl.y - v.y, incl.z - v.z);
-  const int3 tot = s[kThreads - 1];
-  __syncthreads();
-  return tot;
-}
-
 template <bool VEC>
 __global__ __launch_bounds__(kThreads) void sr_mesh_count_kernel(Params p) {
   const int64_t brick = blockIdx.x;
   int act, nv, nt;
   uint64_t packed;
   group_info<VEC>(p, brick * kThreads + threadIdx.x, act, nv, nt, packed);
-  int3 excl;
-  const int3 tot = block_scan3(make_int3(act, nv, nt), excl);
+  const int v[3] = {act, nv, nt};
+  int excl[3], tot[3];
+  sr_block_scan<3, kThreads>(v, excl, tot);
   if (threadIdx.x == 0) {
-    p.brick_cnt[brick] = tot.x;
-    p.brick_cnt[p.nbricks + brick] = tot.y;
-    p.brick_cnt[2 * p.nbricks + brick] = tot.z;
+    p.brick_cnt[brick] = tot[0];
+    p.brick_cnt[p.nbricks + brick] = tot[1];
+    p.brick_cnt[2 * p.nbricks + brick] = tot[2];
   }
 }
 
@@ -191,12 +172,13 @@ __global__ __launch_bounds__(kThreads) void sr_mesh_compact_kernel(Params p) {
   int act, nv, nt;
   uint64_t packed;
   group_info<VEC>(p, g, act, nv, nt, packed);
-  int3 excl;
-  block_scan3(make_int3(act, nv, nt), excl);
+  const int v[3] = {act, nv, nt};
+  int excl[3], tot[3];
+  sr_block_scan<3, kThreads>(v, excl, tot);
   if (!act) return;
-  int64_t a = p.brick_off[brick] + excl.x;
-  int64_t vo = p.brick_off[p.nbricks + brick] + excl.y;
-  int64_t to = p.brick_off[2 * p.nbricks + brick] + excl.z;
+  int64_t a = p.brick_off[brick] + excl[0];
+  int64_t vo = p.brick_off[p.nbricks + brick] + excl[1];
+  int64_t to = p.brick_off[2 * p.nbricks + brick] + excl[2];
   const int64_t lin0 = g / p.groups_z * p.Z + (g % p.groups_z) * 8;
   for (int m = 0; m < 8; ++m) {
     const int info = (int)((packed >> (7 * m)) & 127), mask = info & 7, ntri = info >> 3;
@@ -209,17 +191,6 @@ __global__ __launch_bounds__(kThreads) void sr_mesh_compact_kernel(Params p) {
     vo += __popc(mask);
     to += ntri;
   }
-}
-
-// Index of `key` in keys[lo, A) (it is there: the owner of a crossing edge is an active voxel), or -1.
-__device__ __forceinline__ int64_t find_key(const Params& p, int64_t lo, int64_t key) {
-  int64_t hi = p.A;
-  while (lo < hi) {
-    const int64_t mid = lo + ((hi - lo) >> 1);
-    if (p.keys[mid] < key) lo = mid + 1;
-    else hi = mid;
-  }
-  return (lo < p.A && p.keys[lo] == key) ? lo : -1;
 }
 
 // Central-difference gradient of the clamped values at voxel (x,y,z); one-sided at the border.
@@ -292,7 +263,8 @@ __global__ __launch_bounds__(kThreads) void sr_mesh_emit_kernel(Params p) {
     vbase[oc] = -1;
     vmask[oc] = 0;
     if (q.cross & owned) {
-      const int64_t m = find_key(p, n + 1, lin + (oc & 1) * yz + ((oc >> 1) & 1) * p.Z + ((oc >> 2) & 1));
+      // (found: the owner of a crossing edge is an active voxel, and it sorts after this one)
+      const int64_t m = sr_find_sorted(p.keys, n + 1, p.A, lin + (oc & 1) * yz + ((oc >> 1) & 1) * p.Z + ((oc >> 2) & 1));
       if (m >= 0) {
         const int4 o = p.meta[m];
         vbase[oc] = o.x;

@@ -21,6 +21,7 @@
 #include <math.h>
 
 #include "sr_common.h"
+#include "sr_block.h"
 
 // every product and sum below is rounded on its own; nothing may be contracted into an FMA
 #pragma clang fp contract(off)
@@ -374,12 +375,6 @@ __global__ __launch_bounds__(kT) void sr_sample_kernel(const float* __restrict__
 constexpr int kPerThread = 16;
 constexpr int kBlockItems = kT * kPerThread;
 
-__device__ __forceinline__ double wave_sum_d(double v) {
-#pragma unroll
-  for (int o = SR_WAVE / 2; o > 0; o >>= 1) v += __shfl_xor(v, o);
-  return v;
-}
-
 __global__ __launch_bounds__(kT) void sr_mm_partial_kernel(const float* __restrict__ d_pred, int64_t m,
                                                            const float* __restrict__ d_gt, int64_t n, int64_t blocks_pred,
                                                            float thr, double* __restrict__ rec) {
@@ -397,8 +392,8 @@ __global__ __launch_bounds__(kT) void sr_mm_partial_kernel(const float* __restri
       c += x < thr ? 1.0 : 0.0;
     }
   }
-  s = wave_sum_d(s);
-  c = wave_sum_d(c);
+  s = sr_wave_sum(s);
+  c = sr_wave_sum(c);
   __shared__ double red[kWaves][2];
   const int lane = threadIdx.x & (SR_WAVE - 1), wv = threadIdx.x / SR_WAVE;
   if (lane == 0) { red[wv][0] = s; red[wv][1] = c; }
@@ -424,7 +419,7 @@ __global__ __launch_bounds__(kT) void sr_mm_finalize_kernel(const double* __rest
   const int lane = threadIdx.x & (SR_WAVE - 1), wv = threadIdx.x / SR_WAVE;
 #pragma unroll
   for (int k = 0; k < 4; ++k) {
-    const double t = wave_sum_d(a[k]);
+    const double t = sr_wave_sum(a[k]);
     if (lane == 0) red[wv][k] = t;
   }
   __syncthreads();

@@ -16,6 +16,7 @@
 #include <math.h>
 
 #include "sr_common.h"
+#include "sr_block.h"
 
 #pragma clang fp contract(off)
 
@@ -44,26 +45,10 @@ struct MetricParams {
   double* records;        // [B, tiles, kFields]
 };
 
-// F.interpolate(mode="nearest") source index along one axis (ATen's identity and exact-2x cases, else
-// min(floor(dst * (in / out)), in - 1) in fp32).
-__device__ __forceinline__ int nearest_src(int dst, int in, int out) {
-  if (in == out) return dst;
-  if (out == 2 * in) return dst >> 1;
-  const float scale = (float)in / (float)out;
-  const int s = (int)floorf((float)dst * scale);
-  return s < in - 1 ? s : in - 1;
-}
-
 __device__ __forceinline__ int gather_index(const MetricParams& p, int pix) {
   if (!p.nearest) return pix;
   const int y = pix / p.W, x = pix - y * p.W;
-  return nearest_src(y, p.h, p.H) * p.w + nearest_src(x, p.w, p.W);
-}
-
-__device__ __forceinline__ double wave_sum_d(double v) {
-#pragma unroll
-  for (int o = SR_WAVE / 2; o > 0; o >>= 1) v += __shfl_xor(v, o);
-  return v;
+  return sr_nearest_src(y, p.h, p.H) * p.w + sr_nearest_src(x, p.w, p.W);
 }
 
 // One valid pixel's contribution, in the reference's operation order (fp32 terms, fp64 sums).
@@ -140,7 +125,7 @@ __global__ __launch_bounds__(kT) void sr_metrics_tile_kernel(MetricParams p) {
   const int lane = threadIdx.x & (SR_WAVE - 1), wv = threadIdx.x / SR_WAVE;
 #pragma unroll
   for (int f = 0; f < kFields; ++f) {
-    const double t = wave_sum_d(acc[f]);
+    const double t = sr_wave_sum(acc[f]);
     if (lane == 0) red[wv][f] = t;
   }
   __syncthreads();

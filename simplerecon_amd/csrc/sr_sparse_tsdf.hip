@@ -12,6 +12,7 @@
 // weight is 0 or the block is missing) in LDS; one pass counts vertices and faces per block, a second writes vertices,
 // colours and the vertex table, a third the faces (a face's vertices may belong to a neighbour block).
 #include "sr_common.h"
+#include "sr_block.h"
 #include "sr_mc.h"
 
 #pragma clang fp contract(off)
@@ -209,37 +210,6 @@ struct MeshParams {
   int32_t* faces;
 };
 
-// Sorted index of `key` in keys[0, n), or -1.
-__device__ __forceinline__ int64_t find_block(const MeshParams& p, int64_t key) {
-  int64_t lo = 0, hi = p.n;
-  while (lo < hi) {
-    const int64_t mid = lo + ((hi - lo) >> 1);
-    if (p.keys[mid] < key) lo = mid + 1;
-    else hi = mid;
-  }
-  return (lo < p.n && p.keys[lo] == key) ? lo : -1;
-}
-
-// Exclusive scan of two counters over the workgroup.
-__device__ __forceinline__ int2 block_scan2(int2 v, int2& total) {
-  __shared__ int2 s[kThreads];
-  const int t = threadIdx.x;
-  s[t] = v;
-  __syncthreads();
-#pragma unroll 1
-  for (int d = 1; d < kThreads; d <<= 1) {
-    int2 o = make_int2(0, 0);
-    if (t >= d) o = s[t - d];
-    __syncthreads();
-    if (t >= d) { s[t].x += o.x; s[t].y += o.y; }
-    __syncthreads();
-  }
-  const int2 incl = s[t];
-  total = s[kThreads - 1];
-  __syncthreads();
-  return make_int2(incl.x - v.x, incl.y - v.y);
-}
-
 __device__ __forceinline__ float halo(const float* hv, int x, int y, int z) { return hv[(x * kHalo + y) * kHalo + z]; }
 
 template <int PASS>
@@ -255,7 +225,7 @@ __global__ __launch_bounds__(kThreads) void sr_stsdf_mesh_kernel(MeshParams p) {
     int64_t idx = -1;
     if (t == 0) idx = n;
     else if (key_in_range(bx + dx) && key_in_range(by + dy) && key_in_range(bz + dz))
-      idx = find_block(p, pack_key(bx + dx, by + dy, bz + dz));
+      idx = sr_find_sorted(p.keys, 0, p.n, pack_key(bx + dx, by + dy, bz + dz));
     nb_idx[t] = idx;
     nb_slot[t] = idx < 0 ? -1 : p.slots[idx];
   }
@@ -289,17 +259,18 @@ __global__ __launch_bounds__(kThreads) void sr_stsdf_mesh_kernel(MeshParams p) {
     nv += __popc(mask);
     nt += ntri;
   }
-  int2 total;
-  const int2 excl = block_scan2(make_int2(nv, nt), total);
+  const int cnt[2] = {nv, nt};
+  int excl[2], total[2];
+  sr_block_scan<2, kThreads>(cnt, excl, total);
   if (PASS == kCount) {
     if (t == 0) {
-      p.counts[n] = total.x;
-      p.counts[p.n + n] = total.y;
+      p.counts[n] = total[0];
+      p.counts[p.n + n] = total[1];
     }
     return;
   }
   if (PASS == kVertices) {
-    int64_t vi = p.offsets[n] + excl.x;
+    int64_t vi = p.offsets[n] + excl[0];
 #pragma unroll 1
     for (int m = 0; m < 16; ++m) {
       const int mask = (int)(info[m >> 2] >> (8 * (m & 3))) & 7;
@@ -333,7 +304,7 @@ __global__ __launch_bounds__(kThreads) void sr_stsdf_mesh_kernel(MeshParams p) {
     return;
   }
   // PASS == kFaces: every vertex table of this block and its neighbours was written by the previous launch
-  int64_t fi = p.offsets[p.n + n] + excl.y;
+  int64_t fi = p.offsets[p.n + n] + excl[1];
 #pragma unroll 1
   for (int m = 0; m < 16; ++m) {
     const int ntri = (int)(info[m >> 2] >> (8 * (m & 3) + 3)) & 31;

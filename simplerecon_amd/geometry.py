@@ -11,23 +11,14 @@ from torch import nn
 from . import _lib
 
 
+# intrinsics / poses: data on this path (the reference does not optimise them either) -- no gradient is produced
+_CAMERAS = "cameras are data for the HIP geometry helpers"
+
+
 def _f32c(name, t):
-    _lib.require_device_f32(name, t)
+    t = _lib.device_f32(name, t)
     _lib.refuse_autograd(t)
-    return t.contiguous()
-
-
-def _data(name, t):
-    """Intrinsics / poses: data on this path (the reference does not optimise them either) -- no gradient is produced."""
-    _lib.require_device_f32(name, t)
-    if torch.is_grad_enabled() and t.requires_grad:
-        raise _lib.HipLibraryError(f"{name} requires a gradient: cameras are data for the HIP geometry helpers")
-    return t.detach().contiguous()
-
-
-def _diff(name, t):
-    _lib.require_device_f32(name, t)
-    return t.contiguous()
+    return t
 
 
 class _Backproject(torch.autograd.Function):
@@ -86,7 +77,7 @@ class BackprojectDepth(nn.Module):
 
     def forward(self, depth_b1hw, invK_b44):
         """depth [B,1,h,w], invK [B,4,4] -> homogeneous camera points [B,4,h*w] (reference geometry_utils.py:51-59)."""
-        depth, invK = _diff("depth_b1hw", depth_b1hw), _data("invK_b44", invK_b44)
+        depth, invK = _lib.device_f32("depth_b1hw", depth_b1hw), _lib.data_f32("invK_b44", invK_b44, _CAMERAS)
         b = depth.shape[0]
         if tuple(depth.shape[-2:]) != (self.height, self.width) or depth.numel() != b * self.height * self.width:
             raise ValueError(f"depth map {tuple(depth.shape)} does not match {self.height}x{self.width}")
@@ -103,7 +94,8 @@ class Project3D(nn.Module):
 
     def forward(self, points_b4N, K_b44, cam_T_world_b44):
         """points [B,4,N] -> [B,3,N] = (pixel x, pixel y, depth + eps) (reference geometry_utils.py:72-89)."""
-        pts, K, T = _diff("points_b4N", points_b4N), _data("K_b44", K_b44), _data("cam_T_world_b44", cam_T_world_b44)
+        pts = _lib.device_f32("points_b4N", points_b4N)
+        K, T = _lib.data_f32("K_b44", K_b44, _CAMERAS), _lib.data_f32("cam_T_world_b44", cam_T_world_b44, _CAMERAS)
         b, four, n = pts.shape
         if four != 4 or tuple(K.shape) != (b, 4, 4) or tuple(T.shape) != (b, 4, 4):
             raise ValueError("expected points [B,4,N], K [B,4,4], cam_T_world [B,4,4]")

@@ -15,25 +15,15 @@ MAX_SOURCES = 15   # SR_LOSS_MAX_SOURCES
 PROJECT_EPS = 1e-8   # Project3D's eps
 
 
-def _f32(name, t):
-    """dtype first, then device: a half / double input is refused as such on any machine."""
-    if isinstance(t, torch.Tensor) and t.dtype != torch.float32:
-        raise TypeError(f"{name} must be float32 (the losses run in fp32), got {t.dtype}")
-    _lib.require_device_f32(name, t)
+_FP32 = "the losses run in fp32"
+_DATA = "it is data for the training losses"
 
 
 def _dev(name, t, min_hw=3):
-    _f32(name, t)
+    t = _lib.device_f32(name, t, _FP32)
     if t.dim() < 2 or t.shape[-1] < min_hw or t.shape[-2] < min_hw:
         raise ValueError(f"{name} {tuple(t.shape)}: the losses need maps of at least {min_hw}x{min_hw}")
-    return t.contiguous()
-
-
-def _data(name, t):
-    _f32(name, t)
-    if torch.is_grad_enabled() and t.requires_grad:
-        raise _lib.HipLibraryError(f"{name} requires a gradient: it is data for the training losses")
-    return t.detach().contiguous()
+    return t
 
 
 def _mask(name, t):
@@ -50,18 +40,11 @@ def _ws(nbytes, device, what):
     return torch.empty(int(nbytes), dtype=torch.uint8, device=device)
 
 
-def _bhw(t):
-    """[B,1,h,w] or [B,h,w] -> (B, h, w)."""
-    if t.dim() == 4 and t.shape[1] != 1:
-        raise ValueError(f"expected a one-channel map, got {tuple(t.shape)}")
-    return t.shape[0], t.shape[-2], t.shape[-1]
-
-
 # ------------------------------------------------------------------------------------------------ normals -----------
 class _Normals(torch.autograd.Function):
     @staticmethod
     def forward(ctx, depth, invK):
-        B, h, w = _bhw(depth)
+        B, h, w = _lib.map_bhw("depth", depth)
         dev = depth.device
         ws = _ws(_lib.lib().sr_normals_workspace_bytes(B, h, w), dev, "normals")
         out = torch.empty((B, 3, h, w), dtype=torch.float32, device=dev)
@@ -72,7 +55,7 @@ class _Normals(torch.autograd.Function):
     @staticmethod
     def backward(ctx, g):
         depth, invK = ctx.saved_tensors
-        B, h, w = _bhw(depth)
+        B, h, w = _lib.map_bhw("depth", depth)
         dev = depth.device
         g = g.contiguous()
         ws = _ws(_lib.lib().sr_normals_workspace_bytes(B, h, w), dev, "normals")
@@ -84,7 +67,7 @@ class _Normals(torch.autograd.Function):
 def normals_from_depth(depth_b1hw, invK_b44):
     """NormalGenerator(h, w)(depth, invK) with the reference's 5x5 / std 2 blur: [B,3,h,w]."""
     depth = _dev("depth_b1hw", depth_b1hw)
-    invK = _data("invK_b44", invK_b44)
+    invK = _lib.data_f32("invK_b44", invK_b44, _DATA, _FP32)
     if tuple(invK.shape) != (depth.shape[0], 4, 4):
         raise ValueError("expected invK [B,4,4]")
     return _Normals.apply(depth, invK)
@@ -115,7 +98,7 @@ class NormalsLoss(nn.Module):
     """Reference losses.py:57-77: the masked mean of 0.5 (1 - n_pred . n_gt) over the pixels where both are finite."""
 
     def forward(self, normals_gt_b3hw, normals_pred_b3hw):
-        ngt = _data("normals_gt_b3hw", normals_gt_b3hw)
+        ngt = _lib.data_f32("normals_gt_b3hw", normals_gt_b3hw, _DATA, _FP32)
         npred = _dev("normals_pred_b3hw", normals_pred_b3hw)
         if npred.dim() != 4 or npred.shape[1] != 3 or ngt.shape != npred.shape:
             raise ValueError("expected normals [B,3,h,w] of equal shape")
@@ -126,7 +109,7 @@ class NormalsLoss(nn.Module):
 class _GradLoss(torch.autograd.Function):
     @staticmethod
     def forward(ctx, gt, pred):
-        B, h, w = _bhw(pred)
+        B, h, w = _lib.map_bhw("pred", pred)
         dev = pred.device
         ws = _ws(_lib.lib().sr_grad_loss_workspace_bytes(B, h, w), dev, "gradient loss")
         out = torch.empty(5, dtype=torch.float32, device=dev)
@@ -138,7 +121,7 @@ class _GradLoss(torch.autograd.Function):
     @staticmethod
     def backward(ctx, g):
         gt, pred, stats = ctx.saved_tensors
-        B, h, w = _bhw(pred)
+        B, h, w = _lib.map_bhw("pred", pred)
         g = g.contiguous()
         gp = torch.empty_like(pred)
         ws = ctx.ws
@@ -157,28 +140,29 @@ class MSGradientLoss(nn.Module):
         self.num_scales = num_scales
 
     def forward(self, depth_gt, depth_pred):
-        gt = _data("depth_gt", depth_gt)
+        gt = _lib.data_f32("depth_gt", depth_gt, _DATA, _FP32)
         pred = _dev("depth_pred", depth_pred)
         if gt.shape != pred.shape:
             raise ValueError("depth_gt and depth_pred differ in shape")
-        _bhw(pred)
+        _lib.map_bhw("depth_pred", pred)
         return _GradLoss.apply(gt, pred)[0]
 
 
 # ------------------------------------------------------------------------------------------- multi-view -------------
 def _mv_args(cur_depth, src_depth, cur_invK, src_K, cur_world_T_cam, src_cam_T_world, height, width):
-    gt = _data("cur_depth_b1hw", cur_depth)
-    B, h, w = _bhw(gt)
+    gt = _lib.data_f32("cur_depth_b1hw", cur_depth, _DATA, _FP32)
+    B, h, w = _lib.map_bhw("cur_depth_b1hw", gt)
     if (h, w) != (height, width) or h < 3 or w < 3:
         raise ValueError(f"depth {tuple(gt.shape)} does not match {height}x{width}")
-    src = _data("src_depth", src_depth)
+    src = _lib.data_f32("src_depth", src_depth, _DATA, _FP32)
     K = src.shape[1] if src.dim() == 5 else 1
     if not 1 <= K <= MAX_SOURCES:
         raise ValueError(f"{K} source views: the multi-view loss takes 1..{MAX_SOURCES}")
     if src.numel() != B * K * h * w:
         raise ValueError("source depths do not match the current depth map")
-    mats = [_data("cur_invK_b44", cur_invK), _data("src_K", src_K), _data("cur_world_T_cam_b44", cur_world_T_cam),
-            _data("src_cam_T_world", src_cam_T_world)]
+    mats = [_lib.data_f32(n, m, _DATA, _FP32) for n, m in (("cur_invK_b44", cur_invK), ("src_K", src_K),
+                                                           ("cur_world_T_cam_b44", cur_world_T_cam),
+                                                           ("src_cam_T_world", src_cam_T_world))]
     for m, n in zip(mats, (B, B * K, B, B * K)):
         if m.numel() != n * 16:
             raise ValueError("expected [B,4,4] current and [B,K,4,4] source matrices")
@@ -188,7 +172,7 @@ def _mv_args(cur_depth, src_depth, cur_invK, src_K, cur_world_T_cam, src_cam_T_w
 class _MVLoss(torch.autograd.Function):
     @staticmethod
     def forward(ctx, pred, gt, src, invK, srcK, wTc, cTw, K):
-        B, h, w = _bhw(pred)
+        B, h, w = _lib.map_bhw("pred", pred)
         dev = pred.device
         ws = _ws(_lib.lib().sr_mv_loss_workspace_bytes(B, K, h, w), dev, "multi-view loss")
         out = torch.empty(1 + 2 * K, dtype=torch.float32, device=dev)
@@ -201,7 +185,7 @@ class _MVLoss(torch.autograd.Function):
     @staticmethod
     def backward(ctx, g):
         pred, gt, src, invK, srcK, wTc, cTw, stats = ctx.saved_tensors
-        B, h, w = _bhw(pred)
+        B, h, w = _lib.map_bhw("pred", pred)
         g = g.contiguous()
         gp = torch.empty_like(pred)
         _lib.call("sr_mv_loss_bwd", pred.device, g, stats, pred, gt, src, invK, srcK, wTc, cTw, B, ctx.K, h, w, PROJECT_EPS,
@@ -263,7 +247,7 @@ DEPTH_TERMS = ("ms_loss", "abs_loss", "inv_abs_loss", "log_l1_loss", "si_loss")
 class _DepthTerms(torch.autograd.Function):
     @staticmethod
     def forward(ctx, gt, mask, pred, si_lambda, gt_is_log, l0, l1, l2, l3):
-        B, h, w = _bhw(gt)
+        B, h, w = _lib.map_bhw("gt", gt)
         dev = gt.device
         logs = [l0, l1, l2, l3]
         dims = []
@@ -282,7 +266,7 @@ class _DepthTerms(torch.autograd.Function):
     def backward(ctx, g):
         gt, mask, pred, stats, *logs = ctx.saved_tensors
         logs = [t if p else None for t, p in zip(logs, ctx.present)]
-        B, h, w = _bhw(gt)
+        B, h, w = _lib.map_bhw("gt", gt)
         dev = gt.device
         g = g.contiguous()
         gpred = torch.empty_like(pred)
@@ -298,8 +282,8 @@ class _DepthTerms(torch.autograd.Function):
 def depth_terms(depth_gt, mask_b, depth_pred, log_depth_preds, si_lambda=0.85):
     """compute_losses' depth terms (reference depth_model.py:447-479) in one launch + finalize: a dict of the five
     scalars of DEPTH_TERMS.  `log_depth_preds`: {scale i: log_depth_pred_s{i}_b1hw}; scale 0 must be at gt size."""
-    gt = _data("depth_b1hw", depth_gt)
-    B, h, w = _bhw(gt)
+    gt = _lib.data_f32("depth_b1hw", depth_gt, _DATA, _FP32)
+    B, h, w = _lib.map_bhw("depth_b1hw", gt)
     mask = _mask("mask_b_b1hw", mask_b)
     pred = _dev("depth_pred_s0_b1hw", depth_pred, 1)
     if not log_depth_preds:
@@ -326,8 +310,8 @@ class ScaleInvariantLoss(nn.Module):
         self.si_lambda = si_lambda
 
     def forward(self, log_depth_gt, log_depth_pred):
-        lgt = _data("log_depth_gt", log_depth_gt)
-        _f32("log_depth_pred", log_depth_pred)
+        lgt = _lib.data_f32("log_depth_gt", log_depth_gt, _DATA, _FP32)
+        _lib.device_f32("log_depth_pred", log_depth_pred, _FP32)
         if lgt.shape != log_depth_pred.shape or lgt.numel() == 0:
             raise ValueError("log_depth_gt and log_depth_pred must have the same, non-empty shape")
         n = lgt.numel()

@@ -21,12 +21,7 @@ RESAMPLE_IDENTITY, RESAMPLE_NEAREST = 0, 1   # SR_RESAMPLE_*
 MAX_PIXELS = 1 << 24                          # SR_METRICS_MAX_PIXELS
 
 
-def _f32(name, t):
-    """dtype first, then device: a half / double input is refused as such on any machine."""
-    if isinstance(t, torch.Tensor) and t.dtype != torch.float32:
-        raise TypeError(f"{name} must be float32 (the metrics run in fp32), got {t.dtype}")
-    _lib.require_device_f32(name, t)
-    return t.detach().contiguous()
+_FP32 = "the metrics run in fp32"
 
 
 def _mask(name, t, like):
@@ -39,15 +34,6 @@ def _mask(name, t, like):
     if t.numel() != like.numel():
         raise ValueError(f"{name} {tuple(t.shape)} does not cover the ground truth {tuple(like.shape)}")
     return t.detach().contiguous().view(torch.uint8)
-
-
-def _bhw(name, t):
-    """[B,1,h,w] or [B,h,w] -> (B, h, w)."""
-    if t.dim() == 4 and t.shape[1] == 1:
-        return t.shape[0], t.shape[2], t.shape[3]
-    if t.dim() == 3:
-        return tuple(t.shape)
-    raise ValueError(f"{name}: expected a [B,1,h,w] or [B,h,w] map, got {tuple(t.shape)}")
 
 
 def _run(gt, pred, mask, min_depth, B, H, W, h, w, resample, mult_a, pooled):
@@ -85,10 +71,10 @@ def _as_dict(values):
 def score_block(depth_gt_b1HW, depth_pred_b1hw, min_depth=0.5, mask_b1HW=None, mult_a=True):
     """score_frames() as one flat device buffer of B*13 fp32 words (split_block() takes it apart), so that a single
     device-to-host copy brings the metrics and the valid counts of a batch to the host."""
-    gt = _f32("depth_gt_b1HW", depth_gt_b1HW)
-    pred = _f32("depth_pred_b1hw", depth_pred_b1hw)
-    B, H, W = _bhw("depth_gt_b1HW", gt)
-    Bp, h, w = _bhw("depth_pred_b1hw", pred)
+    gt = _lib.device_f32("depth_gt_b1HW", depth_gt_b1HW, _FP32).detach()
+    pred = _lib.device_f32("depth_pred_b1hw", depth_pred_b1hw, _FP32).detach()
+    B, H, W = _lib.map_bhw("depth_gt_b1HW", gt)
+    Bp, h, w = _lib.map_bhw("depth_pred_b1hw", pred)
     if Bp != B:
         raise ValueError(f"batch sizes differ: gt {B}, pred {Bp}")
     mask = None if mask_b1HW is None else _mask("mask_b1HW", mask_b1HW, gt)
@@ -110,8 +96,8 @@ def score_frames(depth_gt_b1HW, depth_pred_b1hw, min_depth=0.5, mask_b1HW=None, 
 def compute_depth_metrics_batched(gt_bN, pred_bN, valid_masks_bN, mult_a=False):
     """The reference's batched rule (metrics_utils.py compute_depth_metrics_batched) on [B,N] maps: a dict of [B]
     tensors.  Invalid pixels are dropped, each error metric is a nanmean, the a-metrics divide by the valid count."""
-    gt = _f32("gt_bN", gt_bN)
-    pred = _f32("pred_bN", pred_bN)
+    gt = _lib.device_f32("gt_bN", gt_bN, _FP32).detach()
+    pred = _lib.device_f32("pred_bN", pred_bN, _FP32).detach()
     if gt.dim() != 2 or pred.shape != gt.shape:
         raise ValueError(f"expected gt_bN and pred_bN of one [B,N] shape, got {tuple(gt.shape)}, {tuple(pred.shape)}")
     mask = _mask("valid_masks_bN", valid_masks_bN, gt)
@@ -122,8 +108,8 @@ def compute_depth_metrics_batched(gt_bN, pred_bN, valid_masks_bN, mult_a=False):
 def masked_depth_metrics(gt, pred, mask, mult_a=False):
     """compute_depth_metrics(gt[mask], pred[mask], mult_a) without materialising the selection: gt, pred and mask of
     one shape; a dict of 0-dim tensors."""
-    gt = _f32("gt", gt)
-    pred = _f32("pred", pred)
+    gt = _lib.device_f32("gt", gt, _FP32).detach()
+    pred = _lib.device_f32("pred", pred, _FP32).detach()
     if pred.shape != gt.shape:
         raise ValueError(f"gt {tuple(gt.shape)} and pred {tuple(pred.shape)} differ")
     mask = _mask("mask", mask, gt)
@@ -138,7 +124,7 @@ def compute_depth_metrics(gt, pred, mult_a=False):
     """The reference's pooled rule (metrics_utils.py compute_depth_metrics) over every element of gt / pred (the
     reference calls it on masked selections): plain means, so a NaN term makes its metric NaN.  A dict of 0-dim
     tensors."""
-    gt = _f32("gt", gt)
+    gt = _lib.device_f32("gt", gt, _FP32).detach()
     ones = torch.ones(gt.shape, dtype=torch.uint8, device=gt.device)
     return masked_depth_metrics(gt, pred, ones, mult_a)
 
@@ -234,8 +220,8 @@ class ResultsAverager:
 def _gather(pred_b1hw, H, W):
     """Tests only: the prediction read through the kernels' nearest index map at H x W ([B,H,W]), i.e. what
     F.interpolate(mode="nearest") gives."""
-    pred = _f32("pred_b1hw", pred_b1hw)
-    B, h, w = _bhw("pred_b1hw", pred)
+    pred = _lib.device_f32("pred_b1hw", pred_b1hw, _FP32).detach()
+    B, h, w = _lib.map_bhw("pred_b1hw", pred)
     out = torch.empty((B, H, W), dtype=torch.float32, device=pred.device)
     _lib.call("sr_depth_metrics_gather", pred.device, pred, B, H, W, h, w, RESAMPLE_NEAREST, out)
     return out

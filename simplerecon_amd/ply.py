@@ -1,7 +1,9 @@
-"""PLY reader for ground-truth meshes and point clouds (host, numpy).
+"""PLY reader for ground-truth meshes and point clouds, and the writer behind TriangleMesh.write_ply and
+PointCloud.write_ply (host, numpy).
 
     read_ply(path) -> tsdf.TriangleMesh      when the file has a face element
                    -> point_cloud.PointCloud otherwise
+    write_ply(path, columns, faces=None)     binary little-endian: per-vertex columns, optional triangles
 
 Reads `binary_little_endian` and `ascii` files.  Vertex properties may have any scalar type: `x, y, z` are kept as fp32
 and `red, green, blue` as uint8 for point clouds, as fp32 in [0, 1] (integer values / 255) for meshes; every other property (ScanNet's `alpha`, normals, ...) is skipped.
@@ -19,6 +21,30 @@ _SCALARS = {
     "int": "i4", "int32": "i4", "uint": "u4", "uint32": "u4",
     "float": "f4", "float32": "f4", "double": "f8", "float64": "f8",
 }
+_NAMES = {"i1": "char", "u1": "uchar", "i2": "short", "u2": "ushort", "i4": "int", "u4": "uint", "f4": "float",
+          "f8": "double"}
+
+
+def write_ply(path, columns, faces=None):
+    """Writes a binary little-endian PLY.  `columns` is the ordered list of per-vertex properties as (name, dtype, [V]
+    array) with a little-endian numpy scalar dtype ("<f4", "u1", ...); `faces`, when given (an empty array included),
+    is [F,3] int32 and becomes a `list uchar int vertex_indices` face element -- the layout trimesh writes."""
+    n = len(columns[0][2])
+    vrec = np.empty(n, dtype=[(name, dt) for name, dt, _ in columns])
+    for name, _, values in columns:
+        vrec[name] = values
+    header = ["ply", "format binary_little_endian 1.0", f"element vertex {n}"]
+    header += [f"property {_NAMES[np.dtype(dt).str[1:]]} {name}" for name, dt, _ in columns]
+    body = vrec.tobytes()
+    if faces is not None:
+        frec = np.empty(len(faces), dtype=[("n", "u1"), ("i", "<i4", (3,))])
+        frec["n"] = 3
+        frec["i"] = faces
+        header += [f"element face {len(faces)}", "property list uchar int vertex_indices"]
+        body += frec.tobytes()
+    with open(path, "wb") as fh:
+        fh.write(("\n".join(header + ["end_header"]) + "\n").encode("ascii"))
+        fh.write(body)
 
 
 class _Element:

@@ -13,7 +13,7 @@ import numpy as np
 import torch
 import torch.nn.functional as F
 
-from . import _lib
+from . import _lib, ply
 
 SCRATCH_BYTES = 1 << 30   # per-chunk output of the consistency kernel (points + counts), about 1 GB by default
 _FRAME_BYTES_PER_PIXEL = 16
@@ -76,22 +76,11 @@ class PointCloud:
     def write_ply(self, path):
         """Binary little-endian PLY: `float x,y,z` and, with colours, `uchar red,green,blue` per vertex."""
         v = self.points.detach().cpu().numpy().astype("<f4", copy=False).reshape(-1, 3)
-        fields = [("x", "<f4"), ("y", "<f4"), ("z", "<f4")]
-        if self.colors is not None:
-            fields += [("red", "u1"), ("green", "u1"), ("blue", "u1")]
-        rec = np.empty(len(v), dtype=fields)
-        for i, n in enumerate("xyz"):
-            rec[n] = v[:, i]
+        columns = [(n, "<f4", v[:, i]) for i, n in enumerate("xyz")]
         if self.colors is not None:
             c = self.colors.detach().cpu().numpy().reshape(-1, 3)
-            for i, n in enumerate(("red", "green", "blue")):
-                rec[n] = c[:, i]
-        header = ["ply", "format binary_little_endian 1.0", f"element vertex {len(v)}"]
-        header += [f"property {'float' if t == '<f4' else 'uchar'} {n}" for n, t in fields]
-        header += ["end_header"]
-        with open(path, "wb") as fh:
-            fh.write(("\n".join(header) + "\n").encode("ascii"))
-            fh.write(rec.tobytes())
+            columns += [(n, "u1", c[:, i]) for i, n in enumerate(("red", "green", "blue"))]
+        ply.write_ply(path, columns)
 
 
 def frame_constants(cam_T_world, K):

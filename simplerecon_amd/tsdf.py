@@ -23,7 +23,7 @@ from typing import Optional, Tuple
 import numpy as np
 import torch
 
-from . import _lib
+from . import _lib, ply
 
 
 class TriangleMesh:
@@ -46,36 +46,15 @@ class TriangleMesh:
         """Binary little-endian PLY: `float x,y,z` (+ `nx,ny,nz`) (+ `uchar red,green,blue`, clamp(floor(c * 255 + 0.5))
         of the [0, 1] colours) per vertex and a `list uchar int vertex_indices` face element -- the layout trimesh
         writes."""
-        v = self.vertices.detach().cpu().numpy().astype("<f4", copy=False).reshape(-1, 3)
-        f = self.faces.detach().cpu().numpy().astype("<i4", copy=False).reshape(-1, 3)
-        names = ["x", "y", "z"]
-        cols = [v]
+        def f32(t):
+            return t.detach().cpu().numpy().astype("<f4", copy=False).reshape(-1, 3)
+        columns = [(n, "<f4", f32(self.vertices)[:, i]) for i, n in enumerate("xyz")]
         if self.normals is not None:
-            names += ["nx", "ny", "nz"]
-            cols.append(self.normals.detach().cpu().numpy().astype("<f4", copy=False).reshape(-1, 3))
-        fields = [(n, "<f4") for n in names]
+            columns += [(n, "<f4", f32(self.normals)[:, i]) for i, n in enumerate(("nx", "ny", "nz"))]
         if self.colors is not None:
-            fields += [(n, "u1") for n in ("red", "green", "blue")]
-        vrec = np.empty(len(v), dtype=fields)
-        for idx, n in enumerate(names):
-            vrec[n] = cols[idx // 3][:, idx % 3]
-        if self.colors is not None:
-            c = self.colors.detach().cpu().numpy().astype(np.float32, copy=False).reshape(-1, 3)
-            c8 = np.clip(np.floor(c * np.float32(255) + np.float32(0.5)), 0, 255).astype(np.uint8)
-            for idx, n in enumerate(("red", "green", "blue")):
-                vrec[n] = c8[:, idx]
-        frec = np.empty(len(f), dtype=[("n", "u1"), ("i", "<i4", (3,))])
-        frec["n"] = 3
-        frec["i"] = f
-        header = ["ply", "format binary_little_endian 1.0", f"element vertex {len(v)}"]
-        header += [f"property float {n}" for n in names]
-        if self.colors is not None:
-            header += [f"property uchar {n}" for n in ("red", "green", "blue")]
-        header += [f"element face {len(f)}", "property list uchar int vertex_indices", "end_header"]
-        with open(path, "wb") as fh:
-            fh.write(("\n".join(header) + "\n").encode("ascii"))
-            fh.write(vrec.tobytes())
-            fh.write(frec.tobytes())
+            c8 = np.clip(np.floor(f32(self.colors) * np.float32(255) + np.float32(0.5)), 0, 255).astype(np.uint8)
+            columns += [(n, "u1", c8[:, i]) for i, n in enumerate(("red", "green", "blue"))]
+        ply.write_ply(path, columns, self.faces.detach().cpu().numpy().astype("<i4", copy=False).reshape(-1, 3))
 
 
 def marching_cubes(tsdf_values: torch.Tensor, level=0.0, origin=(0.0, 0.0, 0.0), scale=1.0,

@@ -27,6 +27,58 @@ def test_library_is_built_and_exports_every_declared_symbol():
     assert sorted(_lib.SIGNATURES) == declared, "binding lists symbols the header does not declare"
 
 
+def _declared_prototypes():
+    """name -> (return type, [parameter types]) of every prototype in the header, as C type strings without the
+    parameter names (`const float*`, `int64_t`, ...)."""
+    src = open(os.path.join(ROOT, "include", "simplerecon_hip.h")).read()
+    src = re.sub(r"/\*.*?\*/", " ", src, flags=re.S)
+    src = re.sub(r"//[^\n]*|^\s*#[^\n]*", " ", src, flags=re.M)
+
+    def ctype(text, named):
+        text = re.sub(r"\s*\*\s*", "* ", " ".join(text.split())).strip()
+        if named and not text.endswith("*"):
+            text = text.rsplit(" ", 1)[0]           # drop the parameter name
+        return text.strip()
+
+    protos = {}
+    for ret, name, params in re.findall(r"([A-Za-z_][\w\s]*?\*?)\s*\b(sr_[a-z0-9_]+)\s*\(([^()]*)\)\s*;", src):
+        params = [] if params.strip() in ("", "void") else [ctype(q, True) for q in params.split(",")]
+        protos[name] = (ctype(ret, False), params)
+    return protos
+
+
+_SCALAR_CTYPES = {"int": ctypes.c_int, "int64_t": ctypes.c_int64, "uint64_t": ctypes.c_uint64, "float": ctypes.c_float,
+                  "double": ctypes.c_double, "size_t": ctypes.c_size_t}
+
+
+def _binds(c_type, bound):
+    """True when the ctypes type `bound` carries a C value of type `c_type` unchanged."""
+    if c_type == "const char*":
+        return bound is ctypes.c_char_p
+    if c_type.endswith("*"):
+        return bound is ctypes.c_void_p or bound is ctypes.POINTER(ctypes.c_int) and c_type == "int*"
+    return bound is _SCALAR_CTYPES[c_type]
+
+
+def test_binding_types_match_the_header():
+    """Return type and every parameter type of _lib.SIGNATURES, in order, against the header's prototypes: an `int`
+    bound where the header says `int64_t` (or float for double) loads cleanly and corrupts arguments silently."""
+    from simplerecon_amd import _lib
+    protos = _declared_prototypes()
+    assert sorted(protos) == _declared_symbols() and len(protos) >= 150
+    wrong = []
+    for name, (ret, params) in sorted(protos.items()):
+        res, args = _lib.SIGNATURES[name]
+        if not _binds(ret, res):
+            wrong.append(f"{name}: returns {ret}, bound as {res.__name__}")
+        if len(args) != len(params):
+            wrong.append(f"{name}: {len(params)} parameters, {len(args)} bound")
+            continue
+        wrong += [f"{name} argument {k}: {c}, bound as {a.__name__}" for k, (c, a) in enumerate(zip(params, args))
+                  if not _binds(c, a)]
+    assert not wrong, "\n".join(wrong)
+
+
 def test_binding_loads_and_reports_target():
     from simplerecon_amd import _lib
     lib = _lib.lib()
