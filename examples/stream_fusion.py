@@ -3,11 +3,12 @@
 encoder and UNet++ decoder, all on HIP kernels) -> TSDF fusion of the predicted depth (simplerecon_amd.tsdf; with
 --fuser open3d the sparse, unbounded colour volume of simplerecon_amd.scalable_tsdf, --color for vertex colours) -> with
 --mesh, marching cubes on the GPU and a PLY file; with --point-cloud, multi-view consistency fusion of the same depth maps
-into a coloured point cloud (simplerecon_amd.point_cloud, the reference's pc_fusion.py).  It mirrors what the reference's test.py does per scan
+into a coloured point cloud (simplerecon_amd.point_cloud, the reference's pc_fusion.py); with --viz DIR, the colour-mapped
+predicted depth and the normal map of every keyframe as PNGs (simplerecon_amd.visualization).  It mirrors what the reference's test.py does per scan
 (test.py:210-410) without datasets or checkpoints.
 
     python examples/stream_fusion.py [--frames 120] [--height 192] [--width 256] [--mesh out.ply] [--point-cloud out.ply]
-                                     [--fuser {ours,open3d}] [--color]
+                                     [--fuser {ours,open3d}] [--color] [--viz DIR]
 
 Weights are random, so the depth maps are meaningless -- the point is the data flow and the API.
 """
@@ -51,7 +52,7 @@ def camera_path(n, seed=0):
 
 
 def run(frames=120, height=192, width=256, views=8, device="cuda:0", verbose=True, mesh_path=None,
-        point_cloud_path=None, fuser_name="ours", color=False):
+        point_cloud_path=None, fuser_name="ours", color=False, viz_dir=None):
     opts = dm.default_options(image_width=width, image_height=height, model_num_views=views)
     model = dm.DepthModel(opts)
     for i, m in enumerate((model.encoder, model.matching_model, model.cost_volume_net, model.depth_decoder,
@@ -70,6 +71,10 @@ def run(frames=120, height=192, width=256, views=8, device="cuda:0", verbose=Tru
     K1 = intrinsics(width, height, 1)          # matching resolution = image / 4 -> "s1" of the reference's pyramid
     K_depth = intrinsics(width, height, 1)     # the s0 prediction comes out at image / 2
     invK1 = torch.linalg.inv(K1)
+    if viz_dir:
+        from PIL import Image
+        from simplerecon_amd import visualization as viz
+        os.makedirs(viz_dir, exist_ok=True)
     g = torch.Generator(device="cpu").manual_seed(0)
     predicted = 0
     for i, world_T_cam in enumerate(camera_path(frames)):
@@ -96,6 +101,10 @@ def run(frames=120, height=192, width=256, views=8, device="cuda:0", verbose=Tru
             fuser.fuse_frames(depth, K_depth[None].to(device), cur["cam_T_world_b44"], cur["image_b3hw"])
             if pc_fuser is not None:
                 pc_fuser.fuse_frames(depth, K_depth[None].to(device), cur["cam_T_world_b44"], cur["image_b3hw"])
+            if viz_dir:   # both pictures are made on the device; 8-bit pixels come to the host
+                normals = model.compute_normals(depth, torch.linalg.inv(K_depth)[None].to(device))
+                for name, picture in (("pred_depth", viz.colormap_u8(depth)), ("normals", viz.normals_u8(normals))):
+                    Image.fromarray(picture[0].cpu().numpy()).save(os.path.join(viz_dir, f"{i:06d}_{name}.png"))
         predicted += 1
     if fuser_name == "open3d":
         vol = fuser.volume
@@ -129,6 +138,8 @@ if __name__ == "__main__":
     ap.add_argument("--fuser", choices=["ours", "open3d"], default="ours",
                     help="ours: dense TSDF over fixed bounds; open3d: sparse colour TSDF, unbounded")
     ap.add_argument("--color", action="store_true", help="fuse vertex colours (the open3d fuser; ours ignores it)")
+    ap.add_argument("--viz", default=None, metavar="DIR",
+                    help="write each keyframe's colour-mapped predicted depth and normal map as PNGs into DIR")
     a = ap.parse_args()
     run(a.frames, a.height, a.width, mesh_path=a.mesh, point_cloud_path=a.point_cloud, fuser_name=a.fuser,
-        color=a.color)
+        color=a.color, viz_dir=a.viz)

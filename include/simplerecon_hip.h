@@ -964,6 +964,62 @@ int sr_frames_depth(const void* in, int in_is_int32, int B, int h, int w, const 
                     int W, float scale, float min_valid, float max_valid, int flip, float* depth, float* mask,
                     uint8_t* mask_b, void* stream);
 
+/* ------------------------------------------------------------------ visualisation ----
+ *
+ * The pictures the reference makes with utils/visualization_utils.py (colormap_image, quick_viz_export) and its
+ * training log (experiment_modules/depth_model.py:542-562), computed where the maps already are.  An image is n = H * W
+ * fp32 values, a batch B images back to back.  Every pixel value is a chain of separately rounded IEEE fp32 operations
+ * in the order written below (correctly rounded division, no fused multiply-add), so results equal the reference's CPU
+ * results bit for bit.
+ *
+ * Masks: mask_kind SR_VIZ_MASK_NONE (mask ignored), SR_VIZ_MASK_U8 (uint8 / bool [B,n]) or SR_VIZ_MASK_F32 (fp32
+ * [B,n]).  A value is SELECTED where the mask is non-zero (Tensor.bool(): NaN and -1 select, -0.0 does not); the mask's
+ * float VALUE m (1 / 0 for 8-bit masks) blends colours.
+ *
+ * sr_viz_range: minimum and maximum of the selected values, range [B,2] = (min, max) per image, or [2] over the whole
+ * batch when pooled.  One selected NaN makes both ends NaN (torch.min / torch.max).  An EMPTY selection gives NaN for
+ * both ends: the reference raises there, which cannot be done without a host synchronisation (a documented departure).
+ * Min and max do not depend on the order of comparisons (-0 orders below +0), so the result is the same bits on every
+ * run.  Two launches through `workspace` (sr_viz_range_workspace_bytes, 4-byte aligned); the result stays on the
+ * device.
+ *
+ * sr_viz_colormap, per pixel x of image b:
+ *     t = (x - vmin) / (vmax - vmin);  i = (int) clamp(t * 255, 0, 255), truncated toward zero, NaN -> 0
+ *     rgb = lut[i]                                 lut: [256,3] fp32 (already reversed by the caller for flip=True)
+ *     with a mask: rgb = rgb * m + invalid * (1 - m)
+ * vmin = vmin_dev[b * vmin_stride] when vmin_dev is not NULL (stride 2 into a [B,2] range, 0 for a shared value), else
+ * the host scalar `vmin`; vmax likewise.  Writes out_f32 [B,3,n] (the reference's result), out_u8 [B,n,3] interleaved
+ * = (uint8) clamp(rgb * 255, 0, 255) truncated (np.uint8(rgb * 255); the clamp changes nothing in range, NaN -> 0),
+ * or both; at least one must be given.
+ *
+ * sr_viz_unit: `in` [B,3,n] fp32 -> the same two outputs, with v =
+ *     SR_VIZ_UNIT_NORMALS  nan_to_num(0.5 * (1 + x))           (NaN -> 0, +-inf -> +-FLT_MAX)
+ *     SR_VIZ_UNIT_COLOR    (x - mean_c) / std_c                utils/generic_utils.py reverse_imagenet_normalize:
+ *                          mean = (-2.11790393, -2.03571429, -1.80444444), std = (4.36681223, 4.46428571, 4.44444444),
+ *                          rounded to fp32; subtract then divide (torchvision's normalize)
+ * Values that leave [0, 1] are clamped in the 8-bit output (np.uint8 of an out-of-range float is undefined).
+ *
+ * A workgroup owns SR_VIZ_CHUNK consecutive pixels of one image.  When n % 4 == 0 and every array is 16-byte aligned
+ * (4 bytes for 8-bit arrays) a thread moves 4 pixels per access, otherwise 1: same values either way.  All offsets are
+ * 64-bit.  SR_ERR_UNSUPPORTED: B above SR_VIZ_MAX_BATCH, n above SR_VIZ_MAX_PIXELS.  No call allocates or
+ * synchronises with the host. */
+#define SR_VIZ_MASK_NONE 0
+#define SR_VIZ_MASK_U8 1
+#define SR_VIZ_MASK_F32 2
+#define SR_VIZ_UNIT_NORMALS 0
+#define SR_VIZ_UNIT_COLOR 1
+#define SR_VIZ_CHUNK 4096
+#define SR_VIZ_MAX_BATCH 65535
+#define SR_VIZ_MAX_PIXELS (1ll << 30)
+size_t sr_viz_range_workspace_bytes(int B, int64_t n);
+int sr_viz_range(const float* image, const void* mask, int mask_kind, int B, int64_t n, int pooled, float* range,
+                 void* workspace, size_t workspace_bytes, void* stream);
+int sr_viz_colormap(const float* image, const void* mask, int mask_kind, int B, int64_t n, const float* lut,
+                    const float* vmin_dev, int64_t vmin_stride, const float* vmax_dev, int64_t vmax_stride, float vmin,
+                    float vmax, float invalid_r, float invalid_g, float invalid_b, float* out_f32, uint8_t* out_u8,
+                    void* stream);
+int sr_viz_unit(const float* in, int B, int64_t n, int mode, float* out_f32, uint8_t* out_u8, void* stream);
+
 /* ------------------------------------------------------ backward (training) -------------
  *
  * Backward of sr_dot_volume_sweep (reference: autograd through CostVolumeManager.build_cost_volume,

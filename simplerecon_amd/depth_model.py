@@ -406,6 +406,12 @@ class DepthModel(nn.Module):
         outputs["normals_pred_b3hw"] = self.compute_normals(outputs["depth_pred_s0_b1hw"], cur_data["invK_s0_b44"])
         return self.compute_losses(cur_data, src_data, outputs)["loss"]
 
+    def training_images(self, cur_data, outputs, count=4):
+        """The pictures the reference's training step logs every log_every_n_steps (depth_model.py:542-562), from
+        `cur_data` and `outputs` as step() leaves them: visualization.training_images.  Nothing calls this by default."""
+        from . import visualization
+        return visualization.training_images(cur_data, outputs, count)
+
     def image_prior_pyramid(self, cur_image):
         """`self.encoder(cur_image)` (reference depth_model.py:358), launched on a side HIP stream when the encoder
         runs HIP kernels on the GPU: returns a PendingPyramid that hot_path() joins where the pyramid is consumed."""

@@ -63,7 +63,7 @@ def _mesh_folder(fuser, mask_pred_depth, fusion_use_raw_lowest_cost, fuse_color=
 
 def evaluate(model, scans, output_dir, name, split="test", batch_size=4, run_fusion=False, fuser_factory=None,
              mask_pred_depth=False, fusion_use_raw_lowest_cost=False, gt_mesh_factory=None, depth_fuser="ours",
-             fuse_color=False):
+             fuse_color=False, dump_depth_visualization=False):
     """Scores `model` on `scans` as test.py does and writes output_dir/scores/{scan}_metrics.json (`/` in the scan
     name becomes `_`), all_scene_avg_metrics_{split}.json and all_frame_avg_metrics_{split}.json.  With run_fusion,
     `fuser_factory(scan_name)` (default: on the model's device, tsdf.OurFuser for depth_fuser="ours" or
@@ -74,6 +74,9 @@ def evaluate(model, scans, output_dir, name, split="test", batch_size=4, run_fus
     With run_fusion and `gt_mesh_factory(scan_name)` returning a ground truth (a TriangleMesh, a PointCloud or a PLY path; None skips the
     scan), the exported mesh is scored against it by mesh_metrics.mesh_metrics with its defaults, into
     scores/{scan}_mesh_metrics.json and all_scene_avg_mesh_metrics_{split}.json.
+    With dump_depth_visualization (test.py --dump_depth_visualization), visualization.quick_viz_export writes four PNGs
+    per frame -- ground truth, lowest-cost and predicted depth, colour -- to output_dir/viz/quick_viz/{scan}/, with
+    valid_mask_b = full_res_depth_b1hw > 0.5 (test.py:172-177, 375-388); the scores are not affected.
 
     Returns (all_frame_metrics, all_scene_metrics), the two top-level ResultsAveragers with final averages."""
     device = _model_device(model)
@@ -103,7 +106,11 @@ def evaluate(model, scans, output_dir, name, split="test", batch_size=4, run_fus
         for scan, frames in scans:
             fuser = fuser_factory(scan) if run_fusion else None
             scene_frame_metrics = metrics.ResultsAverager(name, f"scene {scan} metrics")
-            for cur_data, src_data in _batches(frames, batch_size):
+            if dump_depth_visualization:
+                from .visualization import quick_viz_export
+                viz_dir = os.path.join(output_dir, "viz", "quick_viz", scan)
+                os.makedirs(viz_dir, exist_ok=True)
+            for batch_ind, (cur_data, src_data) in enumerate(_batches(frames, batch_size)):
                 cur_data, src_data = _to(cur_data, device), _to(src_data, device)
                 depth_gt = cur_data["full_res_depth_b1hw"]
                 B, size = depth_gt.shape[0], depth_gt.shape[-2:]
@@ -136,6 +143,9 @@ def evaluate(model, scans, output_dir, name, split="test", batch_size=4, run_fus
                         depth[~overall_mask] = -1
                     color = cur_data.get("high_res_color_b3hw", cur_data.get("image_b3hw"))
                     fuser.fuse_frames(depth, cur_data["K_full_depth_b44"], cur_data["cam_T_world_b44"], color)
+
+                if dump_depth_visualization:
+                    quick_viz_export(viz_dir, outputs, cur_data, batch_ind, depth_gt > MIN_DEPTH, batch_size)
 
             if run_fusion:
                 mesh_dir = os.path.join(output_dir, "meshes",
