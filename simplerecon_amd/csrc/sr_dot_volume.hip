@@ -35,7 +35,8 @@ __global__ void sr_geom_kernel(const float* __restrict__ K_src, const float* __r
     const float* Tc = T_cur_src + 16 * (size_t)i;
     t0 = Tc[3]; t1 = Tc[7]; t2 = Tc[11];
     const float tr = (Tc[0] + Tc[5]) + Tc[10];
-    rm = sqrtf(2.0f * (1.0f - fminf(3.0f, tr) / 3.0f));
+    const float trc = tr > 3.0f ? 3.0f : tr;   // torch.minimum: a NaN trace stays NaN (fminf would give 3)
+    rm = sqrtf(2.0f * (1.0f - trc / 3.0f));
     tm = sqrtf((t0 * t0 + t1 * t1) + t2 * t2);
     dist = sqrtf(tm * tm + rm * rm);
   }

@@ -98,7 +98,8 @@ __global__ void sr_pose_distance_kernel(const float* __restrict__ T, float* __re
   const float* Tc = T + 16 * (size_t)i;
   const float t0 = Tc[3], t1 = Tc[7], t2 = Tc[11];
   const float tr = (Tc[0] + Tc[5]) + Tc[10];
-  const float rm = sqrtf(2.0f * (1.0f - fminf(3.0f, tr) / 3.0f));
+  const float trc = tr > 3.0f ? 3.0f : tr;   // torch.minimum / np.minimum: a NaN trace stays NaN (fminf would give 3)
+  const float rm = sqrtf(2.0f * (1.0f - trc / 3.0f));
   const float tm = sqrtf((t0 * t0 + t1 * t1) + t2 * t2);
   out[3 * (size_t)i + 0] = sqrtf(tm * tm + rm * rm);
   out[3 * (size_t)i + 1] = rm;

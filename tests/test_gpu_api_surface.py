@@ -17,9 +17,10 @@ DEV = "cuda:0"
 
 
 def _torch_backproject(depth_b1hw, invK, h, w):
-    """ATen statement of BackprojectDepth.forward (test-side reference)."""
-    ys, xs = torch.meshgrid(torch.arange(h, device=DEV), torch.arange(w, device=DEV), indexing="ij")
-    pix = torch.stack([xs.flatten() + 0.5, ys.flatten() + 0.5, torch.ones(h * w, device=DEV)], 0).unsqueeze(0).float()
+    """ATen statement of BackprojectDepth.forward (test-side reference) in the dtype and on the device of the depth map."""
+    dev, dt = depth_b1hw.device, depth_b1hw.dtype
+    ys, xs = torch.meshgrid(torch.arange(h, device=dev), torch.arange(w, device=dev), indexing="ij")
+    pix = torch.stack([xs.flatten() + 0.5, ys.flatten() + 0.5, torch.ones(h * w, device=dev)], 0).unsqueeze(0).to(dt)
     cam = depth_b1hw.flatten(start_dim=2) * torch.matmul(invK[:, :3, :3], pix)
     return torch.cat([cam, torch.ones_like(cam[:, :1])], 1)
 
@@ -98,16 +99,17 @@ def test_geometry_modules_are_differentiable_like_the_reference():
 
 
 def _torch_warp(inp, planes_b1hw, h, w):
-    """Plain PyTorch fp32 reference of the op (same composition as reference cost_volume.py:139-234)."""
+    """Plain PyTorch reference of the op (same composition as reference cost_volume.py:139-234) in the dtype and on the
+    device of its inputs."""
     b, k, c = inp["src_feats"].shape[:3]
     wp = _torch_backproject(planes_b1hw, inp["cur_invK"], h, w).repeat_interleave(k, dim=0)
     cam = _torch_project(wp, inp["src_Ks"].view(-1, 4, 4), inp["src_extrinsics"].view(-1, 4, 4)).view(-1, 3, h, w)
-    scale = torch.tensor([1 / w, 1 / h], device=DEV).view(1, 1, 1, 2)
+    scale = torch.tensor([1 / w, 1 / h], device=cam.device, dtype=cam.dtype).view(1, 1, 1, 2)
     uv = 2 * cam[:, :2].permute(0, 2, 3, 1) * scale - 1
     warped = F.grid_sample(inp["src_feats"].view(-1, c, h, w), uv, padding_mode="zeros", mode="bilinear",
                            align_corners=False).view(b, k, c, h, w)
     depths = cam[:, 2:].view(b, k, h, w)
-    return wp, depths, warped, (depths > 0).float(), cam[:, :2].view(b, k, 2, h, w)
+    return wp, depths, warped, (depths > 0).to(depths.dtype), cam[:, :2].view(b, k, 2, h, w)
 
 
 @pytest.mark.parametrize("name", ["dot_small", "dot_edge"])
