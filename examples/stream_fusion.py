@@ -4,11 +4,12 @@ encoder and UNet++ decoder, all on HIP kernels) -> TSDF fusion of the predicted 
 --fuser open3d the sparse, unbounded colour volume of simplerecon_amd.scalable_tsdf, --color for vertex colours) -> with
 --mesh, marching cubes on the GPU and a PLY file; with --point-cloud, multi-view consistency fusion of the same depth maps
 into a coloured point cloud (simplerecon_amd.point_cloud, the reference's pc_fusion.py); with --viz DIR, the colour-mapped
-predicted depth and the normal map of every keyframe as PNGs (simplerecon_amd.visualization).  It mirrors what the reference's test.py does per scan
+predicted depth and the normal map of every keyframe as PNGs (simplerecon_amd.visualization); with --render FILE, a shaded
+picture of the fused mesh from the last keyframe's camera (simplerecon_amd.render.render_color).  It mirrors what the reference's test.py does per scan
 (test.py:210-410) without datasets or checkpoints.
 
     python examples/stream_fusion.py [--frames 120] [--height 192] [--width 256] [--mesh out.ply] [--point-cloud out.ply]
-                                     [--fuser {ours,open3d}] [--color] [--viz DIR]
+                                     [--fuser {ours,open3d}] [--color] [--viz DIR] [--render out.png]
 
 Weights are random, so the depth maps are meaningless -- the point is the data flow and the API.
 """
@@ -52,7 +53,7 @@ def camera_path(n, seed=0):
 
 
 def run(frames=120, height=192, width=256, views=8, device="cuda:0", verbose=True, mesh_path=None,
-        point_cloud_path=None, fuser_name="ours", color=False, viz_dir=None):
+        point_cloud_path=None, fuser_name="ours", color=False, viz_dir=None, render_path=None):
     opts = dm.default_options(image_width=width, image_height=height, model_num_views=views)
     model = dm.DepthModel(opts)
     for i, m in enumerate((model.encoder, model.matching_model, model.cost_volume_net, model.depth_decoder,
@@ -76,7 +77,7 @@ def run(frames=120, height=192, width=256, views=8, device="cuda:0", verbose=Tru
         from simplerecon_amd import visualization as viz
         os.makedirs(viz_dir, exist_ok=True)
     g = torch.Generator(device="cpu").manual_seed(0)
-    predicted = 0
+    predicted, last_cam_T_world = 0, None
     for i, world_T_cam in enumerate(camera_path(frames)):
         image = torch.randn((3, height, width), generator=g)
         if buf.try_new_keyframe(world_T_cam, image, index=i) != kf.KeyframeBuffer.ADDED:
@@ -106,6 +107,7 @@ def run(frames=120, height=192, width=256, views=8, device="cuda:0", verbose=Tru
                 for name, picture in (("pred_depth", viz.colormap_u8(depth)), ("normals", viz.normals_u8(normals))):
                     Image.fromarray(picture[0].cpu().numpy()).save(os.path.join(viz_dir, f"{i:06d}_{name}.png"))
         predicted += 1
+        last_cam_T_world = cur["cam_T_world_b44"]
     if fuser_name == "open3d":
         vol = fuser.volume
         touched = int((vol.weights > 0).sum())
@@ -125,6 +127,14 @@ def run(frames=120, height=192, width=256, views=8, device="cuda:0", verbose=Tru
         pc_fuser.export_point_cloud(point_cloud_path)   # pc_fusion.py:152-172
         if verbose:
             print(f"point cloud: {len(pc_fuser.get_point_cloud())} points -> {point_cloud_path}")
+    if render_path and predicted:   # shaded on the device; the 8-bit picture comes to the host for PNG encoding
+        from PIL import Image
+        from simplerecon_amd.render import render_color
+        picture = render_color(fuser.get_mesh(), intrinsics(width, height, 0)[None].to(device), last_cam_T_world, height,
+                               width, output="u8")
+        Image.fromarray(picture[0].cpu().numpy()).save(render_path)
+        if verbose:
+            print(f"render: {width} x {height} -> {render_path}")
     return predicted, touched
 
 
@@ -140,6 +150,8 @@ if __name__ == "__main__":
     ap.add_argument("--color", action="store_true", help="fuse vertex colours (the open3d fuser; ours ignores it)")
     ap.add_argument("--viz", default=None, metavar="DIR",
                     help="write each keyframe's colour-mapped predicted depth and normal map as PNGs into DIR")
+    ap.add_argument("--render", default=None, metavar="FILE",
+                    help="write a shaded picture of the fused mesh, seen from the last keyframe's camera, to this .png file")
     a = ap.parse_args()
     run(a.frames, a.height, a.width, mesh_path=a.mesh, point_cloud_path=a.point_cloud, fuser_name=a.fuser,
-        color=a.color, viz_dir=a.viz)
+        color=a.color, viz_dir=a.viz, render_path=a.render)

@@ -915,6 +915,72 @@ int sr_raster_visibility_mask(const int32_t* face_bhw, int B, int64_t pixels_per
 int sr_raster_visibility_count(uint64_t* masks, int64_t num_faces, int32_t* counts, int min_views, uint8_t* visible,
                                void* stream);
 
+/* ------------------------------------------------------------- mesh shading ----
+ *
+ * Colour and shaded renders of a mesh from the face-id image sr_raster_resolve writes (a deferred pass), and the
+ * vertex normals that pass needs.  tests/shade_oracle.py restates both in float64 numpy; that file is the yardstick.
+ * The shading model is a stated one, ambient plus Lambert: pyrender, whose metallic-roughness shader the reference
+ * draws with, cannot be run next to this code, and nothing here tries to match its pictures (the same standing as the
+ * half-pixel convention of the rasteriser, simplerecon_amd/render.py).
+ *
+ * sr_mesh_vertex_normals: area-weighted vertex normals (Open3D's compute_vertex_normals rule),
+ *     n_v = normalise(sum over the faces f that contain v of (x1 - x0) x (x2 - x0)),
+ * summed in fp64 from the fp32 vertices in ascending face order, normals [V,3] fp32.  A face is skipped when one of
+ * its indices is outside [0, V) or its cross product is not finite.  A vertex gets (0, 0, 0) when no usable face
+ * touches it or when its sum is zero or not finite.  The caller sorts the 3F face corners (corner 3f + j is vertex j
+ * of face f) by vertex id with a STABLE sort: corner_order [3F] int64 is that permutation, vertex_offsets [V + 1]
+ * int64 the start of every vertex's run in it (corners whose vertex id is outside [0, V) sort behind the last
+ * run).  One thread sums one vertex's run, so there is no atomic and the result is the same bits on every run.  Entries
+ * of the two arrays that point outside the faces, or at a corner that is not the vertex's, are ignored.
+ *
+ * sr_raster_shade: mesh, K, cam_T_world, H, W and pixel_offset as for the rasteriser; face_bhw [B,H,W] int32 (-1, or
+ * any value outside [0, F), or a face with an index outside [0, V): an empty pixel); colors [V,3] fp32 or NULL; normals
+ * [V,3] fp32 (world frame) or NULL.  HOST arrays, read before the call returns: base_color [3], background [3], lights
+ * [num_lights][SR_SHADE_LIGHT_FLOATS] = (kind, x, y, z, r, g, b intensity, unused), num_lights <= SR_SHADE_MAX_LIGHTS.
+ * Per pixel with a face, in fp64 from the fp32 inputs, every step a separately rounded IEEE operation (correctly
+ * rounded divide and square root, no fused multiply-add), rounded to fp32 once at the end:
+ *  - X_i = R x_i + t; a = X_0, e1 = X_1 - X_0, e2 = X_2 - X_0, n = e1 x e2; the pixel's ray r as the rasteriser
+ *    defines it; d = r . n; hit point P = ((a . n) / d) r.  Barycentrics from the ray (perspective-correct, and valid
+ *    for a face the rasteriser clipped): u = -(r . (a x e2)) / d, v = -(r . (e1 x a)) / d, w = (1 - (u + v), u, v), each
+ *    clamped to [0, 1], then divided by their sum.  An attribute is interpolated as x_0 w_0 + (x_1 w_1 + x_2 w_2).
+ *  - base colour c: the interpolated vertex colour, or base_color without colours.
+ *  - geometric normal n_g = n / |n|, negated when n_g . P > 0 (it faces the viewer).  Smooth normal: m = R (the
+ *    interpolated vertex normal), n = m / |m|, negated when the face is back-facing (a . n >= 0, the rasteriser's
+ *    rule); n = n_g when |m| < 1e-12 or is not finite, without normals, and with SR_SHADE_NORMAL_FLAT.
+ *  - SR_SHADE_UNLIT: out = c.  SR_SHADE_NORMALS: out = 0.5 (1 + n), n in the camera frame.  SR_SHADE_LAMBERT:
+ *    out_k = c_k (ambient + sum_l I_lk max(0, n . l_l) a_l), where max(0, NaN) = 0 and per kind
+ *      SR_SHADE_LIGHT_DIRECTIONAL  xyz = the direction the light travels, world frame: l = -R (xyz / |xyz|), a = 1
+ *      SR_SHADE_LIGHT_POINT        xyz = the position, world frame: with D = (R xyz + t) - P, l = D / |D|,
+ *                                  a = 1 / max(|D|^2, 1e-12)
+ *      SR_SHADE_LIGHT_HEAD         l = -P / |P|, a = 1
+ * Outputs, any of them NULL but not all: out_f32 [B,3,H,W] clamped to [0, 1] with NaN -> 0; out_u8 [B,H,W,3]
+ * interleaved = (uint8)(out_f32 * 255.0f) truncated, in fp32 from the value out_f32 holds (sr_viz's rule);
+ * normals_out [B,3,H,W] = n, 0 where the pixel is empty.  An empty pixel gets `background` as given in out_f32 (and
+ * its bytes by the same rule, clamped).
+ *
+ * A workgroup owns 256 consecutive pixels of one view, one lane each; B * ceil(H W / 256) * 256 must stay within
+ * SR_RASTER_MAX_THREADS.  All offsets are 64-bit; no atomics; the library allocates nothing and no call synchronises
+ * with the host.  Refused on the host before any launch (SR_ERR_INVALID_ARGUMENT): NULL required pointers, no output,
+ * an unknown shading mode, normal mode or light kind, more than SR_SHADE_MAX_LIGHTS lights, sizes beyond
+ * SR_RASTER_MAX_SIDE or SR_RASTER_MAX_THREADS, a pixel_offset outside [-1, 1]. */
+#define SR_SHADE_UNLIT 0
+#define SR_SHADE_NORMALS 1
+#define SR_SHADE_LAMBERT 2
+#define SR_SHADE_NORMAL_SMOOTH 0
+#define SR_SHADE_NORMAL_FLAT 1
+#define SR_SHADE_LIGHT_DIRECTIONAL 0
+#define SR_SHADE_LIGHT_POINT 1
+#define SR_SHADE_LIGHT_HEAD 2
+#define SR_SHADE_MAX_LIGHTS 32
+#define SR_SHADE_LIGHT_FLOATS 8
+int sr_mesh_vertex_normals(const float* vertices, int64_t num_vertices, const int32_t* faces, int64_t num_faces,
+                           const int64_t* corner_order, const int64_t* vertex_offsets, float* normals, void* stream);
+int sr_raster_shade(const float* vertices, int64_t num_vertices, const int32_t* faces, int64_t num_faces, const float* K,
+                    const float* cam_T_world, int B, int H, int W, float pixel_offset, const int32_t* face_bhw,
+                    const float* colors, const float* normals, const float* base_color, const float* background,
+                    float ambient, const float* lights, int num_lights, int shading, int normal_mode, float* out_f32,
+                    uint8_t* out_u8, float* normals_out, void* stream);
+
 /* ------------------------------------------------------------- frame preparation ----
  *
  * What the reference's data loader does to a decoded frame (datasets/generic_mvs_dataset.py get_frame,

@@ -197,6 +197,9 @@ SIGNATURES = {
     "sr_raster_resolve": (_i, [_p, _i64, _p, _p, _p]),
     "sr_raster_visibility_mask": (_i, [_p, _i, _i64, _i64, _p, _p]),
     "sr_raster_visibility_count": (_i, [_p, _i64, _p, _i, _p, _p]),
+    "sr_mesh_vertex_normals": (_i, [_p, _i64, _p, _i64, _p, _p, _p, _p]),
+    "sr_raster_shade": (_i, [_p, _i64, _p, _i64, _p, _p, _i, _i, _i, _f, _p, _p, _p, _p, _p, _f, _p, _i, _i, _i, _p, _p,
+                             _p, _p]),
     "sr_frames_resize_fits_lds": (_i, [_i, _i, _i, _i]),
     "sr_frames_resize": (_i, [_p, _i, _i, _i, _i, _p, _i, _p, _i, _i, _p, _p, _i, _i, _i, _i, _p, _p]),
     "sr_frames_depth": (_i, [_p, _i, _i, _i, _i, _p, _p, _i, _i, _f, _f, _f, _i, _p, _p, _p, _p]),
