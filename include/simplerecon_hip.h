@@ -1276,6 +1276,44 @@ int sr_conv_wgrad_padded_nhwc(const float* in, int64_t in_batch_stride, int in_p
                               int Cout, int ksize, int stride, int pad_top, int pad_left, int Ho, int Wo, void* workspace,
                               size_t workspace_bytes, void* stream);
 
+/* ---- 16-bit MFMA convolutions of the autocast training path (csrc/sr_conv16.hip; opt-in: SR_AUTOCAST_MFMA16) ----------
+ * The reference trains under 16-bit autocast (options.py:100-101 `precision: 16`, train.py:132): its convolutions multiply
+ * 16-bit operands.  sr_conv16_nhwc_fwd is that convolution as an implicit GEMM on v_mfma_f32_32x32x16_{f16,bf16}:
+ *     out = round_to(out_dtype, act(sum + bias + residual))
+ * 3x3 with stride 1 or 2 and zero padding 1 (output (h + 2 - 3) / stride + 1), or 1x1 with stride 1, on channels-last
+ * views (strides in ELEMENTS; arbitrary batch / pixel strides, so channel slices of wider buffers work).  It serves the
+ * forward pass and, on the flipped and transposed weight (sr_conv_flip_transpose_weights), the data gradient.
+ * Numeric contract: input and residual are fp16 (io_dtype = 1) or bf16 (io_dtype = 2); the weight is rounded ONCE to the same
+ * type by sr_conv16_pack_weights (round to nearest even, exactly tensor.to(dtype); an fp16 overflow becomes inf, as under
+ * torch autocast); products of two 16-bit values are exact and are summed in fp32 on the matrix pipe, taps and channels in a
+ * fixed order per output element (no atomics, no K split: two runs give the same bits); bias (fp32), residual and the
+ * activation (`leaky_slope` >= 0: LeakyReLU, SR_ACT_NONE: identity; SR_ACT_SILU is SR_ERR_UNSUPPORTED) are applied in fp32;
+ * ONE rounding to nearest even on the way out, to out_dtype = io_dtype, or none with out_dtype = 0 (fp32 output: the heads
+ * that feed fp32 losses).  Subnormals (from the CDNA ISA text, NOT measured here): the fp32 C input and D output of
+ * an MFMA never flush; its A / B operands follow the wave's MODE denormal controls as VALU operations do, and the compiler's
+ * default kernel mode keeps subnormals for fp16 as for fp32, so 16-bit subnormal operands enter the sum as the values they
+ * encode (a build with -fgpu-flush-denormals-to-zero may flush the operands, never the accumulator); the fp32 epilogue runs
+ * in the same default mode, and the output rounding produces 16-bit subnormals where the value calls for one.
+ * Requirements (SR_ERR_UNSUPPORTED otherwise, nothing is launched): Cin % 8 == 0 and Cout % 8 == 0 (eight input channels
+ * are one 16-byte access; the output is written in whole 4-channel quads, there is no scalar tail), every batch and pixel
+ * stride a multiple of 8 elements, pixel strides >= the channel count, 16-byte aligned `in`, `packed_w`, `residual`, `out`.
+ * Cin that is no multiple of the 16-channel MFMA step (8, 24, 40, ...) and Cout that is no multiple of the 32-channel tile
+ * (8, 40, 160) are zero-filled inside the kernel; nothing is read past a row.  SR_ERR_INVALID_ARGUMENT: a NULL in / packed_w
+ * / out, io_dtype outside {1, 2}, out_dtype outside {0, io_dtype}, k outside {1, 3}, stride outside {1, 2} or 2 with k = 1.
+ * sr_conv16_supported: the shape test alone (pure host function; pointers and strides are checked at launch).
+ * sr_conv16_prefers: 1 where the kernel measured faster than the path the same 16-bit tensors took before it
+ * (profiles/r07_conv16.txt) -- what SR_AUTOCAST_MFMA16=1 routes by.  sr_conv16_packed_weight_bytes: size of `packed`
+ * (>= 2 Cout Cin k k, a multiple of 16; `packed` must be 16-byte aligned).  Nothing here allocates or synchronises. */
+size_t sr_conv16_packed_weight_bytes(int Cout, int Cin, int k);
+int sr_conv16_pack_weights(const float* weight /* [Co][Ci][k][k] fp32 */, int Cout, int Cin, int k, int dtype, void* packed,
+                           void* stream);
+int sr_conv16_supported(int B, int H, int W, int Cin, int Cout, int k, int stride);
+int sr_conv16_prefers(int B, int H, int W, int Cin, int Cout, int k, int stride);
+int sr_conv16_nhwc_fwd(const void* in, int64_t in_batch_stride, int in_pix_stride, const void* packed_w, const float* bias,
+                       const void* residual, int64_t res_batch_stride, int res_pix_stride, void* out,
+                       int64_t out_batch_stride, int out_pix_stride, int B, int H, int W, int Cin, int Cout, int k, int stride,
+                       float leaky_slope, int io_dtype, int out_dtype, void* stream);
+
 #ifdef __cplusplus
 }
 #endif

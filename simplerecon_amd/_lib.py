@@ -40,6 +40,11 @@ SIGNATURES = {
     "sr_se_gate2_fwd": (_i, [_p, _i, _i, _p, _p, _p, _p, _p, _p, _i, _i, _i, _p]),
     "sr_conv3x3_wino_io_nhwc_fwd": (_i, [_p, _i64, _i, _p, _p, _p, _i64, _i, _p, _i64, _i, _i, _i, _i, _i, _i, _f, _i, _p]),
     "sr_pw_conv_io_nhwc_fwd": (_i, [_p, _i64, _i, _p, _p, _p, _i64, _i, _p, _i64, _i, _i, _i, _i, _i, _f, _i, _p]),
+    "sr_conv16_packed_weight_bytes": (_sz, [_i, _i, _i]),
+    "sr_conv16_pack_weights": (_i, [_p, _i, _i, _i, _i, _p, _p]),
+    "sr_conv16_supported": (_i, [_i, _i, _i, _i, _i, _i, _i]),
+    "sr_conv16_prefers": (_i, [_i, _i, _i, _i, _i, _i, _i]),
+    "sr_conv16_nhwc_fwd": (_i, [_p, _i64, _i, _p, _p, _p, _i64, _i, _p, _i64, _i, _i, _i, _i, _i, _i, _i, _i, _f, _i, _i, _p]),
     "sr_pw_conv_tiled_workspace_bytes": (_sz, [_i, _i, _i]),
     "sr_pw_conv_tiled_plan": (_i, [_i, _i, _i, _i, _p, _p]),
     "sr_pw_conv_tiled_nhwc_fwd": (_i, [_p, _i, _p, _p, _p, _p, _i, _p, _i, _i, _i, _i, _i, _f, _p, _sz, _p]),

@@ -64,6 +64,16 @@ STORE_HALF = os.environ.get("SR_AUTOCAST_HALF_STORAGE", "0") != "0"
 # fp32 copies of the saved tensors; stride-2 and explicitly padded convolutions convert at their boundary.
 HALF_IO = os.environ.get("SR_AUTOCAST_HALF_IO", "0") != "0"
 _IO_CODE = {torch.float16: 1, torch.bfloat16: 2}
+# 16-bit MFMA convolutions (r07; SR_AUTOCAST_MFMA16, default 0 = off: exactly the paths above).  Where HALF_IO has put 16-bit
+# activations on the path, the convolutions of the conv stack -- 3x3 at stride 1 and 2, 1x1 -- multiply on the 16-bit matrix pipe
+# (csrc/sr_conv16.hip: weights rounded once to the activation dtype, fp32 accumulation, bias / residual / LeakyReLU in fp32,
+# one rounding on the way out): the arithmetic of the reference's `precision: 16` convolutions, with an fp32 instead of a 16-bit
+# result before the activation.  A layer whose forward ran there takes its data gradient there as well (the post-activation
+# gradient is cast to the layer's dtype); weight / bias gradients and the activation derivative stay fp32.
+# 1 = the layers sr_conv16_supported AND sr_conv16_prefers (the measured rule, profiles/r07_conv16.txt) accept, 2 = every
+# supported layer (tests, A/B runs).  Read at call time, like HALF_IO.  fp16 (not bf16) needs a loss scaler: the 16-bit data
+# gradient underflows otherwise.
+MFMA16 = int(os.environ.get("SR_AUTOCAST_MFMA16", "0") or 0)
 
 
 def _amp_state_fwd(fwd):
@@ -208,9 +218,53 @@ def _aligned8(t):
     return t is None or (t.data_ptr() % 8 == 0 and all(s % 4 == 0 for s in _strides(t)))
 
 
+def _aligned16(t):
+    """None, or a 16-bit channels-last view whose pixel rows all start 16-byte aligned (eight channels per access)."""
+    return t is None or (t.data_ptr() % 16 == 0 and all(s % 8 == 0 for s in _strides(t)))
+
+
+def _mfma16_selects(b, h, w, ci, co, k, stride, pads):
+    """The routing predicate of MFMA16 on a layer's shape: never with the switch at 0, never for explicit `pads`."""
+    mode = MFMA16
+    if not mode or pads is not None or b <= 0:
+        return False
+    lib = _lib.lib()
+    if not lib.sr_conv16_supported(b, h, w, ci, co, k, stride):
+        return False
+    return mode >= 2 or bool(lib.sr_conv16_prefers(b, h, w, ci, co, k, stride))
+
+
+def _conv16_routes(x, weight, stride, residual, pads):
+    """True when _conv_raw_io takes this call (16-bit channels-last views `x`, `residual`) to the 16-bit MFMA kernel."""
+    b, ci, h, w = x.shape
+    co, _, k, _ = weight.shape
+    return x.dtype in _IO_CODE and _mfma16_selects(b, h, w, ci, co, k, stride, pads) and _aligned16(x) and \
+        (residual is None or (residual.dtype == x.dtype and _aligned16(residual)))
+
+
+def _conv16(x, weight, bias, stride, residual, slope, out_f32=False):
+    """act(conv(x, weight) + bias [+ residual]) on sr_conv16_nhwc_fwd: `x` / `residual` fp16 or bf16 channels-last views, the
+    fp32 weight tensor rounded to that dtype and packed on the fly, output in the same dtype or (out_f32) fp32."""
+    dt = x.dtype
+    b, ci, h, w = x.shape
+    co, _, k, _ = weight.shape
+    pad = k // 2
+    ho, wo = (h + 2 * pad - k) // stride + 1, (w + 2 * pad - k) // stride + 1
+    out = torch.empty((b, co, ho, wo), dtype=torch.float32 if out_f32 else dt, device=x.device,
+                      memory_format=torch.channels_last)
+    wp = torch.empty(_lib.lib().sr_conv16_packed_weight_bytes(co, ci, k), dtype=torch.uint8, device=x.device)
+    _lib.call("sr_conv16_pack_weights", x.device, weight.detach().float().contiguous(), co, ci, k, _IO_CODE[dt], wp)
+    bd = bias.detach().float().contiguous() if bias is not None else None
+    rsb, rsp = _strides(residual) if residual is not None else (0, 0)
+    _lib.call("sr_conv16_nhwc_fwd", x.device, x, *_strides(x), wp, bd, residual, rsb, rsp, out, *_strides(out), b, h, w, ci, co,
+              k, stride, _act_code(slope, None), _IO_CODE[dt], 0 if out_f32 else _IO_CODE[dt])
+    return out
+
+
 def _conv_raw_io(x, weight, bias, stride, residual, slope, pads):
-    """_conv_raw on fp16 / bf16 activations: 16-bit kernel I/O where the kernel has it (3x3 / stride 1 through Winograd,
-    1x1 / stride 1 through the pointwise GEMM), boundary conversion around the fp32 kernel otherwise."""
+    """_conv_raw on fp16 / bf16 activations: the 16-bit MFMA kernel where MFMA16 selects the layer (3x3 at stride 1 and 2, 1x1);
+    else 16-bit kernel I/O where the kernel has it (3x3 / stride 1 through Winograd, 1x1 / stride 1 through the pointwise
+    GEMM), boundary conversion around the fp32 kernel otherwise."""
     dt = x.dtype
     x = _nhwc_any(x, "conv input")
     b, ci, h, w = x.shape
@@ -219,6 +273,8 @@ def _conv_raw_io(x, weight, bias, stride, residual, slope, pads):
         raise ValueError(f"conv weight expects {ci_w} input channels, got {ci}")
     if residual is not None:
         residual = _nhwc_any(residual if residual.dtype == dt else residual.to(dt), "residual")
+    if MFMA16 and _conv16_routes(x, weight, stride, residual, pads):
+        return _conv16(x, weight, bias, stride, residual, slope)
     wino = pads is None and stride == 1 and k == 3 and b > 0 and ci % 4 == 0 and co % 4 == 0 and \
         bool(_lib.lib().sr_conv_prefers_wino(b, h, w, ci, co, k, stride))
     pw = pads is None and stride == 1 and k == 1 and b > 0 and ci % 4 == 0
@@ -294,6 +350,11 @@ class _ConvBiasAct(torch.autograd.Function):
             for name, t in (("conv input", x), ("conv weight", weight)):
                 _lib.require_device_f32(name, t)
             x = as_nhwc(x, "conv input")
+        ctx.mfma16 = False
+        if MFMA16 and dt != torch.float32:   # (the same test _conv_raw_io makes, on the same views: the backward follows it)
+            x = _nhwc_any(x, "conv input")
+            residual = _nhwc_any(residual, "residual") if residual is not None else None
+            ctx.mfma16 = _conv16_routes(x, weight, stride, residual, pads)
         out = _conv_raw(x, weight, bias, stride, residual, slope, pads)
         ctx.stride, ctx.slope, ctx.pads = stride, slope, pads
         ctx.has_bias, ctx.has_res = bias is not None, residual is not None
@@ -305,6 +366,7 @@ class _ConvBiasAct(torch.autograd.Function):
     def backward(ctx, g):
         x, weight, out = _unstash(ctx)
         # (16-bit I/O: the backward kernels take fp32 copies of what the forward saved in 16 bits)
+        dt16 = x.dtype if ctx.mfma16 else None   # the layer's 16-bit dtype when its forward ran on the 16-bit MFMA kernel
         x = x if x.dtype == torch.float32 else x.float()
         out = out if (out is None or out.dtype == torch.float32) else out.float()
         lib = _lib.lib()
@@ -365,7 +427,16 @@ class _ConvBiasAct(torch.autograd.Function):
                     src = empty_nhwc(b, co, h, w, dev)
                     if b > 0:
                         _lib.call("sr_zero_stuff2x_nhwc", dev, gp, gsb, gsp, src, b, ho, wo, h, w, co)
-                if pads is None:
+                if dt16 is not None and b > 0:
+                    # the forward ran on the 16-bit MFMA kernel: so does the data gradient, on the gradient cast to the layer's
+                    # dtype (stride 2: the fp32 stuffing kernel first -- either order is two launches); d_x comes out in
+                    # the caller's dtype when that is fp32 (no cast behind the kernel)
+                    src = src.to(dt16)
+                    if _conv16_routes(src, wt, 1, None, None):
+                        d_x = _conv16(src, wt, None, 1, None, None, out_f32=ctx.in_dtypes[0] == torch.float32)
+                    else:   # (MFMA16 = 1 and the rule declines the transposed shape, or the switch changed since the forward)
+                        d_x = _conv_raw(src, wt, None, 1)
+                elif pads is None:
                     d_x = _conv_raw(src, wt, None, 1)
                 elif s == 1:   # full correlation: pads k-1-p on the opposite roles
                     d_x = _conv_raw(src, wt, None, 1, pads=(k - 1 - pads[0], k - 1 - pads[1], k - 1 - pads[2], k - 1 - pads[3]))

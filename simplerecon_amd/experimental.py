@@ -32,3 +32,29 @@ def split_precision(mode="f16", sweep=True, convs=True):
     finally:
         for n, v in saved.items():
             _lib.set_option(n, v)
+
+
+@contextlib.contextmanager
+def autocast_mfma16(mode=1, storage=True):
+    """16-bit MFMA convolutions for the training steps made inside the block, to be combined with torch.autocast:
+
+        with torch.autocast("cuda", dtype=torch.bfloat16), experimental.autocast_mfma16():
+            loss = model.step(...)
+
+    Sets `autograd_ops.HALF_IO` (16-bit activations between the conv-stack layers), `autograd_ops.MFMA16 = mode` (1: the
+    layers the measured rule sr_conv16_prefers accepts, 2: every layer sr_conv16_supported accepts) and, with `storage`,
+    `autograd_ops.STORE_HALF` (saved activations in 16 bits); restores the three previous values on exit.  The backward pass
+    must run inside the block too (the data gradient reads the switch).  fp16, unlike bf16, needs a loss scaler.
+    The switches are module attributes, hence process-wide: forward / backward passes that OTHER threads run while the block
+    is open take the 16-bit paths as well."""
+    from . import autograd_ops
+    if mode not in (0, 1, 2):
+        raise ValueError(f"autocast_mfma16 mode must be 0, 1 or 2, got {mode!r}")
+    saved = (autograd_ops.HALF_IO, autograd_ops.MFMA16, autograd_ops.STORE_HALF)
+    try:
+        autograd_ops.HALF_IO, autograd_ops.MFMA16 = True, mode
+        if storage:
+            autograd_ops.STORE_HALF = True
+        yield
+    finally:
+        autograd_ops.HALF_IO, autograd_ops.MFMA16, autograd_ops.STORE_HALF = saved
