@@ -46,14 +46,17 @@ struct SrSample {
   float pix_x, pix_y;  // q_x * s, q_y * s                   (geometry_utils.py:85-87)
   float w_nw, w_ne, w_sw, w_se;  // bilinear weights, already zeroed for out-of-image taps
   int o_nw, o_ne, o_sw, o_se;    // texel indices (y*w + x), clamped in-image
+  bool any_tap;                  // at least one of the four taps lies inside the image
 };
 
 typedef float sr_f2v __attribute__((ext_vector_type(2)));
 
 // Integer tap origin (floats, unclamped) and the four bilinear weights of the unnormalised sampling position (ix, iy)
 // (grid_sample, bilinear, zeros padding, align_corners=False): weights of out-of-image taps are zero.
+// any_tap: some tap is inside the image -- tap (xi, yj) is valid iff column xi and row yj both are, so this is
+// (vx0 | vx1) & (vy0 | vy1), the validity tests themselves and not a guess from the weights (a valid tap may weigh 0).
 __device__ __forceinline__ void sr_bilinear_taps(float ix, float iy, int h, int w, float& fx0, float& fy0, float& w_nw,
-                                                 float& w_ne, float& w_sw, float& w_se) {
+                                                 float& w_ne, float& w_sw, float& w_se, bool& any_tap) {
 #pragma clang fp contract(off)
   const sr_f2v ixy = {ix, iy};
   fx0 = floorf(ix);
@@ -73,6 +76,12 @@ __device__ __forceinline__ void sr_bilinear_taps(float ix, float iy, int h, int 
   w_ne = (vx1 & vy0) ? wtop.y : 0.0f;
   w_sw = (vx0 & vy1) ? wbot.x : 0.0f;
   w_se = (vx1 & vy1) ? wbot.y : 0.0f;
+  any_tap = (vx0 | vx1) & (vy0 | vy1);
+}
+__device__ __forceinline__ void sr_bilinear_taps(float ix, float iy, int h, int w, float& fx0, float& fy0, float& w_nw,
+                                                 float& w_ne, float& w_sw, float& w_se) {
+  bool any_tap;
+  sr_bilinear_taps(ix, iy, h, w, fx0, fy0, w_nw, w_ne, w_sw, w_se, any_tap);
 }
 
 // Core of the projection: everything up to the bilinear weights, with the UNCLAMPED integer tap origin (fx0, fy0) as
@@ -85,6 +94,7 @@ struct SrSampleXY {
   float ix, iy;                  // unnormalised sampling position (texel units; may be anything, incl. NaN)
   float fx0, fy0;                // its floor = the NW tap
   float w_nw, w_ne, w_sw, w_se;  // bilinear weights, already zeroed for out-of-image taps
+  bool any_tap;                  // at least one tap inside the image (sr_bilinear_taps)
 };
 
 __device__ __forceinline__ void sr_project_sample_xy(const float* __restrict__ g /*geom record*/,
@@ -105,7 +115,7 @@ __device__ __forceinline__ void sr_project_sample_xy(const float* __restrict__ g
   const sr_f2v ixy = ((uv + 1.0f) * size - 1.0f) / 2.0f;
   s.ix = ixy.x;
   s.iy = ixy.y;
-  sr_bilinear_taps(s.ix, s.iy, h, w, s.fx0, s.fy0, s.w_nw, s.w_ne, s.w_sw, s.w_se);
+  sr_bilinear_taps(s.ix, s.iy, h, w, s.fx0, s.fy0, s.w_nw, s.w_ne, s.w_sw, s.w_se, s.any_tap);
 }
 
 __device__ __forceinline__ void sr_project_sample(const float* __restrict__ g /*geom record*/,
@@ -115,6 +125,7 @@ __device__ __forceinline__ void sr_project_sample(const float* __restrict__ g /*
   sr_project_sample_xy(g, X0, X1, X2, h, w, inv_w, inv_h, c);
   s.zp = c.zp; s.pix_x = c.pix_x; s.pix_y = c.pix_y;
   s.w_nw = c.w_nw; s.w_ne = c.w_ne; s.w_sw = c.w_sw; s.w_se = c.w_se;
+  s.any_tap = c.any_tap;
   const float wm = (float)(w - 1), hm = (float)(h - 1);
   const float fx1 = c.fx0 + 1.0f, fy1 = c.fy0 + 1.0f;
   // clamp (NaN-safe: fmaxf(NaN, 0) = 0) so every tap address is in-image; weight 0 kills it

@@ -160,6 +160,13 @@ __device__ __forceinline__ void sr_l1_step_init(f32x16 (&acc)[2][4], const f32x1
   acc[1][3] = SR_MFMA(wA.w, bQ, hc[1][3]);
 }
 
+// a wave-uniform flag in a scalar register whose value the optimiser cannot see through
+__device__ __forceinline__ int sr_opaque(bool flag) {
+  int v = __builtin_amdgcn_readfirstlane((int)flag);
+  asm volatile("" : "+s"(v));
+  return v;
+}
+
 #define SR_LDS_W3_FLOATS 256  // w3tab (128) + b3 + pad, in front of W1 in LDS
 
 template <bool W1_LDS, bool W2_LDS>
@@ -196,21 +203,30 @@ __global__ __launch_bounds__(256, 1) void sr_mlp_volume_kernel(SrMlpParams p) {
   // again and again (r03 PMC, cfg5: 1.2 GB of fabric traffic per launch for 244 MB of compulsory bytes).  Units are
   // ordered (image, pixel tile, plane chunk): give XCD x the contiguous eighth [x U8, (x + 1) U8) -- a band of pixel tiles
   // whose tap footprints overlap -- and let its waves stride through that band.
-  long wave0 = (long)blockIdx.x * (blockDim.x >> 6) + (threadIdx.x >> 6);
-  long nwaves = (long)gridDim.x * (blockDim.x >> 6);
+  constexpr int WPB = 4;  // waves per block: every launch is 256 threads (__launch_bounds__, SR_MLP_LAUNCH)
+  // (the wave index as a scalar: units, planes and views then loop under scalar branches, and the dead-view bodies below are
+  // selected by plain s_cbranch instead of being flattened into a predicated chain)
+  const int wid = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);
+  long wave0 = (long)blockIdx.x * WPB + wid;
+  long nwaves = (long)gridDim.x * WPB;
   long unit_end = nunits;
   if ((gridDim.x & 7) == 0) {
     const long u8 = (nunits + 7) / 8;
     const int xcd = blockIdx.x & 7;
-    nwaves = (long)(gridDim.x >> 3) * (blockDim.x >> 6);
-    wave0 = xcd * u8 + (long)(blockIdx.x >> 3) * (blockDim.x >> 6) + (threadIdx.x >> 6);
+    nwaves = (long)(gridDim.x >> 3) * WPB;
+    wave0 = xcd * u8 + (long)(blockIdx.x >> 3) * WPB + wid;
     unit_end = min(nunits, (xcd + 1) * u8);
   }
   const int half = lane >> 5;
 
+  // A wave strides through the units by nwaves, usually a multiple of the chunk count: it would own the SAME plane chunk of
+  // every pixel tile it visits.  Planes no longer cost the same (near planes have the most dead views, see below), and the
+  // waves of the far chunks would finish last with everybody else idle.  So the chunk of a unit is rotated by the number
+  // of strides that lead to it: per pixel tile still every chunk exactly once, per wave every chunk in turn.
+  const int rot = (int)max(1L, nwaves / p.chunks);
   for (long unit = wave0; unit < unit_end; unit += nwaves) {
-    const int chunk = (int)(unit % p.chunks);
     const long tb = unit / p.chunks;
+    const int chunk = (int)((unit % p.chunks + tb / rot) % p.chunks);
     const int tile = (int)(tb % p.tiles);
     const int b = (int)(tb / p.tiles);
     const int j0 = chunk * p.chunk, j1 = min(p.D, j0 + p.chunk);
@@ -275,11 +291,24 @@ __global__ __launch_bounds__(256, 1) void sr_mlp_volume_kernel(SrMlpParams p) {
 
     SrSample smp;
     float4 taps[16];
-    float f[SR_VIEW_SLOTS], fn[SR_VIEW_SLOTS];
     float X0, X1, X2, d;
     bool any_depth, any_bounds;
-    auto issue_view = [&](int k) {
-      sr_project_sample(geom_b + k * SR_GEOM_STRIDE, X0, X1, X2, p.h, p.w, p.inv_w, p.inv_h, smp);
+    // A view is DEAD for this wave at this plane when no tap of any of its pixels lies inside the source image: its 16
+    // warped channels and dot * mask are exact zeros (zeros padding), so its feature k-steps 0..7 would add W . 0 and its
+    // tap loads, interpolation and dot product would only produce those zeros.  Wave-uniform (a ballot), keyed on the
+    // tap validity tests and not on z' > 0: a point behind the camera has mask 0, but its mirrored taps can be in the
+    // image and the reference does not mask the warped features by depth.  The clamped lanes of a ragged last tile
+    // (pix >= N) do not vote; what they compute is never stored.
+    // (the view's camera centre is read here, in front of its tap loads: vector loads return in order, and read behind
+    // them it made the first k-step wait for all 16 taps)
+    float gt0, gt1, gt2;
+    auto project_view = [&](int k) -> bool {
+      const float* g = geom_b + k * SR_GEOM_STRIDE;
+      gt0 = g[12]; gt1 = g[13]; gt2 = g[14];
+      sr_project_sample(g, X0, X1, X2, p.h, p.w, p.inv_w, p.inv_h, smp);
+      return __builtin_amdgcn_ballot_w64(active & smp.any_tap) == 0;
+    };
+    auto load_taps = [&](int k) {
       const float* img = src_b + (size_t)k * N * C;
       const float4* t_nw = reinterpret_cast<const float4*>(img + (size_t)smp.o_nw * C);
       const float4* t_ne = reinterpret_cast<const float4*>(img + (size_t)smp.o_ne * C);
@@ -292,13 +321,15 @@ __global__ __launch_bounds__(256, 1) void sr_mlp_volume_kernel(SrMlpParams p) {
     };
     // pieces of the per-view feature assembly (o = fn or f); the ray pieces need no taps
     float rv0, rv1, rv2, rsd, rdot;
-#define SR_RAY_A(o, g, kview)                                                                 \
+#define SR_RAY_A_T(o, t0, t1, t2, kview)                                                      \
     {                                                                                         \
       _Pragma("clang fp contract(off)")                                                       \
-      rv0 = X0 - (g)[12]; rv1 = X1 - (g)[13]; rv2 = X2 - (g)[14];                              \
+      rv0 = X0 - (t0); rv1 = X1 - (t1); rv2 = X2 - (t2);                                       \
       rsd = fmaxf(sqrtf((rv0 * rv0 + rv1 * rv1) + rv2 * rv2), 1e-12f);                         \
       (o)[23] = ((kview) == 0) ? d : 0.0f; /* plane depth rides in view 0's spare slot */      \
     }
+#define SR_RAY_A(o, g, kview) SR_RAY_A_T(o, (g)[12], (g)[13], (g)[14], kview)
+#define SR_RAY_A0(o, kview) SR_RAY_A_T(o, gt0, gt1, gt2, kview)  /* camera centre read by project_view */
   // (r03) the source ray F.normalize(X - t_k) (cost_volume.py:654-669) and the ray angle F.cosine_similarity(...)
   // (:683-688) divide three components by one norm each: ONE IEEE reciprocal + three multiplies per normalisation
   // instead of three IEEE divisions (10 VALU instructions apiece beside the MFMAs).  x * (1/n) differs from x / n by at
@@ -340,13 +371,22 @@ __global__ __launch_bounds__(256, 1) void sr_mlp_volume_kernel(SrMlpParams p) {
       (o)[17] = smp.zp;              /* z'_k (cost_volume.py:603-609) */                      \
       (o)[18] = front ? rdot : 0.0f; /* dot * mask (cost_volume.py:691-695) */                \
     }
+#define SR_DOT_DEAD(o)  /* SR_DOT of a dead view: channels 0..15 are never read, dot * mask is 0 */ \
+    {                                                                                         \
+      const bool front = smp.zp > 0.0f;                                                       \
+      any_depth |= front;                                                                     \
+      any_bounds |= sr_in_bounds(smp, p.h, p.w);                                              \
+      (o)[16] = front ? 1.0f : 0.0f;                                                          \
+      (o)[17] = smp.zp;                                                                       \
+      (o)[18] = 0.0f;                                                                         \
+    }
 #define SR_SB __builtin_amdgcn_sched_barrier(0);
 
     // costs of this unit's planes, kept until the 16-byte stores at its end: in registers (select chain), or -- in the
     // variants that stream W1 and have neither registers nor a full LDS -- in a wave-private LDS strip
     constexpr bool CST_LDS = !W1_LDS;
     const int cst_base = SR_LDS_W3_FLOATS + W2_FLOATS +
-                         __builtin_amdgcn_readfirstlane(threadIdx.x >> 6) * (SR_PLANE_CHUNK * 64);   // scalar
+                         wid * (SR_PLANE_CHUNK * 64);   // scalar
     float cst[SR_PLANE_CHUNK];
 #pragma unroll
     for (int q = 0; q < SR_PLANE_CHUNK; ++q) cst[q] = 0.0f;
@@ -359,52 +399,95 @@ __global__ __launch_bounds__(256, 1) void sr_mlp_volume_kernel(SrMlpParams p) {
       }
       any_depth = false; any_bounds = false;
       f32x16 acc[2][4];
+      // per plane, so that the channels a dead view leaves unwritten (and nobody reads) are not live across layer 2
+      float f[SR_VIEW_SLOTS], fn[SR_VIEW_SLOTS];
 
-      {  // view 0, not overlapped
-        issue_view(0);
-        SR_RAY_A(f, geom_b, 0) SR_RAY_B(f) SR_RAY_C(f)
+      bool dc = project_view(0), dn;  // is the view being multiplied / being assembled dead?
+      if (!dc) {  // view 0, not overlapped
+        load_taps(0);
+        SR_RAY_A0(f, 0) SR_RAY_B(f) SR_RAY_C(f)
         SR_INTERP2(f, 0, 0) SR_INTERP2(f, 0, 1) SR_INTERP2(f, 1, 0) SR_INTERP2(f, 1, 1)
         SR_INTERP2(f, 2, 0) SR_INTERP2(f, 2, 1) SR_INTERP2(f, 3, 0) SR_INTERP2(f, 3, 1)
         SR_DOT(f)
+      } else {
+        SR_RAY_A0(f, 0) SR_RAY_B(f) SR_RAY_C(f)
+        SR_DOT_DEAD(f)
+        f[0] = f[1] = 0.0f;  // named (not used) by the select in front of the first step
       }
-      // ---- layer 1, software-pipelined over views: the feature vector of view k+1 is assembled in 12 small
-      // VALU pieces, each placed in the shadow of one k-step (8 MFMAs = 512 cycles) of view k; its 16 tap
-      // loads are issued before step 0 and first touched at step 3.  sched_barrier(0) pins the placement.
-      // view 0's first step takes the hoisted invariant part as its C operand; the loop below handles the rest
+      // ---- layer 1, software-pipelined over views: the feature vector of view k+1 is assembled in small VALU
+      // pieces, each placed in the shadow of one k-step (8 MFMAs = 512 cycles) of view k; its 16 tap loads are
+      // issued before the first step.  sched_barrier(0) pins the placement.  Four straight-line bodies, selected by
+      // scalar branches per view (so every tap load is consumed inside the body that issued it and no s_waitcnt has to
+      // be pessimistic behind a join):
+      //   view k live: steps 0..11; the taps of view k+1 are first touched at step 7 (>= 3.5k cycles after issue)
+      //   view k dead: steps 8..11 only (slots 16..23: mask, z', rays, angle, plane depth); the taps of view k+1 are
+      //                first touched at step 10
+      //   view k+1 dead: no tap loads, no interpolation, no dot product
+      // The executed k-steps keep their ascending (view, step) order, so every accumulator sees the same sequence of
+      // non-zero additions as without the skip.  The last iteration has no view k+1: it re-derives the metadata of
+      // view K-1 as a dead view (any_depth / any_bounds are ORs: idempotent), nothing reads it.
+      // The first executed step of view 0 takes the hoisted invariant part as its C operand (no accumulator copy).
 #define SR_STEP(t)                                           \
         wN = wk[((t) + 1 < VS ? (t) + 1 : (t)) * 64];       \
         sr_l1_step(acc, wA, f[2 * (t)], f[2 * (t) + 1]);     \
         wA = wN;
-#define SR_VIEW_BODY(FIRST)                                                            \
+#define SR_IF_LIVE(ND, x) if (!(ND)) { x }
+#define SR_VIEW_BODY(FIRST, CD, ND)                                                    \
         {                                                                              \
-          const int kn = min(k + 1, p.K - 1); /* last iteration re-derives view K-1 */ \
-          const float* g = geom_b + kn * SR_GEOM_STRIDE;                               \
-          issue_view(kn);                                                              \
+          if (!(ND)) load_taps(kn);                                                    \
           const float4* wk = W1p + (size_t)(VS * k) * 64 + lane;                       \
-          float4 wA = wk[0], wN;                                                       \
+          float4 wA = wk[((CD) ? 8 : 0) * 64 + ((FIRST) ? 64 : 0)], wN;                \
           SR_SB                                                                        \
-          if (FIRST) { wN = wk[64]; sr_l1_step_init(acc, hc, wA, f[0], f[1]); wA = wN; } \
-          else { SR_STEP(0) }                                                          \
-          SR_RAY_A(fn, g, kn) SR_SB                                                    \
-          SR_STEP(1) SR_RAY_B(fn) SR_SB                                                \
-          SR_STEP(2) SR_RAY_C(fn) SR_SB                                                \
-          SR_STEP(3) SR_SB /* taps not touched before step 7 (>= 3.5k cycles after issue) */ \
-          SR_STEP(4) SR_SB                                                             \
-          SR_STEP(5) SR_SB                                                             \
-          SR_STEP(6) SR_SB                                                             \
-          SR_STEP(7) SR_INTERP2(fn, 0, 0) SR_INTERP2(fn, 0, 1) SR_SB                   \
-          SR_STEP(8) SR_INTERP2(fn, 1, 0) SR_INTERP2(fn, 1, 1) SR_SB                   \
-          SR_STEP(9) SR_INTERP2(fn, 2, 0) SR_INTERP2(fn, 2, 1) SR_SB                   \
-          SR_STEP(10) SR_INTERP2(fn, 3, 0) SR_SB                                       \
-          SR_STEP(11) SR_INTERP2(fn, 3, 1) SR_DOT(fn) SR_SB                            \
-          _Pragma("unroll") for (int t = 0; t < SR_VIEW_SLOTS; ++t) f[t] = fn[t];      \
+          if (!(CD)) {                                                                 \
+            if (!(FIRST)) { SR_STEP(0) SR_RAY_A0(fn, kn) SR_SB }                     \
+            SR_STEP(1) if (FIRST) { SR_RAY_A0(fn, kn) } SR_RAY_B(fn) SR_SB           \
+            SR_STEP(2) SR_RAY_C(fn) SR_SB                                              \
+            SR_STEP(3) SR_SB                                                           \
+            SR_STEP(4) SR_SB                                                           \
+            SR_STEP(5) SR_SB                                                           \
+            SR_STEP(6) SR_SB                                                           \
+            SR_STEP(7) SR_IF_LIVE(ND, SR_INTERP2(fn, 0, 0) SR_INTERP2(fn, 0, 1)) SR_SB \
+            SR_STEP(8) SR_IF_LIVE(ND, SR_INTERP2(fn, 1, 0) SR_INTERP2(fn, 1, 1)) SR_SB \
+            SR_STEP(9) SR_IF_LIVE(ND, SR_INTERP2(fn, 2, 0) SR_INTERP2(fn, 2, 1)) SR_SB \
+            SR_STEP(10) SR_IF_LIVE(ND, SR_INTERP2(fn, 3, 0)) SR_SB                     \
+            SR_STEP(11) if (ND) { SR_DOT_DEAD(fn) } else { SR_INTERP2(fn, 3, 1) SR_DOT(fn) } SR_SB \
+          } else {                                                                     \
+            if (!(FIRST)) { SR_STEP(8) SR_RAY_A0(fn, kn) SR_SB }                     \
+            SR_STEP(9) if (FIRST) { SR_RAY_A0(fn, kn) } SR_RAY_B(fn) SR_RAY_C(fn) SR_SB \
+            SR_STEP(10) SR_IF_LIVE(ND, SR_INTERP2(fn, 0, 0) SR_INTERP2(fn, 0, 1)       \
+                                       SR_INTERP2(fn, 1, 0) SR_INTERP2(fn, 1, 1)) SR_SB \
+            SR_STEP(11) if (ND) { SR_DOT_DEAD(fn) } else {                             \
+              SR_INTERP2(fn, 2, 0) SR_INTERP2(fn, 2, 1) SR_INTERP2(fn, 3, 0) SR_INTERP2(fn, 3, 1) SR_DOT(fn) } SR_SB \
+          }                                                                            \
+          _Pragma("unroll") for (int t = (ND) ? 16 : 0; t < SR_VIEW_SLOTS; ++t) f[t] = fn[t]; \
         }
+      // The four bodies are four if-without-else in a row on four flags the compiler cannot relate to each other
+      // (sr_opaque): hipcc flattens an if / else between live accumulators into a predicated chain whose joins carry
+      // undefined accumulator values, and then copies (128 v_accvgpr_mov per view) and spills them.
+#define SR_VIEW(FIRST)                                                                 \
+        {                                                                              \
+          const int kn = min(k + 1, p.K - 1);                                          \
+          dn = project_view(kn) | (k + 1 >= p.K);                                      \
+          const int ll = sr_opaque(!dc & !dn), ld = sr_opaque(!dc & dn);               \
+          const int dl = sr_opaque(dc & !dn), dd = sr_opaque(dc & dn);                 \
+          if (ll) SR_VIEW_BODY(FIRST, false, false)                                    \
+          if (ld) SR_VIEW_BODY(FIRST, false, true)                                     \
+          if (dl) SR_VIEW_BODY(FIRST, true, false)                                     \
+          if (dd) SR_VIEW_BODY(FIRST, true, true)                                      \
+          dc = dn;                                                                     \
+        }
+      {  // the first executed step of view 0 (step 0, or step 8 when the view is dead) takes the hoisted invariant part
+         // as its C operand: no accumulator copy.  ONE site for both cases, outside the bodies below: with the
+         // step that reads hc under a branch, hipcc evicts hc around layer 2 (80 accumulators to scratch per plane).
+        const float4 w0 = W1p[(size_t)(dc ? 8 * 64 : 0) + lane];
+        sr_l1_step_init(acc, hc, w0, dc ? f[16] : f[0], dc ? f[17] : f[1]);
+      }
       {
         const int k = 0;
-        SR_VIEW_BODY(true)
+        SR_VIEW(true)
       }
 #pragma unroll 1
-      for (int k = 1; k < p.K; ++k) SR_VIEW_BODY(false)
+      for (int k = 1; k < p.K; ++k) SR_VIEW(false)
 
       // layer 2: the layer-1 accumulators, passed through LeakyReLU(slope) = max(v, slope*v) (networks.py:139,
       // 0 < slope < 1) on the fly, are the B operands; W2 streams from L2 three steps ahead
