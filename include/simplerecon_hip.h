@@ -1030,6 +1030,73 @@ int sr_frames_depth(const void* in, int in_is_int32, int B, int h, int w, const 
                     int W, float scale, float min_valid, float max_valid, int flip, float* depth, float* mask,
                     uint8_t* mask_b, void* stream);
 
+/* Colour jitter: transforms.ColorJitter on the to_tensor image, which the reference's loader runs on every frame of a
+ * training tuple before the flip and the normalisation (generic_mvs_dataset.py:517-525, ColorJitter(0.2, 0.2, 0.2,
+ * 0.2)).  torchvision is not a dependency of this library and is absent where it was written: what follows restates
+ * the published tensor path (ColorJitter.forward, functional_tensor) and PARITY AGAINST THE PACKAGE ITSELF IS UNPINNED.
+ * tests/jitter_oracle.py is the same rule in torch's CPU operations.
+ *
+ * Input: the resized 8-bit image uint8 [B,H,W,3] interleaved (what sr_frames_resize writes), x = float(v) / 255.0f per
+ * channel.  Every operation below is a separately rounded fp32 operation (no fused multiply-add, correctly rounded
+ * division), in the order written.
+ *     gray(x)        = 0.2989 r + 0.587 g + 0.114 b
+ *     blend(a, b, f) = clamp(f a + (1 - f) b, 0, 1); 1 - f is computed by the host in double and passed as a second fp32
+ *                      number, as torch passes a Python scalar.  Every operator ends in this clamp.
+ *     0 brightness   blend(x, 0, f) = clamp(f x)
+ *     1 contrast     blend(x, m, f), m = the mean over all pixels of gray(x) of the image as it stands when the
+ *                    operator runs (summed in double here, divided by H W in double, rounded to fp32)
+ *     2 saturation   blend(x, gray(x), f) per pixel
+ *     3 hue          rgb2hsv, h = (h + f) mod 1 with Python's sign convention, hsv2rgb:
+ *         rgb2hsv: maxc / minc over the channels; eq = maxc == minc; cr = maxc - minc; s = cr / (eq ? 1 : maxc);
+ *                  d = eq ? 1 : cr; (rc, gc, bc) = (maxc - (r, g, b)) / d;
+ *                  h' = (maxc == r) ? bc - gc : (maxc == g) ? 2 + rc - bc : 4 + gc - rc;
+ *                  h = fmod(h' / 6 + 1, 1); v = maxc
+ *         hsv2rgb: i = floor(6 h); fr = 6 h - i; i = i mod 6; p = clamp(v (1 - s)); q = clamp(v (1 - s fr));
+ *                  t = clamp(v (1 - s (1 - fr))); rgb = (v,t,p), (q,v,p), (p,v,t), (p,q,v), (t,p,v), (v,p,q) for i = 0..5
+ *         (a mod 1 is a - floor(a): the shifted hue of a slightly negative sum rounds to 1.0, which hsv2rgb takes as 0)
+ * The rule is continuous across hue sectors, ties of the largest channel and greys.
+ *
+ * Parameters (ColorJitter.__init__ / get_params; drawn by simplerecon_amd/frames.py jitter_params): a value a for
+ * brightness, contrast or saturation means the range [max(0, 1 - a), 1 + a], for hue [-a, a] with 0 <= a <= 0.5; a
+ * (lo, hi) pair is taken as given; a range that collapses to the neutral value switches the operator off, and an
+ * operator that is off is neither drawn nor applied.  One draw per frame: order = randperm(4), then for each operator
+ * that is on, in the order brightness, contrast, saturation, hue, one uniform_(lo, hi) as fp32; the operators run in
+ * `order`.  The loader draws the flip once per tuple first, then the jitter of each frame, the reference frame first.
+ *
+ * Table `params`, on the device, SR_FRAMES_JITTER_PARAM_WORDS 32-bit words per frame: [0..3] int32 operator ids in the
+ * order they run, -1 for an empty slot; then fp32 [4] brightness f, [5] 1 - f, [6] contrast f, [7] 1 - f,
+ * [8] saturation f, [9] 1 - f, [10] hue shift, [11] unused.  The kernels trust it: sr_frames_jitter_check_params reads
+ * the HOST copy before it is sent and returns SR_ERR_INVALID_ARGUMENT for an id outside -1..3 or an operator that
+ * appears twice in a frame; a kernel passes over a slot it does not know.
+ *
+ * sr_frames_jitter writes `out` fp32 planes [B,3,H,W], columns mirrored when flip, (x - mean_c) / std_c with the
+ * ImageNet constants rounded to fp32 when normalise (a rounded subtract, then a rounded divide: to_tensor + normalize
+ * of an image with no operator on gives the bytes of sr_frames_resize's f32 output).  Two launches:
+ *   mean pass   only when `scratch` is given.  Workgroup x of frame b applies the operators in front of contrast to
+ *               its pixels, adds their grey in double (registers, wave butterfly, LDS) and writes partial [b][x]; at
+ *               most SR_FRAMES_JITTER_MAX_PARTIALS workgroups per frame, each striding over the frame.  A frame
+ *               without contrast leaves at once.
+ *   apply pass  adds the frame's partials in one fixed tree (no atomics: equal bytes on every run), recomputes the
+ *               whole chain per pixel, flips, normalises, stores.  A lane owns 4 consecutive pixels of a row: when
+ *               W % 4 == 0, `in_u8` is 4-byte and `out` 16-byte aligned it loads three words and stores 16 bytes per
+ *               plane (with flip, its four pixels reversed); otherwise it moves single bytes and floats, the last
+ *               lane of a row fewer than four.
+ * scratch = NULL says no frame has contrast on: the mean pass is not launched and a contrast slot is passed over.
+ * Otherwise scratch is 8-byte aligned with at least sr_frames_jitter_scratch_bytes(B, H, W) bytes
+ * (SR_ERR_WORKSPACE_TOO_SMALL).  Both passes read 3 bytes per pixel and the apply pass writes 12: 18 bytes per pixel.
+ * All offsets are 64-bit.  SR_ERR_UNSUPPORTED: a side above SR_FRAMES_MAX_SIDE, B above SR_FRAMES_MAX_BATCH.  No
+ * call allocates or synchronises with the host; both launches can be captured in a HIP graph. */
+#define SR_FRAMES_JITTER_PARAM_WORDS 12
+#define SR_FRAMES_JITTER_MAX_PARTIALS 128
+#define SR_FRAMES_JITTER_BRIGHTNESS 0
+#define SR_FRAMES_JITTER_CONTRAST 1
+#define SR_FRAMES_JITTER_SATURATION 2
+#define SR_FRAMES_JITTER_HUE 3
+size_t sr_frames_jitter_scratch_bytes(int B, int H, int W);
+int sr_frames_jitter_check_params(const void* params_host, int B);
+int sr_frames_jitter(const uint8_t* in_u8, int B, int H, int W, const void* params, float* out, int flip, int normalise,
+                     void* scratch, size_t scratch_bytes, void* stream);
+
 /* ------------------------------------------------------------------ visualisation ----
  *
  * The pictures the reference makes with utils/visualization_utils.py (colormap_image, quick_viz_export) and its

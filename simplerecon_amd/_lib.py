@@ -208,6 +208,9 @@ SIGNATURES = {
     "sr_frames_resize_fits_lds": (_i, [_i, _i, _i, _i]),
     "sr_frames_resize": (_i, [_p, _i, _i, _i, _i, _p, _i, _p, _i, _i, _p, _p, _i, _i, _i, _i, _p, _p]),
     "sr_frames_depth": (_i, [_p, _i, _i, _i, _i, _p, _p, _i, _i, _f, _f, _f, _i, _p, _p, _p, _p]),
+    "sr_frames_jitter_scratch_bytes": (_sz, [_i, _i, _i]),
+    "sr_frames_jitter_check_params": (_i, [_p, _i]),
+    "sr_frames_jitter": (_i, [_p, _i, _i, _i, _p, _p, _i, _i, _p, _sz, _p]),
     "sr_viz_range_workspace_bytes": (_sz, [_i, _i64]),
     "sr_viz_range": (_i, [_p, _p, _i, _i, _i64, _i, _p, _p, _sz, _p]),
     "sr_viz_colormap": (_i, [_p, _p, _i, _i, _i64, _p, _p, _i64, _p, _i64, _f, _f, _f, _f, _f, _p, _p, _p]),

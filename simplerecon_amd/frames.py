@@ -1,8 +1,9 @@
-"""Frame preparation on HIP kernels (csrc/sr_frames.hip): from a decoded frame -- an 8-bit colour image, a 16-bit
-depth map, a pose and the depth sensor's intrinsics -- to the `cur_data` / `src_data` dictionaries DepthModel and
-evaluate consume, with the bits the reference's loader produces (datasets/generic_mvs_dataset.py get_frame,
-datasets/scannet_dataset.py load_intrinsics / load_target_size_depth_and_mask, utils/generic_utils.py
-read_image_file).  The rules are stated in include/simplerecon_hip.h, section "frame preparation".
+"""Frame preparation on HIP kernels (csrc/sr_frames.hip, csrc/sr_frames_jitter.hip): from a decoded frame -- an 8-bit
+colour image, a 16-bit depth map, a pose and the depth sensor's intrinsics -- to the `cur_data` / `src_data`
+dictionaries DepthModel and evaluate consume, with the bits the reference's loader produces
+(datasets/generic_mvs_dataset.py get_frame, datasets/scannet_dataset.py load_intrinsics /
+load_target_size_depth_and_mask, utils/generic_utils.py read_image_file).  The rules are stated in
+include/simplerecon_hip.h, section "frame preparation".
 
     resample_tables(in_size, out_size, resample) -> (first, count, weights_i32)     host, Pillow's coefficient rules
     nearest_table(in_size, out_size) -> int32 source indices                        host, Pillow's nearest rule
@@ -10,11 +11,19 @@ read_image_file).  The rules are stated in include/simplerecon_hip.h, section "f
     prepare_color(image_bhwc, height, width, ...) -> fp32 [B,3,H,W]                 + to_tensor + ImageNet normalise
     prepare_depth(depth_bhw, height, width, ...) -> (depth_b1hw, mask_b1hw, mask_b_b1hw)
     scaled_intrinsics(K_44, ...) -> {K_s{i}_b44, invK_s{i}_b44, ...}                host, the reference's operations
+    jitter_params(n, 0.2, 0.2, 0.2, 0.2, generator=None) -> JitterParams             host, ColorJitter's draws per frame
+    JitterParams.from_values(order, brightness, contrast, saturation, hue)          host, explicit values (None = off)
+    prepare_color_jittered(image_bhwc, height, width, params, ...) -> fp32 [B,3,H,W]   resize + ColorJitter + flip + normalise
     FramePreparer(...).frame(...) / .tuple(frames) -> get_frame's dictionary / (cur_data, src_data)
+    FramePreparer(color_jitter=(0.2, 0.2, 0.2, 0.2)).train_tuple(frames) -> the training split's tuple: random flip + jitter
+
+The colour jitter restates torchvision's published tensor path (the package is not a dependency and was absent where
+this was written): parity against the package itself is unpinned.  tests/jitter_oracle.py is the rule in torch's CPU
+operations; the kernels follow it within a few fp32 roundings (the mean of contrast is summed in another order).
 
 Out of scope:
   - reading and decoding image files (PNG / JPEG decoding stays on the host);
-  - ColorJitter, torchvision's random training augmentation;
+  - torchvision's PIL path, its other transforms, and jitter of fp32 images that did not come from 8-bit ones;
   - the per-dataset path and metadata conventions (which file holds the pose, the intrinsics, the depth size);
   - crop_image_to_target_ratio: the reference discards its result, so there it does nothing.
 A four-channel image is resized channel by channel (Pillow's CMYK / RGBX); Pillow premultiplies RGBA, this does not.
@@ -261,6 +270,139 @@ def prepare_color(image_bhwc, height, width, resample="bilinear", flip=False):
     return _resize(image_bhwc, height, width, resample, flip, True)
 
 
+JITTER_OPS = ("brightness", "contrast", "saturation", "hue")   # SR_FRAMES_JITTER_*: the ids of an operator order
+JITTER_WORDS = 12                                              # SR_FRAMES_JITTER_PARAM_WORDS
+_NEUTRAL = (1.0, 1.0, 1.0, 0.0)
+
+
+def jitter_range(name, value):
+    """ColorJitter's range of one argument (its _check_input): a number a gives [max(0, 1 - a), 1 + a], for hue
+    [-a, a] with 0 <= a <= 0.5; a (lo, hi) pair is taken as given; None, or a range that collapses to the neutral
+    value, switches the operator off.  Returns (lo, hi) or None."""
+    if name not in JITTER_OPS:
+        raise ValueError(f"name must be one of {JITTER_OPS}, got {name!r}")
+    if value is None:
+        return None
+    hue = name == "hue"
+    center, lo_bound, hi_bound = (0.0, -0.5, 0.5) if hue else (1.0, 0.0, math.inf)
+    if isinstance(value, (int, float, np.integer, np.floating)) and not isinstance(value, bool):
+        if value < 0:
+            raise ValueError(f"if {name} is a single number, it must be non negative")
+        lo, hi = center - float(value), center + float(value)
+        if not hue:
+            lo = max(lo, 0.0)
+    elif isinstance(value, (tuple, list)) and len(value) == 2:
+        lo, hi = float(value[0]), float(value[1])
+    else:
+        raise TypeError(f"{name} should be a single number or a list/tuple with length 2")
+    if not lo_bound <= lo <= hi <= hi_bound:
+        raise ValueError(f"{name} values should be between ({lo_bound}, {hi_bound}), got ({lo}, {hi})")
+    return None if lo == hi == center else (lo, hi)
+
+
+class JitterParams:
+    """The colour jitter of n frames: `order` int64 [n,4], the operator ids (0 brightness, 1 contrast, 2 saturation,
+    3 hue) in the order they run; `factors` float64 [n,4], indexed by operator id; `on`, four booleans, which
+    operators run at all (one answer for all frames, as ColorJitter's).  An operator that is off keeps its neutral
+    factor and is left out of the order the kernels see."""
+
+    def __init__(self, order, factors, on):
+        self.order = np.ascontiguousarray(order, dtype=np.int64)
+        self.factors = np.ascontiguousarray(factors, dtype=np.float64)
+        self.on = tuple(bool(v) for v in on)
+        if self.order.ndim != 2 or self.order.shape[1] != 4 or self.factors.shape != self.order.shape or \
+                len(self.on) != 4:
+            raise ValueError(f"order and factors must be [n,4] and `on` four booleans, got {self.order.shape}, "
+                             f"{self.factors.shape}, {len(self.on)}")
+        if (np.sort(self.order, axis=1) != np.arange(4)).any():
+            raise ValueError("every row of order must be a permutation of 0, 1, 2, 3")
+        if not np.isfinite(self.factors).all():
+            raise ValueError("the factors must be finite")
+        if (self.factors[:, :3] < 0).any() or (np.abs(self.factors[:, 3]) > 0.5).any():
+            raise ValueError("brightness, contrast and saturation factors are non-negative, a hue shift lies in "
+                             "[-0.5, 0.5]")
+
+    def __len__(self):
+        return int(self.order.shape[0])
+
+    @classmethod
+    def from_values(cls, order, brightness=None, contrast=None, saturation=None, hue=None):
+        """Explicit values: `order` [4] or [n,4]; each factor a number, n numbers, or None = that operator is off."""
+        order = np.asarray(order, dtype=np.int64)
+        order = order[None] if order.ndim == 1 else order
+        values = (brightness, contrast, saturation, hue)
+        n = max([order.shape[0]] + [np.size(v) for v in values if v is not None])
+        if order.ndim != 2 or order.shape[0] not in (1, n):
+            raise ValueError(f"order must be [4] or [{n},4], got {order.shape}")
+        factors = np.empty((n, 4), dtype=np.float64)
+        for k, v in enumerate(values):
+            v = np.asarray(_NEUTRAL[k] if v is None else v, dtype=np.float64).reshape(-1)
+            if v.size not in (1, n):
+                raise ValueError(f"{JITTER_OPS[k]}: {v.size} values for {n} frames")
+            factors[:, k] = v
+        return cls(np.broadcast_to(order, (n, 4)), factors, [v is not None for v in values])
+
+    def table(self):
+        """The kernels' table, int32 [n, 12] (include/simplerecon_hip.h): the operators that are on in the order they
+        run, -1 in the empty slots, then the bits of (f, 1 - f) of brightness, contrast and saturation and of the hue
+        shift.  1 - f is computed in double and both are rounded to fp32, as torch rounds a Python scalar."""
+        n = len(self)
+        slots = np.full((n, 4), -1, dtype=np.int32)
+        for i in range(n):
+            ops = [int(o) for o in self.order[i] if self.on[o]]
+            slots[i, :len(ops)] = ops
+        f = np.zeros((n, 8), dtype=np.float32)
+        for k in range(3):
+            f[:, 2 * k] = self.factors[:, k]
+            f[:, 2 * k + 1] = 1.0 - self.factors[:, k]
+        f[:, 6] = self.factors[:, 3]
+        return np.ascontiguousarray(np.concatenate([slots, f.view(np.int32)], axis=1))
+
+
+def jitter_params(n, brightness=0.2, contrast=0.2, saturation=0.2, hue=0.2, generator=None):
+    """ColorJitter(brightness, contrast, saturation, hue).get_params, once per frame for n frames, from torch's global
+    generator or from `generator`: per frame torch.randperm(4), then, for each operator that is on, in the order
+    brightness, contrast, saturation, hue, float(torch.empty(1).uniform_(lo, hi)).  An operator that is off draws
+    nothing."""
+    if isinstance(n, bool) or not isinstance(n, (int, np.integer)) or n < 1:
+        raise ValueError(f"n must be a positive int, got {n!r}")
+    ranges = [jitter_range(name, v) for name, v in zip(JITTER_OPS, (brightness, contrast, saturation, hue))]
+    order = np.empty((n, 4), dtype=np.int64)
+    factors = np.tile(np.array(_NEUTRAL, dtype=np.float64), (n, 1))
+    for i in range(n):
+        order[i] = torch.randperm(4, generator=generator).numpy()
+        for k, r in enumerate(ranges):
+            if r is not None:
+                factors[i, k] = float(torch.empty(1).uniform_(r[0], r[1], generator=generator))
+    return JitterParams(order, factors, [r is not None for r in ranges])
+
+
+def prepare_color_jittered(image_bhwc, height, width, params, resample="bilinear", flip=False, normalize=True):
+    """prepare_color with the training split's augmentation: Pillow's resize, to_tensor, ColorJitter with frame i's
+    `params` (a JitterParams of B frames), the optional x-flip, the ImageNet normalisation unless normalize=False.
+    fp32 [B,3,H,W].  The resize launch, then two for the whole batch (one when no frame has contrast on); the table
+    goes to the device in one copy.  With every operator off, or all factors neutral, the bytes of prepare_color."""
+    if not isinstance(params, JitterParams):
+        raise TypeError(f"params must be a JitterParams, got {type(params)}")
+    small = resize_u8(image_bhwc, height, width, resample)
+    B, H, W, C = (int(v) for v in small.shape)
+    if C != 3:
+        raise ValueError(f"image_bhwc must have 3 channels, got {C}")
+    if len(params) != B:
+        raise ValueError(f"params holds {len(params)} frames, the batch {B}")
+    table = params.table()
+    _lib.check(_lib.lib().sr_frames_jitter_check_params(table.ctypes.data, B), "sr_frames_jitter_check_params")
+    dev = small.device
+    with _lib.on_device(dev):
+        table_dev = torch.from_numpy(table).to(dev)
+        nbytes = int(_lib.lib().sr_frames_jitter_scratch_bytes(B, H, W)) if params.on[1] else 0
+        scratch = torch.empty(nbytes // 8, dtype=torch.float64, device=dev) if nbytes else None
+        out = torch.empty((B, 3, H, W), dtype=torch.float32, device=dev)
+        _lib.call("sr_frames_jitter", dev, small, B, H, W, table_dev, out, int(bool(flip)), int(bool(normalize)), scratch,
+                  nbytes)
+    return out
+
+
 def prepare_depth(depth_bhw, height=None, width=None, scale=1e-3, min_valid=1e-3, max_valid=10.0, flip=False):
     """The reference's depth loading for B sensor depth maps [B,h,w] (uint16 or int32, values 0..65535): Pillow's
     nearest resize to height x width (None: the native size), depth = float(v) * scale, valid where
@@ -335,7 +477,7 @@ class FramePreparer:
     def __init__(self, image_height=384, image_width=512, depth_height=192, depth_width=256, high_res_image_height=480,
                  high_res_image_width=640, include_high_res_color=False, include_full_res_depth=False,
                  include_full_depth_K=False, min_valid_depth=1e-3, max_valid_depth=10.0, resample="bilinear",
-                 device=None):
+                 device=None, color_jitter=None):
         _check_sizes(image_height=image_height, image_width=image_width, depth_height=depth_height,
                      depth_width=depth_width, high_res_image_height=high_res_image_height,
                      high_res_image_width=high_res_image_width)
@@ -350,6 +492,14 @@ class FramePreparer:
         self.min_valid_depth, self.max_valid_depth = float(min_valid_depth), float(max_valid_depth)
         self.resample = resample
         self.device = device
+        # the dataset's color_transform: None, or ColorJitter's four arguments (brightness, contrast, saturation, hue)
+        if color_jitter is not None:
+            color_jitter = tuple(color_jitter)
+            if len(color_jitter) != 4:
+                raise ValueError("color_jitter is None or (brightness, contrast, saturation, hue)")
+            for name, v in zip(JITTER_OPS, color_jitter):
+                jitter_range(name, v)
+        self.color_jitter = color_jitter
 
     def _batch(self, name, items, dtypes, ndim, dev):
         """One device tensor [N, ...] from N same-sized images (a single copy when they come from the host)."""
@@ -368,9 +518,14 @@ class FramePreparer:
             return torch.stack([t.view(torch.int16) for t in parts]).view(torch.uint16)
         return torch.stack(parts)
 
-    def _prepare(self, frames, flip, native_depth_size=None):
+    def _prepare(self, frames, flip, native_depth_size=None, jitter=None):
         """get_frame for N frames [(color, depth or None, world_T_cam, K_depth_native, frame_id_string or None)]:
-        the images of all N go through one launch per output, the 4x4 matrices through the host."""
+        the images of all N go through one launch per output, the 4x4 matrices through the host.  jitter: a
+        JitterParams of N frames for image_b3hw (get_frame's color_transform), or None."""
+        if jitter is not None and not isinstance(jitter, JitterParams):
+            raise TypeError(f"jitter must be a JitterParams or None, got {type(jitter)}")
+        if jitter is not None and len(jitter) != len(frames):
+            raise ValueError(f"jitter holds {len(jitter)} frames, the call {len(frames)}")
         dev = _device(self.device)
         flip = bool(flip)
         colors = self._batch("color_u8_hwc", [f[0] for f in frames], (torch.uint8,), 3, dev)
@@ -378,7 +533,8 @@ class FramePreparer:
         if any(have_depth) != all(have_depth):
             raise ValueError("the frames of a tuple come all with depth or all without")
         out = [{} for _ in frames]
-        image = prepare_color(colors, self.image_height, self.image_width, self.resample, flip)
+        image = prepare_color(colors, self.image_height, self.image_width, self.resample, flip) if jitter is None else \
+            prepare_color_jittered(colors, self.image_height, self.image_width, jitter, self.resample, flip)
         high = prepare_color(colors, self.high_res_image_height, self.high_res_image_width, self.resample,
                              flip) if self.include_high_res_color else None
         target = full = None
@@ -427,27 +583,39 @@ class FramePreparer:
         return f if len(f) == 5 else f + (None,)
 
     def frame(self, color_u8_hwc, depth_u16_hw, world_T_cam_44, K_depth_native_44, flip=False, frame_id_string=None,
-              native_depth_size=None):
+              native_depth_size=None, jitter=None):
         """One get_frame dictionary (no batch dimension; tensors on the device): image_b3hw, world_T_cam_b44,
         cam_T_world_b44, K_s{i}_b44 / invK_s{i}_b44, depth_b1hw, mask_b1hw, mask_b_b1hw, and what the include_*
         options add.  color_u8_hwc uint8 [h,w,3]; depth_u16_hw uint16 / int32 [h',w'] in millimetres;
         K_depth_native_44 the intrinsics at the depth map's native size.  depth_u16_hw may be None (get_frame's
-        load_depth=False: no depth keys); native_depth_size=(height, width) then gives that size."""
+        load_depth=False: no depth keys); native_depth_size=(height, width) then gives that size.  jitter: a
+        JitterParams of one frame, the colour jitter of image_b3hw (no other key changes), or None."""
         out, _, _ = self._prepare([(color_u8_hwc, depth_u16_hw, world_T_cam_44, K_depth_native_44, frame_id_string)],
-                                  flip, native_depth_size)
+                                  flip, native_depth_size, jitter)
         return out[0]
 
-    def tuple(self, frames, flip=False, native_depth_size=None):
+    def tuple(self, frames, flip=False, native_depth_size=None, jitter=None):
         """(cur_data, src_data) of one MVS tuple from a list of frames, the reference frame first, each
         (color_u8_hwc, depth_u16_hw, world_T_cam_44, K_depth_native_44[, frame_id_string]).  src_data stacks the
         sources along a first dimension, ordered by the reference's pose penalty with respect to the reference frame
-        (generic_mvs_dataset.py:643-659)."""
+        (generic_mvs_dataset.py:643-659).  jitter: a JitterParams with one entry per frame, in the order of `frames`:
+        the colour jitter of every image_b3hw (high_res_color_b3hw is never jittered), or None."""
         frames = [self._as_frame(f) for f in frames]
         if len(frames) < 2:
             raise ValueError("a tuple needs the reference frame and at least one source frame")
-        out, world_T_cam, cam_T_world = self._prepare(frames, flip, native_depth_size)
+        out, world_T_cam, cam_T_world = self._prepare(frames, flip, native_depth_size, jitter)
         order = sort_sources_by_pose_penalty(cam_T_world[0], np.stack(world_T_cam[1:]))
         src = [out[1 + i] for i in order]
         src_data = {k: [s[k] for s in src] if k == "frame_id_string" else torch.stack([s[k] for s in src])
                     for k in src[0]}
         return out[0], src_data
+
+    def train_tuple(self, frames, generator=None, native_depth_size=None):
+        """tuple() as the training split draws it (generic_mvs_dataset.py:613-634, 517-519): the flip first, once for
+        the tuple (torch.rand(1).item() < 0.5), then, with color_jitter set, the jitter of each frame in the order of
+        `frames`, the reference frame first.  Draws from torch's global generator or from `generator`."""
+        frames = list(frames)
+        flip = torch.rand(1, generator=generator).item() < 0.5
+        jitter = None if self.color_jitter is None else jitter_params(len(frames), *self.color_jitter,
+                                                                      generator=generator)
+        return self.tuple(frames, flip=flip, native_depth_size=native_depth_size, jitter=jitter)
