@@ -20,6 +20,11 @@ int sr_opt(int id);
 // CU count of the CURRENT device, cached per device index (sr_options.hip); 256 when the runtime cannot be asked
 int sr_device_cus();
 
+// Allows `kernel` (the host-side function pointer) `bytes` of dynamic LDS on the CURRENT device
+// (hipFuncAttributeMaxDynamicSharedMemorySize).  The largest size granted is remembered per (kernel, device), so the
+// runtime is asked once and again only for a larger size; a refusal is not remembered.  Returns the runtime's error.
+hipError_t sr_allow_lds(const void* kernel, size_t bytes);
+
 static inline int sr_hip_rc(hipError_t e) { return e == hipSuccess ? SR_OK : SR_ERR_HIP_BASE + (int)e; }
 
 static inline size_t sr_align_up(size_t v, size_t a) { return (v + a - 1) / a * a; }
@@ -50,6 +55,7 @@ struct SrSample {
 };
 
 typedef float sr_f2v __attribute__((ext_vector_type(2)));
+typedef float f32x16 __attribute__((ext_vector_type(16)));   // accumulator of a 32x32 fp32 MFMA
 
 // Integer tap origin (floats, unclamped) and the four bilinear weights of the unnormalised sampling position (ix, iy)
 // (grid_sample, bilinear, zeros padding, align_corners=False): weights of out-of-image taps are zero.

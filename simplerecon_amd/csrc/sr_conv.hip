@@ -21,8 +21,7 @@
 #include <stdlib.h>
 
 #include "sr_common.h"
-
-typedef float f32x16 __attribute__((ext_vector_type(16)));
+#include "sr_view.h"
 
 // tuning knobs: weight prefetch depth with one N-tile, residual prefetch in the last slab
 #ifndef SR_NB1
@@ -516,8 +515,6 @@ extern "C" int sr_conv_pack_weights(const float* weight, int Cout, int Cin, int 
   return sr_hip_rc(hipGetLastError());
 }
 
-static int sr_num_cus() { return sr_device_cus(); }
-
 template <int KS, int S, int MT, int CM>
 static int sr_conv_launch(SrConvParams& p, int B, int nt, hipStream_t stream) {
   using G = SrConvGeom<KS, S, MT, CM>;
@@ -527,16 +524,16 @@ static int sr_conv_launch(SrConvParams& p, int B, int nt, hipStream_t stream) {
   p.total_tiles = p.tiles_x * p.tiles_y * p.co_blocks * B;
   if (p.ksplit > 1) {   // split-K plan (1x1 / stride 1 only, see sr_conv2d_dispatch): fill the 2-per-CU slots once
     const int chunks = p.G / (G::CK / 8);
-    int ks = (2 * sr_num_cus()) / p.total_tiles;
+    int ks = (2 * sr_device_cus()) / p.total_tiles;
     // 3x3 / stride 2: a work item is 9 taps deep and the finish is a second launch -- measured (scripts/conv_s2_sweep.py): 72 items x
     // 16 slabs 56 -> 28 us split 8 ways, 150 items x 4 slabs 19 -> 28 us split in two, 144 items at batch 8 94 -> 102 us split in three
-    if (KS == 3 && 2 * p.total_tiles > sr_num_cus()) ks = 1;
+    if (KS == 3 && 2 * p.total_tiles > sr_device_cus()) ks = 1;
     if (ks > chunks / 2) ks = chunks / 2;
     if (ks > p.ksplit) ks = p.ksplit;
     p.ksplit = ks < 2 ? 1 : ks;
     p.total_tiles *= p.ksplit;
   }
-  int blocks = sr_num_cus() * (KS == 1 ? SR_CONV_BLOCKS_PER_CU : 2);  // persistent grid: workgroups per CU (register / LDS limit)
+  int blocks = sr_device_cus() * (KS == 1 ? SR_CONV_BLOCKS_PER_CU : 2);  // persistent grid: workgroups per CU (register / LDS limit)
   if (blocks > p.total_tiles) blocks = p.total_tiles;
   dim3 grid(blocks), block(256);
   const bool v4 = p.vec4 && (p.Cin % 4 == 0);
@@ -554,7 +551,7 @@ static int sr_conv_launch(SrConvParams& p, int B, int nt, hipStream_t stream) {
 // Padding waste (partial tiles) and tail quantisation both show up in the tile count.
 struct SrConvCfg { int shape, nt; };
 static SrConvCfg sr_conv_pick(const SrConvParams& p, int B, int stride, int ksize) {
-  const int cus = sr_num_cus();
+  const int cus = sr_device_cus();
   // staging cost per pixel tile relative to its MFMA work: negligible for 3x3 (one slab feeds 9 taps), large for 1x1
   const double stage_w = ksize == 1 ? 0.6 : 0.0;
   const int th[3] = {8, 4, 16}, tw[3] = {32, 32, 8}, mt[3] = {2, 1, 1};
@@ -604,10 +601,8 @@ static bool sr_conv_splitk_eligible(const float* out, int64_t out_sb, int out_sp
   const bool pw = ksize == 1 && stride == 1 && Cin >= 4 * SR_CK1;
   const bool s2 = ksize == 3 && stride == 2 && Cin >= 8 * sr_ck(3);   // r06: the deep down-convolutions of CVEncoder at batch 1
   if (!on || !(pw || s2) || Cout % 4 != 0) return false;
-  auto al = [](const void* q) { return (((uintptr_t)q) & 15) == 0; };
-  if (!al(out) || out_sp % 4 != 0 || out_sb % 4 != 0 || (bias && !al(bias))) return false;
-  if (res && (!al(res) || res_sp % 4 != 0 || res_sb % 4 != 0)) return false;
-  return true;
+  if (!sr_rows_aligned(out, out_sb, out_sp, 15, 4) || (bias && !sr_ptr_aligned(bias, 15))) return false;
+  return !res || sr_rows_aligned(res, res_sb, res_sp, 15, 4);
 }
 
 static int sr_conv2d_dispatch(const float* in, int64_t in_batch_stride, int in_pix_stride,
@@ -647,7 +642,7 @@ static int sr_conv2d_dispatch(const float* in, int64_t in_batch_stride, int in_p
     p.ksplit = fit < 2 ? 1 : (fit < SR_CONV_KSPLIT_MAX ? (int)fit : SR_CONV_KSPLIT_MAX);   // upper bound: the launch plans
     p.part = (float*)workspace;
   }
-  p.vec4 = (((uintptr_t)in & 15) == 0) && (in_pix_stride % 4 == 0) && (in_batch_stride % 4 == 0);
+  p.vec4 = sr_rows_aligned(in, in_batch_stride, in_pix_stride, 15, 4);
   hipStream_t stream = (hipStream_t)stream_;
   const SrConvCfg cfg = sr_conv_cfg(p, B, stride, ksize);
   const int c = cfg.shape, nt = cfg.nt;
@@ -715,7 +710,7 @@ extern "C" size_t sr_conv_splitk_workspace_bytes(int B, int H, int W, int Cin, i
   // nothing to gain
   const int64_t px = s2 ? (int64_t)B * ((H - 1) / 2 + 1) * ((W - 1) / 2 + 1) : (int64_t)B * H * W;
   const int64_t tiles = ((px + 127) / 128) * ((Cout + 31) / 32);
-  if (s2 ? 2 * tiles > sr_num_cus() : tiles >= 2 * sr_num_cus()) return 0;
+  if (s2 ? 2 * tiles > sr_device_cus() : tiles >= 2 * sr_device_cus()) return 0;
   return (size_t)SR_CONV_KSPLIT_MAX * px * Cout * sizeof(float);
 }
 
@@ -752,8 +747,8 @@ extern "C" int sr_upsample2x_nhwc_fwd(const float* in, int64_t in_batch_stride, 
   if (B < 0 || H <= 0 || W <= 0 || C <= 0) return SR_ERR_INVALID_ARGUMENT;
   if (B == 0) return SR_OK;
   if (!in || !out) return SR_ERR_INVALID_ARGUMENT;
-  const int vec4 = (((uintptr_t)in & 15) == 0) && (((uintptr_t)out & 15) == 0) && (in_pix_stride % 4 == 0) &&
-                   (out_pix_stride % 4 == 0) && (in_batch_stride % 4 == 0) && (out_batch_stride % 4 == 0);
+  const int vec4 = sr_rows_aligned(in, in_batch_stride, in_pix_stride, 15, 4) &&
+                   sr_rows_aligned(out, out_batch_stride, out_pix_stride, 15, 4);
   if (vec4 && C % 4 == 0 && sr_opt(SR_OPT_UPSAMPLE_QUAD)) {
     const int cq = C / 4;
     const int64_t rows = (int64_t)B * (H + 1);

@@ -14,21 +14,17 @@
 //   * no LDS, no barrier, no atomics, no K split: one wave owns MT x 32 pixels x NT x 32 channels and sums taps and channel
 //     steps in a fixed order -- two runs give the same bits.
 // bias + residual + LeakyReLU run in fp32 on the accumulator; one rounding on the way out.
-#include "sr_common.h"
+#include "sr_buffer.h"
+#include "sr_view.h"
 
 namespace {
-
-typedef float c16_f16v __attribute__((ext_vector_type(16)));
-typedef float c16_f4 __attribute__((ext_vector_type(4)));
-typedef unsigned c16_u4 __attribute__((ext_vector_type(4)));
-typedef unsigned c16_u2 __attribute__((ext_vector_type(2)));
 
 template <int IO> struct C16Fmt;
 template <> struct C16Fmt<1> {
   typedef _Float16 e;
   typedef _Float16 e4 __attribute__((ext_vector_type(4)));
   typedef _Float16 e8 __attribute__((ext_vector_type(8)));
-  static __device__ __forceinline__ c16_f16v mfma(c16_u4 a, c16_u4 b, c16_f16v c) {
+  static __device__ __forceinline__ f32x16 mfma(sr_u4 a, sr_u4 b, f32x16 c) {
     return __builtin_amdgcn_mfma_f32_32x32x16_f16(__builtin_bit_cast(e8, a), __builtin_bit_cast(e8, b), c, 0, 0, 0);
   }
 };
@@ -36,7 +32,7 @@ template <> struct C16Fmt<2> {
   typedef __bf16 e;
   typedef __bf16 e4 __attribute__((ext_vector_type(4)));
   typedef __bf16 e8 __attribute__((ext_vector_type(8)));
-  static __device__ __forceinline__ c16_f16v mfma(c16_u4 a, c16_u4 b, c16_f16v c) {
+  static __device__ __forceinline__ f32x16 mfma(sr_u4 a, sr_u4 b, f32x16 c) {
     return __builtin_amdgcn_mfma_f32_32x32x16_bf16(__builtin_bit_cast(e8, a), __builtin_bit_cast(e8, b), c, 0, 0, 0);
   }
 };
@@ -60,7 +56,7 @@ static inline int c16_tiles(int Cout) { return (Cout + 31) / 32; }
 
 // fp32 [Co][Ci][k][k] -> A-fragment records (see the head of the file); one thread per 16-byte record
 template <int IO>
-__global__ void sr_conv16_pack_kernel(const float* __restrict__ w, c16_u4* __restrict__ wp, int Co, int Ci, int k,
+__global__ void sr_conv16_pack_kernel(const float* __restrict__ w, sr_u4* __restrict__ wp, int Co, int Ci, int k,
                                       int csteps, int64_t records) {
   typedef typename C16Fmt<IO>::e8 e8;
   const int taps = k * k;
@@ -78,7 +74,7 @@ __global__ void sr_conv16_pack_kernel(const float* __restrict__ w, c16_u4* __res
       const float f = (co < Co && ci < Ci) ? w[((int64_t)co * Ci + ci) * taps + tap] : 0.0f;
       v[j] = (typename C16Fmt<IO>::e)f;   // round to nearest even; fp16 overflow -> inf
     }
-    wp[e] = __builtin_bit_cast(c16_u4, v);
+    wp[e] = __builtin_bit_cast(sr_u4, v);
   }
 }
 
@@ -111,7 +107,7 @@ __global__ __launch_bounds__(256) void sr_conv16_kernel(const SrConv16Params p) 
     in_img[m] = img[m] * p.in_sb;
   }
 
-  c16_f16v acc[MT][NT];
+  f32x16 acc[MT][NT];
 #pragma unroll
   for (int m = 0; m < MT; ++m)
 #pragma unroll
@@ -119,14 +115,14 @@ __global__ __launch_bounds__(256) void sr_conv16_kernel(const SrConv16Params p) 
 #pragma unroll
       for (int i = 0; i < 16; ++i) acc[m][n][i] = 0.0f;
 
-  const c16_u4 zero = {0u, 0u, 0u, 0u};
-  const c16_u4* wrec = (const c16_u4*)p.wp + lane;
+  const sr_u4 zero = {0u, 0u, 0u, 0u};
+  const sr_u4* wrec = (const sr_u4*)p.wp + lane;
   // Fragments of k-step (tap, cs): NT weight records, MT activation groups.  Every load is UNCONDITIONAL, from an address
   // clamped into the tensor (a conditional load makes the compiler wait for it at the end of its branch, which empties the
   // ring below); what must read as zero -- a tap outside the image, a channel group past Cin, a pixel past the last one, a
   // request past the last k-step -- is replaced by zero where the fragment is used (`bok`, `live`).  Tiles past the last one
   // re-read it: their results are never stored.
-  auto load = [&](int tap, int cs, bool live, c16_u4 (&af)[NT], c16_u4 (&bf)[MT], bool (&bok)[MT]) {
+  auto load = [&](int tap, int cs, bool live, sr_u4 (&af)[NT], sr_u4 (&bf)[MT], bool (&bok)[MT]) {
     const int kh = tap / p.k, kw = tap - kh * p.k;
     const int c = 16 * cs + 8 * hh;
     const bool cok = live & (c < p.Cin);
@@ -136,7 +132,7 @@ __global__ __launch_bounds__(256) void sr_conv16_kernel(const SrConv16Params p) 
       const int iy = iy0[m] + kh, ix = ix0[m] + kw;
       bok[m] = pv[m] & cok & ((unsigned)iy < (unsigned)p.H) & ((unsigned)ix < (unsigned)p.W);
       const int iyc = min(max(iy, 0), p.H - 1), ixc = min(max(ix, 0), p.W - 1);
-      bf[m] = *(const c16_u4*)(p.in + in_img[m] + ((int64_t)iyc * p.W + ixc) * p.in_sp + cc);
+      bf[m] = *(const sr_u4*)(p.in + in_img[m] + ((int64_t)iyc * p.W + ixc) * p.in_sp + cc);
     }
 #pragma unroll
     for (int n = 0; n < NT; ++n) {
@@ -147,7 +143,7 @@ __global__ __launch_bounds__(256) void sr_conv16_kernel(const SrConv16Params p) 
 
   // D-deep register ring: the fragments of k-step s + D - 1 are requested before the MFMAs of step s issue, so D - 1 steps of
   // loads are in flight behind the matrix pipe.  Requests past the last step re-read the last one and multiply as 0 x 0.
-  c16_u4 a[D][NT], b[D][MT];
+  sr_u4 a[D][NT], b[D][MT];
   bool bok[D][MT], live[D];
   const int steps = taps * p.csteps;
   int ltap = 0, lcs = 0, ls = 0;   // the next k-step to load
@@ -164,7 +160,7 @@ __global__ __launch_bounds__(256) void sr_conv16_kernel(const SrConv16Params p) 
 #pragma unroll
     for (int d = 0; d < D; ++d) {
       load_next((d + D - 1) % D);
-      c16_u4 af[NT], bf[MT];
+      sr_u4 af[NT], bf[MT];
 #pragma unroll
       for (int n = 0; n < NT; ++n) af[n] = live[d] ? a[d][n] : zero;
 #pragma unroll
@@ -198,18 +194,18 @@ __global__ __launch_bounds__(256) void sr_conv16_kernel(const SrConv16Params p) 
           for (int i = 0; i < 4; ++i) v[i] += p.bias[ch + i];
         }
         if (p.res) {
-          const c16_u2 rr = *(const c16_u2*)(p.res + r_off + ch);
-          const c16_f4 rf = __builtin_convertvector(__builtin_bit_cast(typename F::e4, rr), c16_f4);
+          const sr_u2 rr = *(const sr_u2*)(p.res + r_off + ch);
+          const sr_f4 rf = __builtin_convertvector(__builtin_bit_cast(typename F::e4, rr), sr_f4);
 #pragma unroll
           for (int i = 0; i < 4; ++i) v[i] += rf[i];
         }
         sr_activate_group(v, slope);
-        const c16_f4 vf = {v[0], v[1], v[2], v[3]};
+        const sr_f4 vf = {v[0], v[1], v[2], v[3]};
         if (p.out_f32) {
-          *(c16_f4*)((float*)p.out + o_off + ch) = vf;
+          *(sr_f4*)((float*)p.out + o_off + ch) = vf;
         } else {
           const typename F::e4 q = __builtin_convertvector(vf, typename F::e4);   // round to nearest even
-          *(c16_u2*)((uint16_t*)p.out + o_off + ch) = __builtin_bit_cast(c16_u2, q);
+          *(sr_u2*)((uint16_t*)p.out + o_off + ch) = __builtin_bit_cast(sr_u2, q);
         }
       }
     }
@@ -277,16 +273,16 @@ extern "C" size_t sr_conv16_packed_weight_bytes(int Cout, int Cin, int k) {
 extern "C" int sr_conv16_pack_weights(const float* weight, int Cout, int Cin, int k, int dtype, void* packed, void* stream_) {
   if (!weight || !packed || Cout <= 0 || Cin <= 0 || !(k == 1 || k == 3) || !(dtype == 1 || dtype == 2))
     return SR_ERR_INVALID_ARGUMENT;
-  if ((((uintptr_t)packed) & 15) != 0 || (((uintptr_t)weight) & 3) != 0) return SR_ERR_UNSUPPORTED;
+  if (!sr_ptr_aligned(packed, 15) || !sr_ptr_aligned(weight, 3)) return SR_ERR_UNSUPPORTED;
   const int csteps = c16_csteps(Cin);
   const int64_t records = (int64_t)c16_tiles(Cout) * k * k * csteps * 64;
   const unsigned grid = (unsigned)((records + 255) / 256 < 4096 ? (records + 255) / 256 : 4096);
   hipStream_t stream = (hipStream_t)stream_;
   if (dtype == 1)
-    hipLaunchKernelGGL(sr_conv16_pack_kernel<1>, dim3(grid), dim3(256), 0, stream, weight, (c16_u4*)packed, Cout, Cin, k, csteps,
+    hipLaunchKernelGGL(sr_conv16_pack_kernel<1>, dim3(grid), dim3(256), 0, stream, weight, (sr_u4*)packed, Cout, Cin, k, csteps,
                        records);
   else
-    hipLaunchKernelGGL(sr_conv16_pack_kernel<2>, dim3(grid), dim3(256), 0, stream, weight, (c16_u4*)packed, Cout, Cin, k, csteps,
+    hipLaunchKernelGGL(sr_conv16_pack_kernel<2>, dim3(grid), dim3(256), 0, stream, weight, (sr_u4*)packed, Cout, Cin, k, csteps,
                        records);
   return sr_hip_rc(hipGetLastError());
 }
@@ -303,13 +299,12 @@ extern "C" int sr_conv16_nhwc_fwd(const void* in, int64_t in_batch_stride, int i
   if (!sr_conv16_supported(B, H, W, Cin, Cout, k, stride)) return SR_ERR_UNSUPPORTED;
   if (leaky_slope < -1.5f) return SR_ERR_UNSUPPORTED;   // (SiLU: an inference-path activation)
   // eight channels = one 16-byte access on every 16-bit operand; fp32 output quads are 16 bytes as well
-  if (in_pix_stride % 8 != 0 || in_batch_stride % 8 != 0 || out_pix_stride % 8 != 0 || out_batch_stride % 8 != 0 ||
+  if (!sr_rows_aligned(in, in_batch_stride, in_pix_stride, 15, 8) || !sr_rows_aligned(out, out_batch_stride, out_pix_stride, 15, 8) ||
       in_pix_stride < Cin || out_pix_stride < Cout || in_batch_stride < 0 || out_batch_stride < 0 ||
-      (((uintptr_t)in) & 15) != 0 || (((uintptr_t)packed_w) & 15) != 0 || (((uintptr_t)out) & 15) != 0 ||
-      (bias && (((uintptr_t)bias) & 3) != 0))
+      !sr_ptr_aligned(packed_w, 15) || (bias && !sr_ptr_aligned(bias, 3)))
     return SR_ERR_UNSUPPORTED;
-  if (residual && (res_pix_stride % 8 != 0 || res_batch_stride % 8 != 0 || res_pix_stride < Cout || res_batch_stride < 0 ||
-                   (((uintptr_t)residual) & 15) != 0))
+  if (residual && (!sr_rows_aligned(residual, res_batch_stride, res_pix_stride, 15, 8) || res_pix_stride < Cout ||
+                   res_batch_stride < 0))
     return SR_ERR_UNSUPPORTED;
   const int pad = k / 2;
   SrConv16Params p;

@@ -17,8 +17,6 @@
 //   bilinear x2     = sr_upsample2x_bwd_nhwc, the exact adjoint of sr_upsample2x_nhwc_fwd (same clamped taps).
 #include "sr_common.h"
 
-typedef float f32x16 __attribute__((ext_vector_type(16)));
-
 // ------------------------------------------------------------------------------------------ weight gradient ----
 
 #define WG_P 32        // output pixels of a segment
@@ -275,9 +273,7 @@ extern "C" int sr_conv_wgrad_padded_nhwc(const float* in, int64_t in_batch_strid
   const bool pipe = stride == 1 && (int64_t)H * W * in_pix_stride < 0x7fffffffLL && (int64_t)Ho * Wo * g_pix_stride < 0x7fffffffLL;
 #define SR_WGRAD_LAUNCH(KSV, PV)                                                                                     \
   {                                                                                                                  \
-    hipError_t e = hipFuncSetAttribute((const void*)sr_conv_wgrad_kernel<KSV, PV>,                                   \
-                                       hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);                        \
-    if (e != hipSuccess) return sr_hip_rc(e);                                                                        \
+    if (hipError_t e = sr_allow_lds((const void*)sr_conv_wgrad_kernel<KSV, PV>, lds)) return sr_hip_rc(e);           \
     hipLaunchKernelGGL((sr_conv_wgrad_kernel<KSV, PV>), dim3(blocks * per), dim3(256), lds, stream, p);              \
   }
   if (ksize == 3 && pipe) SR_WGRAD_LAUNCH(3, true)

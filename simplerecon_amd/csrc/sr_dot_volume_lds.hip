@@ -24,7 +24,8 @@
 // atomic max; a small kernel turns the winning plane index into its depth.
 #include <stdlib.h>
 
-#include "sr_common.h"
+#include "sr_buffer.h"
+#include "sr_view.h"
 
 #define LT_H 8    // tile rows
 #define LT_W 32   // tile columns (a wave = 2 rows x 32 columns: every hardware 16-lane LDS group stays inside a row)
@@ -32,7 +33,7 @@
 
 typedef unsigned short sr_us2 __attribute__((ext_vector_type(2)));
 typedef float sr_f2 __attribute__((ext_vector_type(2)));
-typedef float sr_f4 __attribute__((ext_vector_type(4)));  // (arrays of HIP float4 structs are not promoted to registers)
+// (sr_f4 of sr_buffer.h: arrays of HIP float4 structs are not promoted to registers)
 
 template <bool MIN>
 __device__ __forceinline__ unsigned sr_pk16(unsigned a, unsigned b) {
@@ -175,7 +176,7 @@ __device__ __forceinline__ void sr_stage_load(const SrLdsCtx& c, sr_f4 (&v)[NU],
       const int ry = (int)(((unsigned)ch * rcp_nchunk) >> 16), cx = ch - ry * nchunk;   // (scalar)
       const int gy = min(max(miny - 1 + ry, 0), c.h - 1);                               // (scalar)
       const int gx = min(max(lane_x0 + cx * 16, 0), c.w - 1);
-      v[U] = __builtin_bit_cast(sr_f4, __builtin_amdgcn_raw_buffer_load_b128(rs_img, gx * 64 + (c.lane & 3) * 16, gy * c.w * 64, 0));
+      v[U] = sr_buf_load(rs_img, gx * 64 + (c.lane & 3) * 16, gy * c.w * 64);
       sr_stage_load<U + 1, NU, U0>(c, v, rcp_nchunk, nchunk, nchunks, lane_x0, miny, rs_img);
     }
   }
@@ -229,8 +230,7 @@ __device__ __forceinline__ void sr_lds_unit(SrLdsCtx& c, const unsigned (&xy)[G]
     // two batches (6 + the rest of the <= NU chunks of a wave): 24 staging registers instead of 40 keep the kernel
     // inside the 128-register budget of 4 workgroups per CU; typical boxes (<= 24 chunks) need the first batch only
     constexpr int NU = (CAP / 16 + 3) / 4, NA = NU < 6 ? NU : 6;
-    const __amdgpu_buffer_rsrc_t rs_img =
-        __builtin_amdgcn_make_buffer_rsrc(const_cast<float*>(c.img), 0, c.h * c.w * 64, 0x00020000);
+    const __amdgpu_buffer_rsrc_t rs_img = sr_rsrc(c.img, c.h * c.w * 64);   // (below 2^31: sr_launch_dot_volume_lds)
     const int lane_x0 = minx - 1 + (c.lane >> 2);
     {
       sr_f4 v[NA];
@@ -450,6 +450,9 @@ static void sr_launch_lds_variant(const SrDotParams& p, unsigned long long* keys
 
 int sr_launch_dot_volume_lds(const SrDotParams& p, unsigned long long* keys, hipStream_t stream) {
   if (p.w > 65000 || p.h > 65000) return SR_ERR_UNSUPPORTED;
+  // the staging loads address a source map of 64-byte texels through a buffer descriptor: its byte range (and the kernel's
+  // 32-bit `h * w * 64`) must stay below 2^31, i.e. h * w < 2^25; larger maps take the flat-addressed gather kernels
+  if (!sr_view_fits32((int64_t)p.h * p.w, 16, 16, 4)) return SR_ERR_UNSUPPORTED;
   // switches (option table): LDS buffer in texels <-> workgroups per CU (634: 4, 770: 3), planes per group (2 / 4 / 8), hull
   // culling on / off
   const int Genv = sr_opt(SR_OPT_DOT_LDS_G);

@@ -17,9 +17,8 @@
 #include <stdlib.h>
 #include <string.h>
 
-#include "sr_common.h"
-
-typedef float f32x16 __attribute__((ext_vector_type(16)));
+#include "sr_buffer.h"
+#include "sr_view.h"
 
 #define SR_HID 128          // hidden width of the matching MLP (reference cost_volume.py:402)
 // Layer-1 inputs are split into a depth-VARIANT part (per view: 16 warped channels, mask, z', dot, ray
@@ -589,7 +588,6 @@ __global__ __launch_bounds__(256, 1) void sr_mlp_volume_kernel(SrMlpParams p) {
 // fp32 kernel; a k-step now covers 16 inputs (8 per half-wave), so a view is two steps: its 16 warped channels, then its 8
 // metadata slots (upper k-half zero).  The layer-1 accumulators still ARE the layer-2 B operands (after LeakyReLU and
 // the split).  Not the default and not what bench.py's headline measures.
-typedef unsigned sr_u4v __attribute__((ext_vector_type(4)));
 
 template <int FMT> struct SrSplitFmt;
 template <> struct SrSplitFmt<1> {   // two bf16 pieces: 16-17 significant bits, fp32 exponent range
@@ -601,7 +599,7 @@ template <> struct SrSplitFmt<1> {   // two bf16 pieces: 16-17 significant bits,
     const sr_f2v v0 = {__uint_as_float(hi << 16), __uint_as_float(hi & 0xffff0000u)};
     lo = __builtin_bit_cast(unsigned, __builtin_convertvector(v - v0, e2));
   }
-  static __device__ __forceinline__ f32x16 mfma(sr_u4v a, sr_u4v b, f32x16 c) {
+  static __device__ __forceinline__ f32x16 mfma(sr_u4 a, sr_u4 b, f32x16 c) {
     return __builtin_amdgcn_mfma_f32_32x32x16_bf16(__builtin_bit_cast(e8, a), __builtin_bit_cast(e8, b), c, 0, 0, 0);
   }
 };
@@ -614,7 +612,7 @@ template <> struct SrSplitFmt<2> {   // two fp16 pieces: 22-24 significant bits 
     hi = __builtin_bit_cast(unsigned, h);
     lo = __builtin_bit_cast(unsigned, __builtin_convertvector(v - __builtin_convertvector(h, sr_f2v), e2));
   }
-  static __device__ __forceinline__ f32x16 mfma(sr_u4v a, sr_u4v b, f32x16 c) {
+  static __device__ __forceinline__ f32x16 mfma(sr_u4 a, sr_u4 b, f32x16 c) {
     return __builtin_amdgcn_mfma_f32_32x32x16_f16(__builtin_bit_cast(e8, a), __builtin_bit_cast(e8, b), c, 0, 0, 0);
   }
 };
@@ -700,7 +698,7 @@ __global__ void sr_mlp_pack_split_kernel(const float* __restrict__ W1, const flo
   }
 }
 
-__device__ __forceinline__ void sr_swap_halves_u4(const sr_u4v fa, const sr_u4v fb, sr_u4v& bP, sr_u4v& bQ) {
+__device__ __forceinline__ void sr_swap_halves_u4(const sr_u4 fa, const sr_u4 fb, sr_u4& bP, sr_u4& bQ) {
 #pragma unroll
   for (int i = 0; i < 4; ++i) {
     auto r = __builtin_amdgcn_permlane32_swap(fa[i], fb[i], false, false);
@@ -712,10 +710,10 @@ __device__ __forceinline__ void sr_swap_halves_u4(const sr_u4v fa, const sr_u4v 
 // one 16-input k-step of layer 1 or 2: 4 output tiles x 2 point groups x 3 products
 // INIT: 0 accumulate, 1 the first products take c0 as their C operand, 2 they take zero
 template <int FMT, int INIT>
-__device__ __forceinline__ void sr_spl_step(f32x16 (&acc)[2][4], const f32x16 (&c0)[2][4], const sr_u4v* aw, int ls,
-                                            const sr_u4v bPh, const sr_u4v bPl, const sr_u4v bQh, const sr_u4v bQl) {
+__device__ __forceinline__ void sr_spl_step(f32x16 (&acc)[2][4], const f32x16 (&c0)[2][4], const sr_u4* aw, int ls,
+                                            const sr_u4 bPh, const sr_u4 bPl, const sr_u4 bQh, const sr_u4 bQl) {
   typedef SrSplitFmt<FMT> S;
-  sr_u4v ah[4], al[4];
+  sr_u4 ah[4], al[4];
 #pragma unroll
   for (int m = 0; m < 4; ++m) { ah[m] = aw[(2 * m) * ls]; al[m] = aw[(2 * m + 1) * ls]; }
 #pragma unroll
@@ -759,8 +757,8 @@ __global__ __launch_bounds__(256, 1) void sr_mlp_volume_split_kernel(SrMlpParams
     for (int i = threadIdx.x; i < p.K * (SR_SPL_VIEW_WORDS / 4); i += blockDim.x) l4[i] = g4[i];
   }
   __syncthreads();
-  const sr_u4v* W2s = reinterpret_cast<const sr_u4v*>(lds + SR_SPL_TAB);
-  const sr_u4v* W1s = W2s + SR_SPL_W2_WORDS / 4;
+  const sr_u4* W2s = reinterpret_cast<const sr_u4*>(lds + SR_SPL_TAB);
+  const sr_u4* W1s = W2s + SR_SPL_W2_WORDS / 4;
 
   const int N = p.h * p.w;
   const long nunits = (long)p.B * p.tiles * p.chunks;
@@ -775,7 +773,7 @@ __global__ __launch_bounds__(256, 1) void sr_mlp_volume_split_kernel(SrMlpParams
     unit_end = min(nunits, (xcd + 1) * u8);
   }
   const int half = lane >> 5;
-  const sr_u4v zero4 = {0u, 0u, 0u, 0u};
+  const sr_u4 zero4 = {0u, 0u, 0u, 0u};
 
   for (long unit = wave0; unit < unit_end; unit += nwaves) {
     const int chunk = (int)(unit % p.chunks);
@@ -888,13 +886,13 @@ __global__ __launch_bounds__(256, 1) void sr_mlp_volume_split_kernel(SrMlpParams
       {                                                                                                  \
         const int kn = min(k + 1, p.K - 1);                                                              \
         const float* g = geom_b + kn * SR_GEOM_STRIDE;                                                   \
-        const sr_u4v* wk = W1s + (size_t)k * (SR_SPL_VIEW_WORDS / 4);                                    \
-        sr_u4v bPh, bPl, bQh, bQl;                                                                       \
-        sr_swap_halves_u4(sr_u4v{ph[0], ph[1], ph[2], ph[3]}, sr_u4v{ph[4], ph[5], ph[6], ph[7]}, bPh, bQh); \
-        sr_swap_halves_u4(sr_u4v{pl[0], pl[1], pl[2], pl[3]}, sr_u4v{pl[4], pl[5], pl[6], pl[7]}, bPl, bQl); \
-        sr_u4v mPh, mPl, mQh, mQl;                                                                       \
-        sr_swap_halves_u4(sr_u4v{ph[8], ph[9], ph[10], ph[11]}, zero4, mPh, mQh);                        \
-        sr_swap_halves_u4(sr_u4v{pl[8], pl[9], pl[10], pl[11]}, zero4, mPl, mQl);                        \
+        const sr_u4* wk = W1s + (size_t)k * (SR_SPL_VIEW_WORDS / 4);                                    \
+        sr_u4 bPh, bPl, bQh, bQl;                                                                       \
+        sr_swap_halves_u4(sr_u4{ph[0], ph[1], ph[2], ph[3]}, sr_u4{ph[4], ph[5], ph[6], ph[7]}, bPh, bQh); \
+        sr_swap_halves_u4(sr_u4{pl[0], pl[1], pl[2], pl[3]}, sr_u4{pl[4], pl[5], pl[6], pl[7]}, bPl, bQl); \
+        sr_u4 mPh, mPl, mQh, mQl;                                                                       \
+        sr_swap_halves_u4(sr_u4{ph[8], ph[9], ph[10], ph[11]}, zero4, mPh, mQh);                        \
+        sr_swap_halves_u4(sr_u4{pl[8], pl[9], pl[10], pl[11]}, zero4, mPl, mQl);                        \
         issue_view(kn);                                                                                  \
         sr_spl_step<FMT, (FIRST) ? 1 : 0>(acc, hc, wk + lane, 64, bPh, bPl, bQh, bQl);                   \
         SR_RAY_A(fn, g, kn) SR_RAY_B(fn) SR_RAY_C(fn)                                                    \
@@ -917,7 +915,7 @@ __global__ __launch_bounds__(256, 1) void sr_mlp_volume_split_kernel(SrMlpParams
       f32x16 acc2[2][4];
 #pragma unroll
       for (int s = 0; s < 8; ++s) {
-        sr_u4v bh[2], bl[2];
+        sr_u4 bh[2], bl[2];
 #pragma unroll
         for (int g = 0; g < 2; ++g)
 #pragma unroll
@@ -928,7 +926,7 @@ __global__ __launch_bounds__(256, 1) void sr_mlp_volume_split_kernel(SrMlpParams
             bh[g][i] = hi;
             bl[g][i] = lo;
           }
-        const sr_u4v* w2 = W2s + (size_t)s * 512 + lane;
+        const sr_u4* w2 = W2s + (size_t)s * 512 + lane;
         if (s == 0) sr_spl_step<FMT, 2>(acc2, acc2, w2, 64, bh[0], bl[0], bh[1], bl[1]);
         else sr_spl_step<FMT, 0>(acc2, acc2, w2, 64, bh[0], bl[0], bh[1], bl[1]);
       }
@@ -1068,8 +1066,7 @@ static int sr_mlp_volume_sweep_reserved(const float* cur, const float* invK_cur,
   }
   p.chunk = best;
   p.chunks = (D + best - 1) / best;
-  p.vec_store = (cv_sd == 1) && (p.chunk % 4 == 0) && (cv_sp % 4 == 0) && (cv_sb % 4 == 0) &&
-                (((uintptr_t)out_cv & 15) == 0);
+  p.vec_store = (cv_sd == 1) && (p.chunk % 4 == 0) && sr_rows_aligned(out_cv, cv_sb, cv_sp, 15, 4);
   const long nunits = (long)B * p.tiles * p.chunks;
   const int blocks = (int)((nunits + 3) / 4 < cus ? (nunits + 3) / 4 : cus);
   const size_t w3_bytes = SR_LDS_W3_FLOATS * sizeof(float);
@@ -1082,8 +1079,7 @@ static int sr_mlp_volume_sweep_reserved(const float* cur, const float* invK_cur,
     const size_t bytes = ((size_t)SR_SPL_TAB + SR_SPL_W2_WORDS + (size_t)K * SR_SPL_VIEW_WORDS) * 4;
     if (bytes > lds_max) return SR_ERR_UNSUPPORTED;
     const void* fn = split == 1 ? (const void*)sr_mlp_volume_split_kernel<1> : (const void*)sr_mlp_volume_split_kernel<2>;
-    hipError_t e = hipFuncSetAttribute(fn, hipFuncAttributeMaxDynamicSharedMemorySize, (int)bytes);
-    if (e != hipSuccess) return sr_hip_rc(e);
+    if (hipError_t e = sr_allow_lds(fn, bytes)) return sr_hip_rc(e);
     if (split == 1) hipLaunchKernelGGL((sr_mlp_volume_split_kernel<1>), dim3(blocks), dim3(256), bytes, stream, p);
     else hipLaunchKernelGGL((sr_mlp_volume_split_kernel<2>), dim3(blocks), dim3(256), bytes, stream, p);
     int rc = sr_hip_rc(hipGetLastError());
@@ -1093,9 +1089,8 @@ static int sr_mlp_volume_sweep_reserved(const float* cur, const float* invK_cur,
   }
 #define SR_MLP_LAUNCH(L1, L2, BYTES)                                                                              \
   {                                                                                                               \
-    hipError_t e = hipFuncSetAttribute((const void*)sr_mlp_volume_kernel<L1, L2>,                                 \
-                                       hipFuncAttributeMaxDynamicSharedMemorySize, (int)(BYTES));                 \
-    if (e != hipSuccess) return sr_hip_rc(e);                                                                     \
+    /* (BYTES grows with K: sr_allow_lds asks again when a later call needs more than the largest grant) */       \
+    if (hipError_t e = sr_allow_lds((const void*)sr_mlp_volume_kernel<L1, L2>, (BYTES))) return sr_hip_rc(e);     \
     hipLaunchKernelGGL((sr_mlp_volume_kernel<L1, L2>), dim3(blocks), dim3(256), (BYTES), stream, p);              \
   }
   if (w1_bytes + w2_bytes + w3_bytes <= lds_max) SR_MLP_LAUNCH(true, true, w1_bytes + w2_bytes + w3_bytes)

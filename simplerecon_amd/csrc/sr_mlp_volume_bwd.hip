@@ -68,7 +68,6 @@ __host__ __device__ inline size_t sr_mlp_bwd_lds_floats(int K, int C, int Cin) {
 // A reads are conflict-free.  dW1 / dW2 stay in accumulator registers for the whole launch (wave w owns output rows
 // 32w..32w+31: (NT1 + 4) x 16 registers, one wave per SIMD) and are flushed once with fp32 atomics.
 // Work per 32-pixel plane tile: ~2000 MFMAs (= 125 k MFMA cycles per workgroup) against ~0.3 MB of weights from L2.
-typedef float f32x16 __attribute__((ext_vector_type(16)));
 
 // acc += A[32 x 2*ksteps] . B[2*ksteps x 32] on v_mfma_f32_32x32x2_f32: A from LDS (ap[2*ks]), B streamed from global / L2
 // (bp[2*ks*bstride]) through a double-buffered batch of BK fragments, so that ~BK * 64 matrix-pipe cycles cover the L2
@@ -456,8 +455,7 @@ extern "C" int sr_mlp_volume_bwd(const float* grad_cv, int64_t g_sb, int64_t g_s
   const int blocks = p.total_items < cus ? p.total_items : cus;
 #define SR_BWD_LAUNCH(KERNEL)                                                                                          \
   {                                                                                                                    \
-    e = hipFuncSetAttribute((const void*)KERNEL, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);                \
-    if (e != hipSuccess) return sr_hip_rc(e);                                                                          \
+    if ((e = sr_allow_lds((const void*)KERNEL, lds)) != hipSuccess) return sr_hip_rc(e);                               \
     hipLaunchKernelGGL(KERNEL, dim3(blocks), dim3(256), lds, stream, p);                                               \
   }
   const int nt1 = (Cin + 31) / 32;   // dW1 column tiles

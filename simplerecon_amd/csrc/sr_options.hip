@@ -8,7 +8,9 @@
 // working for tuning runs).  After that first access the environment is never read again.  The table is process-wide: an option
 // set while another thread launches affects that thread's next launch (documented in include/simplerecon_hip.h).
 #include <atomic>
+#include <map>
 #include <mutex>
+#include <utility>
 #include <stdlib.h>
 #include <string.h>
 
@@ -95,4 +97,20 @@ int sr_device_cus() {
     cus[dev].store(v, std::memory_order_relaxed);
   }
   return v;
+}
+
+// hipFuncAttributeMaxDynamicSharedMemorySize once per (kernel, device) instead of once per launch: the largest
+// size granted is remembered under the kernel's host pointer, and the runtime is asked again only for a larger one (the MLP
+// sweep's LDS grows with its view count).  A refusal is returned and not remembered.
+hipError_t sr_allow_lds(const void* kernel, size_t bytes) {
+  static std::mutex mu;
+  static std::map<std::pair<const void*, int>, size_t> granted;
+  int dev = 0;
+  if (hipError_t e = hipGetDevice(&dev)) return e;
+  std::lock_guard<std::mutex> lock(mu);
+  size_t& have = granted[{kernel, dev}];
+  if (bytes <= have) return hipSuccess;
+  if (hipError_t e = hipFuncSetAttribute(kernel, hipFuncAttributeMaxDynamicSharedMemorySize, (int)bytes)) return e;
+  have = bytes;
+  return hipSuccess;
 }

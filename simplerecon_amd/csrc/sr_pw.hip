@@ -22,55 +22,23 @@
 // M = 2 400) they split the K range 2 or 4 ways and add their accumulators through LDS in a FIXED order (no atomics).
 #include <stdlib.h>
 
-#include "sr_common.h"
+#include "sr_buffer.h"
+#include "sr_view.h"
 
 namespace {
 
-typedef float pw_f16 __attribute__((ext_vector_type(16)));
-typedef float pw_f4 __attribute__((ext_vector_type(4)));
-typedef unsigned int pw_u4 __attribute__((ext_vector_type(4)));
-#define PW_RSRC_FLAGS 0x00020000
-#define PW_OOB 0x7fffffffu
-
-__device__ __forceinline__ pw_f4 pw_load(__amdgpu_buffer_rsrc_t r, unsigned voff, unsigned soff) {
-  return __builtin_bit_cast(pw_f4, __builtin_amdgcn_raw_buffer_load_b128(r, (int)voff, (int)soff, 0));
-}
-// 16-bit activation I/O (IO = 1: fp16, 2: bf16; 0 = fp32): input / residual / output elements are 2 bytes in HBM, widened on
-// load and rounded to nearest even on store; gate, weights, bias and the accumulation stay fp32 (training under autocast).
-typedef unsigned int pw_u2 __attribute__((ext_vector_type(2)));
-template <int IO>
-__device__ __forceinline__ float pw_widen(unsigned short h) {
-  if (IO == 1) return (float)__builtin_bit_cast(_Float16, h);
-  return __builtin_bit_cast(float, (unsigned)h << 16);
-}
-template <int IO>
-__device__ __forceinline__ unsigned short pw_narrow(float f) {
-  if (IO == 1) return __builtin_bit_cast(unsigned short, (_Float16)f);
-  return __builtin_bit_cast(unsigned short, (__bf16)f);
-}
-template <int IO>
-__device__ __forceinline__ pw_f4 pw_load_a(__amdgpu_buffer_rsrc_t r, unsigned voff, unsigned soff) {
-  if (IO == 0) return __builtin_bit_cast(pw_f4, __builtin_amdgcn_raw_buffer_load_b128(r, (int)voff, (int)soff, 0));
-  const pw_u2 v = __builtin_bit_cast(pw_u2, __builtin_amdgcn_raw_buffer_load_b64(r, (int)voff, (int)soff, 0));
-  return pw_f4{pw_widen<IO>((unsigned short)(v.x & 0xffffu)), pw_widen<IO>((unsigned short)(v.x >> 16)),
-               pw_widen<IO>((unsigned short)(v.y & 0xffffu)), pw_widen<IO>((unsigned short)(v.y >> 16))};
-}
+// (buffer addressing and the 16-bit activation I/O -- IO = 1: fp16, 2: bf16, 0 = fp32; gate, weights, bias and the
+// accumulation stay fp32 -- come from sr_buffer.h; the single-element forms of the scalar epilogue live here)
 template <int IO>
 __device__ __forceinline__ float pw_load_elem(__amdgpu_buffer_rsrc_t r, unsigned voff, unsigned soff) {
   if (IO == 0) return __builtin_bit_cast(float, __builtin_amdgcn_raw_buffer_load_b32(r, (int)voff, (int)soff, 0));
-  return pw_widen<IO>(__builtin_amdgcn_raw_buffer_load_b16(r, (int)voff, (int)soff, 0));
+  return sr_widen<IO>(__builtin_amdgcn_raw_buffer_load_b16(r, (int)voff, (int)soff, 0));
 }
 template <int IO>
 __device__ __forceinline__ void pw_store_elem(float v, __amdgpu_buffer_rsrc_t r, unsigned voff, unsigned soff) {
   if (IO == 0) __builtin_amdgcn_raw_buffer_store_b32(__builtin_bit_cast(unsigned, v), r, (int)voff, (int)soff, 0);
-  else __builtin_amdgcn_raw_buffer_store_b16(pw_narrow<IO>(v), r, (int)voff, (int)soff, 0);
+  else __builtin_amdgcn_raw_buffer_store_b16(sr_narrow<IO>(v), r, (int)voff, (int)soff, 0);
 }
-#define PW_ES(io) ((io) == 0 ? 4u : 2u)
-
-__device__ __forceinline__ __amdgpu_buffer_rsrc_t pw_rsrc(const void* base, int64_t bytes) {
-  return __builtin_amdgcn_make_buffer_rsrc(const_cast<void*>(base), 0, (int)bytes, PW_RSRC_FLAGS);
-}
-
 struct SrPwParams {
   const float* in; int64_t in_sb; int in_sp;
   const float* wp;                   // packed [G][2][Co_pad][4] (sr_conv_pack_weights, ksize 1)
@@ -92,7 +60,7 @@ constexpr int PW_PD = SR_PW_PD;  // loads run PD groups ahead of their MFMAs
 
 template <int NT, int KS, bool GATE, int IO = 0>
 __global__ __launch_bounds__(256, 2) void sr_pw_kernel(SrPwParams p) {
-  constexpr unsigned ES = PW_ES(IO);   // bytes per activation element
+  constexpr unsigned ES = SR_IO_ES(IO);   // bytes per activation element
   extern __shared__ __attribute__((aligned(16))) float red[];   // KS > 1: [m local][KS - 1][NT][16][64]
   const int tid = threadIdx.x;
   const int lane = tid & 63, wave = __builtin_amdgcn_readfirstlane(tid >> 6);
@@ -113,35 +81,35 @@ __global__ __launch_bounds__(256, 2) void sr_pw_kernel(SrPwParams p) {
   const int g1 = min(p.G8, g0 + per);
   const int steps = live && g1 > g0 ? (g1 - g0 + PW_U - 1) / PW_U * PW_U : 0;
 
-  const __amdgpu_buffer_rsrc_t rs_in = pw_rsrc(reinterpret_cast<const char*>(p.in) + (int64_t)img * p.in_sb * ES,
+  const __amdgpu_buffer_rsrc_t rs_in = sr_rsrc(reinterpret_cast<const char*>(p.in) + (int64_t)img * p.in_sb * ES,
                                                ((int64_t)(p.HW - 1) * p.in_sp + p.Cin) * ES);
-  const __amdgpu_buffer_rsrc_t rs_w = pw_rsrc(p.wp, (int64_t)p.G * 2 * p.Co_pad * 16);
-  const __amdgpu_buffer_rsrc_t rs_g = pw_rsrc(GATE ? p.gate + (int64_t)img * p.Cin : p.wp, GATE ? (int64_t)p.Cin * 4 : 0);
+  const __amdgpu_buffer_rsrc_t rs_w = sr_rsrc(p.wp, (int64_t)p.G * 2 * p.Co_pad * 16);
+  const __amdgpu_buffer_rsrc_t rs_g = sr_rsrc(GATE ? p.gate + (int64_t)img * p.Cin : p.wp, GATE ? (int64_t)p.Cin * 4 : 0);
   const int row = row0 + i;
   // lane offsets (bytes): the group index rides in the scalar offset.  A lane whose row is past the image, or whose
   // channel quad is past Cin (Cin % 8 == 4, last group), reads through an out-of-range offset: 0.
-  const unsigned a_voff = (row < p.HW) ? ((unsigned)row * (unsigned)p.in_sp + 4u * kk) * ES : PW_OOB;
+  const unsigned a_voff = (row < p.HW) ? ((unsigned)row * (unsigned)p.in_sp + 4u * kk) * ES : SR_OOB;
   const bool k_tail = (p.Cin & 7) != 0;
   const unsigned w_voff = (unsigned)(kk * p.Co_pad + n0 + i) * 16u;
   const unsigned g_voff = 16u * kk;
   const int g_last_w = p.G - 1;   // weight groups past the packed array are read from its last group (their A operand is 0)
 
-  pw_f16 acc[NT];
+  f32x16 acc[NT];
 #pragma unroll
   for (int n = 0; n < NT; ++n)
 #pragma unroll
     for (int r = 0; r < 16; ++r) acc[n][r] = 0.0f;
 
-  pw_f4 a_f[PW_U], b_f[PW_U][NT], s_f[PW_U];
+  sr_f4 a_f[PW_U], b_f[PW_U][NT], s_f[PW_U];
   auto issue = [&](int g, int slot) {   // loads of group g (wave-uniform): A, gate, NT weight fragments
     const bool in_range = g < g1;
-    unsigned av = in_range ? a_voff : PW_OOB;
-    if (k_tail && 8 * g + 4 * kk + 4 > p.Cin) av = PW_OOB;
-    a_f[slot] = pw_load_a<IO>(rs_in, av, (unsigned)g * 8u * ES);
-    if (GATE) s_f[slot] = pw_load(rs_g, g_voff + (unsigned)g * 32u, 0u);   // (lane offset: past Cin -> out of range -> 0)
+    unsigned av = in_range ? a_voff : SR_OOB;
+    if (k_tail && 8 * g + 4 * kk + 4 > p.Cin) av = SR_OOB;
+    a_f[slot] = sr_io_load<IO>(rs_in, av, (unsigned)g * 8u * ES);
+    if (GATE) s_f[slot] = sr_buf_load(rs_g, g_voff + (unsigned)g * 32u, 0u);   // (lane offset: past Cin -> out of range -> 0)
     const unsigned gw = (unsigned)min(g, g_last_w);
 #pragma unroll
-    for (int n = 0; n < NT; ++n) b_f[slot][n] = pw_load(rs_w, w_voff + 512u * n, gw * 2u * (unsigned)p.Co_pad * 16u);
+    for (int n = 0; n < NT; ++n) b_f[slot][n] = sr_buf_load(rs_w, w_voff + 512u * n, gw * 2u * (unsigned)p.Co_pad * 16u);
   };
   if (steps > 0) {
 #pragma unroll
@@ -151,7 +119,7 @@ __global__ __launch_bounds__(256, 2) void sr_pw_kernel(SrPwParams p) {
 #pragma unroll
     for (int u = 0; u < PW_U; ++u) {
       issue(g0 + gb + u + PW_PD, (u + PW_PD) % PW_U);
-      pw_f4 a = a_f[u];
+      sr_f4 a = a_f[u];
       if (GATE) a = a * s_f[u];
 #pragma unroll
       for (int e = 0; e < 4; ++e)
@@ -183,9 +151,9 @@ __global__ __launch_bounds__(256, 2) void sr_pw_kernel(SrPwParams p) {
   // row0 + (r & 3) + 8 (r >> 2) + 4 kk: a wave's store covers 2 rows x 128 contiguous bytes.
   const float slope = sr_uniform(p.slope);
   const char* resb = p.res ? reinterpret_cast<const char*>(p.res) + (int64_t)img * p.res_sb * ES : nullptr;
-  const __amdgpu_buffer_rsrc_t rs_out = pw_rsrc(reinterpret_cast<char*>(p.out) + (int64_t)img * p.out_sb * ES,
+  const __amdgpu_buffer_rsrc_t rs_out = sr_rsrc(reinterpret_cast<char*>(p.out) + (int64_t)img * p.out_sb * ES,
                                                 ((int64_t)(p.HW - 1) * p.out_sp + p.Cout) * ES);
-  const __amdgpu_buffer_rsrc_t rs_res = pw_rsrc(resb ? (const void*)resb : (const void*)p.wp,
+  const __amdgpu_buffer_rsrc_t rs_res = sr_rsrc(resb ? (const void*)resb : (const void*)p.wp,
                                                 resb ? ((int64_t)(p.HW - 1) * p.res_sp + p.Cout) * ES : (int64_t)0);
   const bool full = (row0 + 32 <= p.HW) & (n0 + 32 * NT <= p.Cout);   // uniform
 #pragma unroll
@@ -204,7 +172,7 @@ __global__ __launch_bounds__(256, 2) void sr_pw_kernel(SrPwParams p) {
       for (int r = 0; r < 16; ++r) {
         const int dr = (r & 3) + 8 * (r >> 2);
         const bool ok = full || (okc && row0 + 4 * kk + dr < p.HW);
-        rv[r] = pw_load_elem<IO>(rs_res, ok ? r_base : PW_OOB, (unsigned)dr * (unsigned)p.res_sp * ES);
+        rv[r] = pw_load_elem<IO>(rs_res, ok ? r_base : SR_OOB, (unsigned)dr * (unsigned)p.res_sp * ES);
       }
 #pragma unroll
       for (int r = 0; r < 16; ++r) v[r] += rv[r];
@@ -214,12 +182,10 @@ __global__ __launch_bounds__(256, 2) void sr_pw_kernel(SrPwParams p) {
     for (int r = 0; r < 16; ++r) {
       const int dr = (r & 3) + 8 * (r >> 2);
       const bool ok = full || (okc && row0 + 4 * kk + dr < p.HW);
-      pw_store_elem<IO>(v[r], rs_out, ok ? o_base : PW_OOB, (unsigned)dr * (unsigned)p.out_sp * ES);
+      pw_store_elem<IO>(v[r], rs_out, ok ? o_base : SR_OOB, (unsigned)dr * (unsigned)p.out_sp * ES);
     }
   }
 }
-
-int pw_num_cus() { return sr_device_cus(); }
 
 struct PwPlan { int nt, ks; };
 
@@ -230,7 +196,7 @@ PwPlan pw_plan(int B, int HW, int Cin, int Cout) {
   const long mt = (long)B * ((HW + 31) / 32);
   const int n32 = (Cout + 31) / 32;
   const int g8 = (Cin + 7) / 8;
-  const long want = (long)pw_num_cus() * 4 * 3 / 2;
+  const long want = (long)sr_device_cus() * 4 * 3 / 2;
   PwPlan best = {1, 1};
   double best_cost = -1.0;
   const int nts[4] = {4, 2, 1, 5};
@@ -289,13 +255,13 @@ static int pw_run(const float* in, int64_t in_batch_stride, int in_pix_stride, c
   if (B == 0) return SR_OK;
   if (!in || !packed_w || !out) return SR_ERR_INVALID_ARGUMENT;
   if (io && gate) return SR_ERR_UNSUPPORTED;   // (the gated projection is an inference path: fp32)
-  if (Cin % 4 != 0 || in_pix_stride % 4 != 0 || in_batch_stride % 4 != 0 || (((uintptr_t)in) & (io ? 7 : 15)) != 0 ||
-      (gate && (((uintptr_t)gate) & 15) != 0))
+  if (Cin % 4 != 0 || !sr_rows_aligned(in, in_batch_stride, in_pix_stride, io ? 7 : 15, 4) || (gate && !sr_ptr_aligned(gate, 15)))
     return SR_ERR_UNSUPPORTED;   // 4-channel A fragments (16 bytes of fp32, 8 of fp16 / bf16)
-  const int64_t lim = (int64_t)1 << 31;
-  if (((int64_t)(HW - 1) * in_pix_stride + Cin) * 4 >= lim || ((int64_t)(HW - 1) * out_pix_stride + Cout) * 4 >= lim ||
-      (residual && ((int64_t)(HW - 1) * res_pix_stride + Cout) * 4 >= lim))
-    return SR_ERR_UNSUPPORTED;   // per-image byte offsets are 32-bit
+  // per-image byte offsets are 32-bit.  (Conservative for 16-bit tensors: the span is taken at 4 bytes per element whatever
+  // `io` says, so a 2-byte view between 2^30 and 2^31 bytes is refused although it would fit.)
+  if (!sr_view_fits32(HW, in_pix_stride, Cin, 4) || !sr_view_fits32(HW, out_pix_stride, Cout, 4) ||
+      (residual && !sr_view_fits32(HW, res_pix_stride, Cout, 4)))
+    return SR_ERR_UNSUPPORTED;
   SrPwParams p;
   p.in = in; p.in_sb = in_batch_stride; p.in_sp = in_pix_stride;
   p.wp = packed_w; p.bias = bias; p.gate = gate;

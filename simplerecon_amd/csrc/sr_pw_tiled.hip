@@ -17,12 +17,10 @@
 // sr_launch_splitk_reduce adds them in index order, then bias + residual + activation -- deterministic, no atomics.
 #include <stdlib.h>
 
-#include "sr_common.h"
+#include "sr_buffer.h"
+#include "sr_view.h"
 
 namespace {
-
-typedef float pt_f16 __attribute__((ext_vector_type(16)));
-typedef float pt_f4 __attribute__((ext_vector_type(4)));
 
 constexpr int PT_KS = 32;             // channels per K slab
 constexpr int PT_AROW = PT_KS + 4;    // floats per staged pixel row (padded: conflict-free b128 fragment reads)
@@ -70,14 +68,14 @@ __global__ __launch_bounds__(256, 2) void sr_pw_tiled_kernel(SrPtParams p) {
     g_ptr[u] = (GATE && ok) ? p.gate + (int64_t)(m / p.HW) * p.Cin + 4 * a_q : nullptr;
   }
   // B: float4 index e = tid + 256 u -> (group, half) = e / BN, column e % BN
-  auto stage_load = [&](int s, pt_f4 (&ra)[A_PER_THREAD], pt_f4 (&rb)[B_PER_THREAD]) {
+  auto stage_load = [&](int s, sr_f4 (&ra)[A_PER_THREAD], sr_f4 (&rb)[B_PER_THREAD]) {
     const int k0 = s * PT_KS;
 #pragma unroll
     for (int u = 0; u < A_PER_THREAD; ++u) {
-      pt_f4 v = {0.f, 0.f, 0.f, 0.f};
+      sr_f4 v = {0.f, 0.f, 0.f, 0.f};
       if (a_ptr[u] && k0 + 4 * a_q < p.Cin) {
-        v = *reinterpret_cast<const pt_f4*>(a_ptr[u] + k0);
-        if (GATE) v = v * *reinterpret_cast<const pt_f4*>(g_ptr[u] + k0);
+        v = *reinterpret_cast<const sr_f4*>(a_ptr[u] + k0);
+        if (GATE) v = v * *reinterpret_cast<const sr_f4*>(g_ptr[u] + k0);
       }
       ra[u] = v;
     }
@@ -86,28 +84,28 @@ __global__ __launch_bounds__(256, 2) void sr_pw_tiled_kernel(SrPtParams p) {
       const int e = tid + 256 * u;
       const int gh = e / BN, col = e - gh * BN;      // gh = 2 * local group + half
       const int g = s * (PT_KS / 8) + (gh >> 1);
-      pt_f4 v = {0.f, 0.f, 0.f, 0.f};
+      sr_f4 v = {0.f, 0.f, 0.f, 0.f};
       if (g < p.G && n0 + col < p.Co_pad)
-        v = *reinterpret_cast<const pt_f4*>(p.wp + ((int64_t)(g * 2 + (gh & 1)) * p.Co_pad + n0 + col) * 4);
+        v = *reinterpret_cast<const sr_f4*>(p.wp + ((int64_t)(g * 2 + (gh & 1)) * p.Co_pad + n0 + col) * 4);
       rb[u] = v;
     }
   };
-  auto stage_store = [&](int buf, const pt_f4 (&ra)[A_PER_THREAD], const pt_f4 (&rb)[B_PER_THREAD]) {
+  auto stage_store = [&](int buf, const sr_f4 (&ra)[A_PER_THREAD], const sr_f4 (&rb)[B_PER_THREAD]) {
     float* A = lds + buf * (A_FLOATS + B_FLOATS);
     float* Bt = A + A_FLOATS;
 #pragma unroll
-    for (int u = 0; u < A_PER_THREAD; ++u) *reinterpret_cast<pt_f4*>(&A[a_row[u] * PT_AROW + 4 * a_q]) = ra[u];
+    for (int u = 0; u < A_PER_THREAD; ++u) *reinterpret_cast<sr_f4*>(&A[a_row[u] * PT_AROW + 4 * a_q]) = ra[u];
 #pragma unroll
-    for (int u = 0; u < B_PER_THREAD; ++u) *reinterpret_cast<pt_f4*>(&Bt[(tid + 256 * u) * 4]) = rb[u];
+    for (int u = 0; u < B_PER_THREAD; ++u) *reinterpret_cast<sr_f4*>(&Bt[(tid + 256 * u) * 4]) = rb[u];
   };
 
-  pt_f16 acc[NTW];
+  f32x16 acc[NTW];
 #pragma unroll
   for (int n = 0; n < NTW; ++n)
 #pragma unroll
     for (int r = 0; r < 16; ++r) acc[n][r] = 0.0f;
 
-  pt_f4 ra[A_PER_THREAD], rb[B_PER_THREAD];
+  sr_f4 ra[A_PER_THREAD], rb[B_PER_THREAD];
   if (s_begin < s_end) {
     stage_load(s_begin, ra, rb);
     stage_store(0, ra, rb);
@@ -123,10 +121,10 @@ __global__ __launch_bounds__(256, 2) void sr_pw_tiled_kernel(SrPtParams p) {
     const float* b_base = Bt + (kk * BN + 32 * wn * NTW + i) * 4;
 #pragma unroll
     for (int gl = 0; gl < PT_KS / 8; ++gl) {
-      const pt_f4 a = *reinterpret_cast<const pt_f4*>(a_base + 8 * gl);
-      pt_f4 b[NTW];
+      const sr_f4 a = *reinterpret_cast<const sr_f4*>(a_base + 8 * gl);
+      sr_f4 b[NTW];
 #pragma unroll
-      for (int n = 0; n < NTW; ++n) b[n] = *reinterpret_cast<const pt_f4*>(b_base + (gl * 2 * BN + 32 * n) * 4);
+      for (int n = 0; n < NTW; ++n) b[n] = *reinterpret_cast<const sr_f4*>(b_base + (gl * 2 * BN + 32 * n) * 4);
 #pragma unroll
       for (int e = 0; e < 4; ++e)
 #pragma unroll
@@ -168,8 +166,6 @@ __global__ __launch_bounds__(256, 2) void sr_pw_tiled_kernel(SrPtParams p) {
   }
 }
 
-int pt_num_cus() { return sr_device_cus(); }
-
 struct PtPlan { int cfg, ks; };   // cfg: 0 = 64 x 128 (2x2 waves, 2 tiles each), 1 = 128 x 160 (4x1, 5), 2 = 128 x 64 (4x1, 2), 3 = 64 x 64 (2x2, 1)
 constexpr int PT_BM[4] = {64, 128, 128, 64}, PT_BN[4] = {128, 160, 64, 64};
 
@@ -178,7 +174,7 @@ constexpr int PT_BM[4] = {64, 128, 128, 64}, PT_BN[4] = {128, 160, 64, 64};
 PtPlan pt_plan(int M, int Cin, int Cout, bool can_split) {
   const int f_cfg = sr_opt(SR_OPT_PT_CFG), f_ks = sr_opt(SR_OPT_PT_KS);   // forced plan (tests, sweeps)
   const int slabs = (Cin + PT_KS - 1) / PT_KS;
-  const long want = (long)pt_num_cus() * 3 / 2;
+  const long want = (long)sr_device_cus() * 3 / 2;
   PtPlan best = {0, 1};
   double best_cost = -1.0;
   for (int cfg = 0; cfg < 4; ++cfg) {
@@ -204,17 +200,9 @@ int pt_launch(const SrPtParams& p, int tiles_m, hipStream_t stream) {
   constexpr int BM = 32 * WM, BN = 32 * WN * NTW;
   const size_t lds = (size_t)2 * (BM * PT_AROW + (PT_KS / 8) * 2 * BN * 4) * sizeof(float);
   const dim3 grid((unsigned)(tiles_m * p.tiles_n), (unsigned)p.ksplit);
-  if (p.gate) {
-    hipError_t e = hipFuncSetAttribute((const void*)sr_pw_tiled_kernel<WM, WN, NTW, true>,
-                                       hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
-    if (e != hipSuccess) return sr_hip_rc(e);
-    hipLaunchKernelGGL((sr_pw_tiled_kernel<WM, WN, NTW, true>), grid, dim3(256), lds, stream, p);
-  } else {
-    hipError_t e = hipFuncSetAttribute((const void*)sr_pw_tiled_kernel<WM, WN, NTW, false>,
-                                       hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
-    if (e != hipSuccess) return sr_hip_rc(e);
-    hipLaunchKernelGGL((sr_pw_tiled_kernel<WM, WN, NTW, false>), grid, dim3(256), lds, stream, p);
-  }
+  auto kernel = p.gate ? sr_pw_tiled_kernel<WM, WN, NTW, true> : sr_pw_tiled_kernel<WM, WN, NTW, false>;
+  if (hipError_t e = sr_allow_lds((const void*)kernel, lds)) return sr_hip_rc(e);
+  hipLaunchKernelGGL(kernel, grid, dim3(256), lds, stream, p);
   return sr_hip_rc(hipGetLastError());
 }
 
@@ -242,11 +230,12 @@ extern "C" int sr_pw_conv_tiled_nhwc_fwd(const float* in, int in_pix_stride, con
   if (M < 0 || HW <= 0 || Cin <= 0 || Cout <= 0) return SR_ERR_INVALID_ARGUMENT;
   if (M == 0) return SR_OK;
   if (!in || !packed_w || !out) return SR_ERR_INVALID_ARGUMENT;
-  if (Cin % 4 != 0 || in_pix_stride % 4 != 0 || (((uintptr_t)in) & 15) != 0 || (gate && (((uintptr_t)gate) & 15) != 0))
+  // (a dense [M, C] view: no batch stride.  Flat 64-bit addressing, so there is no span limit here.)
+  if (Cin % 4 != 0 || !sr_rows_aligned(in, 0, in_pix_stride, 15, 4) || (gate && !sr_ptr_aligned(gate, 15)))
     return SR_ERR_UNSUPPORTED;   // 16-byte staging loads
-  const bool can_split = workspace && (((uintptr_t)workspace) & 15) == 0 && Cout % 4 == 0 &&
-                         (!residual || ((((uintptr_t)residual) & 15) == 0 && res_pix_stride % 4 == 0)) &&
-                         (((uintptr_t)out) & 15) == 0 && out_pix_stride % 4 == 0 && (!bias || (((uintptr_t)bias) & 15) == 0);
+  const bool can_split = workspace && sr_ptr_aligned(workspace, 15) && Cout % 4 == 0 &&
+                         (!residual || sr_rows_aligned(residual, 0, res_pix_stride, 15, 4)) &&
+                         sr_rows_aligned(out, 0, out_pix_stride, 15, 4) && (!bias || sr_ptr_aligned(bias, 15));
   PtPlan pl = pt_plan(M, Cin, Cout, can_split);
   if (pl.ks > 1 && workspace_bytes < (size_t)pl.ks * M * Cout * sizeof(float)) pl = pt_plan(M, Cin, Cout, false);
   SrPtParams p;

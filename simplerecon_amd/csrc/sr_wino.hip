@@ -24,6 +24,7 @@
 // The live set (128 accumulator + 32 weight + 32 operand + 12 staging registers ...) fits 256 VGPRs without scratch spills.
 #include <type_traits>
 
+#include "sr_view.h"
 #include "sr_wino.h"
 
 // U = G g G^T per (co, ci), stored in MFMA B-fragment order: element (xi, g8, kk, co, e) = U_xi[co][8*g8 + 4*kk + e]
@@ -57,43 +58,10 @@ __global__ void sr_wino_pack_kernel(const float* __restrict__ w, float* __restri
   }
 }
 
-// ---- 16-bit activation I/O (r04; training under torch.autocast, reference options.py:100-101 / train.py:132) ----
-// IO = 0: fp32 tensors (inference, the measured path).  IO = 1 / 2: the input, the residual and the output are fp16 / bf16
-// tensors in HBM -- four channels are ONE 8-byte load or store --, widened to fp32 on the way into LDS and rounded (to
-// nearest even) on the way out; weights, bias, the transforms and the MFMA accumulation stay fp32.  Offsets are in bytes,
-// so only the element size changes: WN_ES(IO).
-#define WN_ES(io) ((io) == 0 ? 4u : 2u)
-typedef unsigned int wn_u2 __attribute__((ext_vector_type(2)));
-template <int IO>
-__device__ __forceinline__ float wn_widen(unsigned short h) {
-  if (IO == 1) return (float)__builtin_bit_cast(_Float16, h);
-  return __builtin_bit_cast(float, (unsigned)h << 16);
-}
-template <int IO>
-__device__ __forceinline__ unsigned short wn_narrow(float f) {
-  if (IO == 1) return __builtin_bit_cast(unsigned short, (_Float16)f);
-  return __builtin_bit_cast(unsigned short, (__bf16)f);
-}
-template <int IO>
-__device__ __forceinline__ float4 wn_io_load(__amdgpu_buffer_rsrc_t r, unsigned voff, unsigned soff) {
-  if (IO == 0) return wn_buf_load(r, voff, soff);
-  const wn_u2 v = __builtin_bit_cast(wn_u2, __builtin_amdgcn_raw_buffer_load_b64(r, (int)voff, (int)soff, 0));
-  return make_float4(wn_widen<IO>((unsigned short)(v.x & 0xffffu)), wn_widen<IO>((unsigned short)(v.x >> 16)),
-                     wn_widen<IO>((unsigned short)(v.y & 0xffffu)), wn_widen<IO>((unsigned short)(v.y >> 16)));
-}
-template <int IO>
-__device__ __forceinline__ void wn_io_store(const float4 v, __amdgpu_buffer_rsrc_t r, unsigned voff, unsigned soff) {
-  if (IO == 0) { wn_buf_store(v, r, voff, soff); return; }
-  wn_u2 t;
-  t.x = (unsigned)wn_narrow<IO>(v.x) | ((unsigned)wn_narrow<IO>(v.y) << 16);
-  t.y = (unsigned)wn_narrow<IO>(v.z) | ((unsigned)wn_narrow<IO>(v.w) << 16);
-  __builtin_amdgcn_raw_buffer_store_b64(t, r, (int)(voff + soff), 0, 0);
-}
-
 template <int NT, bool VEC4, bool VOUT, int IO = 0>
 __global__ __launch_bounds__(256, NT == 1 ? SR_WINO_NT1_WAVES : SR_WINO_WAVES) void sr_wino_kernel(SrWinoParams p) {
   static_assert(IO == 0 || (VEC4 && VOUT), "16-bit I/O exists for the vector staging / epilogue instantiation only");
-  constexpr unsigned ES = WN_ES(IO);   // bytes per activation element
+  constexpr unsigned ES = SR_IO_ES(IO);   // bytes per activation element
   extern __shared__ __attribute__((aligned(16))) float lds[];
   float* O = lds;                           // [4 ur][2][32 tiles][32*NT co]   (epilogue only; aliases raw A)
   float* rawA = lds + WN_V_FLOATS(NT);      // [10*18][20]  odd slabs  (inside the O area: dead by the epilogue)
@@ -155,18 +123,18 @@ __global__ __launch_bounds__(256, NT == 1 ? SR_WINO_NT1_WAVES : SR_WINO_WAVES) v
   // ---- staging: global -> registers -> LDS ----
   // Vector path (VEC4): lane offsets in BYTES relative to the image base, through the buffer descriptor `rs_in`.  For an
   // interior region (the whole 10x18 patch inside the image) they are the per-thread constants `rel` plus the scalar
-  // patch origin `s_org`; a border region computes them with the image test (outside -> WN_OOB -> 0).  Scalar path:
+  // patch origin `s_org`; a border region computes them with the image test (outside -> SR_OOB -> 0).  Scalar path:
   // element offsets from the image pointer, -1 = outside (r03 code, unaligned inputs only).
   int offs[WN_STAGE_PER_THREAD];
   unsigned s_org = 0;
   const float* in_b = p.in;
-  __amdgpu_buffer_rsrc_t rs_in = wn_rsrc(p.in, 0);
+  __amdgpu_buffer_rsrc_t rs_in = sr_rsrc(p.in, 0);
   const int64_t in_img_bytes = ((int64_t)(p.H * p.W - 1) * p.in_sp + p.Cin) * ES;
   const int c_quad = 4 * (tid & 3);      // (tid + 256 it) & 3 == tid & 3: a thread stages the same channel quad of a slab
   auto aim = [&](const Region& r) {  // point the staging loads at region r
     in_b = reinterpret_cast<const float*>(reinterpret_cast<const char*>(p.in) + (int64_t)r.b * p.in_sb * ES);
     if (VEC4) {
-      rs_in = wn_rsrc(in_b, in_img_bytes);
+      rs_in = sr_rsrc(in_b, in_img_bytes);
       const bool interior = (r.oy0 >= 1) & (r.oy0 + 2 * WN_TR + 1 <= p.H) & (r.ox0 >= 1) & (r.ox0 + 2 * WN_TC + 1 <= p.W);
       if (interior) {   // no image test: offsets relative to the patch origin, which rides in the scalar operand
         s_org = (unsigned)(((r.oy0 - 1) * p.W + (r.ox0 - 1)) * p.in_sp) * ES;
@@ -176,7 +144,7 @@ __global__ __launch_bounds__(256, NT == 1 ? SR_WINO_NT1_WAVES : SR_WINO_WAVES) v
           const int px = e >> 2;
           const int py = px / WN_PW, pxx = px - py * WN_PW;
           offs[it] = (it < WN_STAGE_PER_THREAD - 1 || e < WN_STAGE_ELEMS) ? (int)(((py * p.W + pxx) * p.in_sp + c_quad) * ES)
-                                                                          : (int)WN_OOB;
+                                                                          : (int)SR_OOB;
         }
       } else {
         s_org = 0;
@@ -187,7 +155,7 @@ __global__ __launch_bounds__(256, NT == 1 ? SR_WINO_NT1_WAVES : SR_WINO_WAVES) v
           const int py = px / WN_PW, pxx = px - py * WN_PW;
           const int iy = r.oy0 - 1 + py, ix = r.ox0 - 1 + pxx;
           const bool ok = (e < WN_STAGE_ELEMS) & (iy >= 0) & (iy < p.H) & (ix >= 0) & (ix < p.W);
-          offs[it] = ok ? (int)(((iy * p.W + ix) * p.in_sp + c_quad) * ES) : (int)WN_OOB;
+          offs[it] = ok ? (int)(((iy * p.W + ix) * p.in_sp + c_quad) * ES) : (int)SR_OOB;
         }
       }
     } else {
@@ -419,11 +387,11 @@ __global__ __launch_bounds__(256, NT == 1 ? SR_WINO_NT1_WAVES : SR_WINO_WAVES) v
       const int cg = tid % CG;
       const int tile0 = tid / CG;
       const int tr0 = tile0 >> 3, tc0 = tile0 & 7;
-      const __amdgpu_buffer_rsrc_t rs_out = wn_rsrc(outp, ((int64_t)(p.H * p.W - 1) * out_sp + p.Cout) * ES);
+      const __amdgpu_buffer_rsrc_t rs_out = sr_rsrc(outp, ((int64_t)(p.H * p.W - 1) * out_sp + p.Cout) * ES);
       const __amdgpu_buffer_rsrc_t rs_res =
-          wn_rsrc(resp ? (const void*)resp : (const void*)p.wu,
+          sr_rsrc(resp ? (const void*)resp : (const void*)p.wu,
                   resp ? ((int64_t)(p.H * p.W - 1) * p.res_sp + p.Cout) * ES : (int64_t)0);
-      const __amdgpu_buffer_rsrc_t rs_bias = wn_rsrc(bias_p ? (const void*)bias_p : (const void*)p.wu,
+      const __amdgpu_buffer_rsrc_t rs_bias = sr_rsrc(bias_p ? (const void*)bias_p : (const void*)p.wu,
                                                      bias_p ? (int64_t)p.Cout * 4 : (int64_t)0);
       const bool okc = co0 + 4 * cg < p.Cout;
       const bool full = (oy0 + 2 * WN_TR <= p.H) & (ox0 + 2 * WN_TC <= p.W) & (co0 + CO <= p.Cout);   // uniform
@@ -436,7 +404,7 @@ __global__ __launch_bounds__(256, NT == 1 ? SR_WINO_NT1_WAVES : SR_WINO_WAVES) v
       };
       // FULL = the region lies inside the image and the channel block inside Cout (every region of the 240x320 and
       // 120x160 levels): one lane offset per tensor serves all eight (unit, pixel) positions.  Otherwise a per-position
-      // offset, WN_OOB outside the image / past Cout.
+      // offset, SR_OOB outside the image / past Cout.
       // LDS offsets of the O exchange as ONE register each + immediates (laundered per region: hoisted out of the work
       // loop, the compiler kept 16 precomputed addresses in scratch and reloaded them in front of every ds_write)
       int o_wr = (wave * 2 * 32 + 4 * kk) * CO + i, o_rd = tile0 * CO + 4 * cg;
@@ -463,7 +431,7 @@ __global__ __launch_bounds__(256, NT == 1 ? SR_WINO_NT1_WAVES : SR_WINO_WAVES) v
               okm |= (unsigned)(okc & (oy < p.H) & (ox < p.W)) << (4 * it + q);
             }
         }
-        auto lane_off = [&](unsigned v, int it, int q) { return (FULL || ((okm >> (4 * it + q)) & 1u)) ? v : WN_OOB; };
+        auto lane_off = [&](unsigned v, int it, int q) { return (FULL || ((okm >> (4 * it + q)) & 1u)) ? v : SR_OOB; };
         float4 rv[UNITS][4];
         if (RES) {
 #pragma unroll
@@ -472,7 +440,7 @@ __global__ __launch_bounds__(256, NT == 1 ? SR_WINO_NT1_WAVES : SR_WINO_WAVES) v
             for (int q = 0; q < 4; ++q)
               rv[it][q] = wn_io_load<IO>(rs_res, lane_off(v_res, it, q), s_res0 + d_pix(it, q) * rsp4);
         }
-        const float4 bv = wn_buf_load(rs_bias, (FULL || okc) ? 16u * cg : WN_OOB, (unsigned)co0 * 4u);
+        const float4 bv = wn_io_load<0>(rs_bias, (FULL || okc) ? 16u * cg : SR_OOB, (unsigned)co0 * 4u);
         SR_TR(10);
 #pragma unroll
         for (int n = 0; n < NT; ++n) {
@@ -518,7 +486,7 @@ __global__ __launch_bounds__(256, NT == 1 ? SR_WINO_NT1_WAVES : SR_WINO_WAVES) v
           if (!fast_leaky) sr_activate_group(o16, slope);
 #pragma unroll
           for (int q = 0; q < 4; ++q) {
-            wn_io_store<IO>(make_float4(o16[4 * q], o16[4 * q + 1], o16[4 * q + 2], o16[4 * q + 3]), rs_out,
+            sr_io_store<IO>(sr_f4{o16[4 * q], o16[4 * q + 1], o16[4 * q + 2], o16[4 * q + 3]}, rs_out,
                             lane_off(v_out, it, q), s_out0 + d_pix(it, q) * osp4);
           }
         }
@@ -624,8 +592,6 @@ int sr_launch_splitk_reduce(const float* part, int ksplit, int64_t part_stride, 
 
 // ------------------------------------------------------------------ C ABI -------------
 
-static int sr_wino_num_cus() { return sr_device_cus(); }
-
 extern "C" size_t sr_wino_packed_weight_floats(int Cout, int Cin) {
   if (Cout <= 0 || Cin <= 0) return 0;
   const size_t G = (size_t)((Cin + 15) / 16) * 2, Co_pad = (size_t)((Cout + 31) / 32) * 32;
@@ -652,10 +618,6 @@ extern "C" int sr_conv_prefers_wino(int B, int H, int W, int Cin, int Cout, int 
   if (mode == 2) return 1;
   const long regions = (long)((H + 7) / 8) * ((W + 15) / 16);
   const double util = (double)H * W / (double)(regions * 128);
-  const int co_pad = ((Cout + 31) / 32) * 32;
-  const int nt = (co_pad % 64 == 0) ? 2 : 1;
-  const long tiles = regions * B * (co_pad / (32 * nt));
-  (void)tiles;
   return (util >= 0.4 && Cin >= 16) ? 1 : 0;
 }
 
@@ -673,7 +635,7 @@ static SrWinoPlan sr_wino_plan(int B, int H, int W, int Cin, int Cout, bool allo
   const int slabs = (Cin + 15) / 16;
   const int forced_nt = sr_opt(SR_OPT_WINO_NT), forced_ks = sr_opt(SR_OPT_WINO_KSPLIT);
   const long regions = (long)((H + 2 * WN_TR - 1) / (2 * WN_TR)) * ((W + 2 * WN_TC - 1) / (2 * WN_TC)) * B;
-  const long cus = sr_wino_num_cus(), slots = 2 * cus;
+  const long cus = sr_device_cus(), slots = 2 * cus;
   SrWinoPlan best = {co_pad % 64 == 0 ? 2 : 1, 1};
   double best_cost = -1.0;
   for (int nt = 2; nt >= 1; --nt) {
@@ -735,24 +697,24 @@ static int sr_wino_run(const float* in, int64_t in_batch_stride, int in_pix_stri
   p.regions_x = (W + 2 * WN_TC - 1) / (2 * WN_TC);
   p.regions_y = (H + 2 * WN_TR - 1) / (2 * WN_TR);
   p.slope = leaky_slope;
-  p.vec4 = (((uintptr_t)in & amask) == 0) && (in_pix_stride % 4 == 0) && (in_batch_stride % 4 == 0) && (Cin % 4 == 0);
+  p.vec4 = sr_rows_aligned(in, in_batch_stride, in_pix_stride, amask, 4) && (Cin % 4 == 0);
   // vector epilogue: whole 4-channel groups, aligned output / residual / bias rows
-  const bool vout = p.vec4 && (Cout % 4 == 0) && (((uintptr_t)out & amask) == 0) && (out_pix_stride % 4 == 0) &&
-                    (out_batch_stride % 4 == 0) && (!bias || ((uintptr_t)bias & 15) == 0) &&
-                    (!residual || ((((uintptr_t)residual & amask) == 0) && (res_pix_stride % 4 == 0) &&
-                                   (res_batch_stride % 4 == 0)));
+  const bool vout = p.vec4 && (Cout % 4 == 0) && sr_rows_aligned(out, out_batch_stride, out_pix_stride, amask, 4) &&
+                    (!bias || sr_ptr_aligned(bias, 15)) &&
+                    (!residual || sr_rows_aligned(residual, res_batch_stride, res_pix_stride, amask, 4));
   if (io && !vout) return SR_ERR_UNSUPPORTED;   // 16-bit I/O: the vector instantiation only
   const int split = sr_wino_split_mode();
   if (split < 0) return SR_ERR_INVALID_ARGUMENT;
   if (split && (io || !vout)) return SR_ERR_UNSUPPORTED;   // split precision: fp32 tensors, the vector instantiation only
-  const int64_t lim = (int64_t)1 << 31;          // per-image byte offsets are 32-bit (buffer addressing)
-  // (the input-side limit applies to the vector STAGING too -- sr_wino_kernel<NT, true, false> --, not only to the vector
-  // epilogue: its buffer descriptors carry 32-bit byte offsets just the same.  Callers fall back to sr_conv2d_nhwc_fwd.)
-  if (p.vec4 && ((int64_t)((int64_t)H * W - 1) * in_pix_stride + Cin) * 4 >= lim) return SR_ERR_UNSUPPORTED;
-  if (vout && (((int64_t)((int64_t)H * W - 1) * out_pix_stride + Cout) * 4 >= lim ||
-               (residual && ((int64_t)((int64_t)H * W - 1) * res_pix_stride + Cout) * 4 >= lim)))
+  // Per-image byte offsets are 32-bit (buffer addressing).  The input-side limit applies to the vector STAGING too --
+  // sr_wino_kernel<NT, true, false> --, not only to the vector epilogue: its buffer descriptors carry 32-bit byte offsets
+  // just the same.  Callers fall back to sr_conv2d_nhwc_fwd.  (Conservative for 16-bit tensors: the span is taken at 4
+  // bytes per element whatever `io` says.)
+  const int64_t HW = (int64_t)H * W;
+  if (p.vec4 && !sr_view_fits32(HW, in_pix_stride, Cin, 4)) return SR_ERR_UNSUPPORTED;
+  if (vout && (!sr_view_fits32(HW, out_pix_stride, Cout, 4) || (residual && !sr_view_fits32(HW, res_pix_stride, Cout, 4))))
     return SR_ERR_UNSUPPORTED;
-  const bool can_split = !io && vout && workspace && (((uintptr_t)workspace & 15) == 0);   // (partials are fp32: fp32 I/O only)
+  const bool can_split = !io && vout && workspace && sr_ptr_aligned(workspace, 15);   // (partials are fp32: fp32 I/O only)
   SrWinoPlan plan = sr_wino_plan(B, H, W, Cin, Cout, can_split);
   if (plan.ks > 1 && workspace_bytes < (size_t)plan.ks * B * H * W * Cout * sizeof(float))
     plan = sr_wino_plan(B, H, W, Cin, Cout, false);
@@ -764,7 +726,7 @@ static int sr_wino_run(const float* in, int64_t in_batch_stride, int in_pix_stri
   p.total = p.regions_x * p.regions_y * p.co_blocks * B * p.ksplit;
   p.xcd_order = sr_opt(SR_OPT_WINO_XCD);
   hipStream_t stream = (hipStream_t)stream_;
-  int blocks = sr_wino_num_cus() * (nt == 1 ? SR_WINO_NT1_WAVES : SR_WINO_WAVES);
+  int blocks = sr_device_cus() * (nt == 1 ? SR_WINO_NT1_WAVES : SR_WINO_WAVES);
   if (blocks > p.total) blocks = p.total;
   const size_t lds = (size_t)WN_LDS_FLOATS(nt) * sizeof(float);
 #ifdef SR_WINO_TRACE
@@ -777,16 +739,12 @@ static int sr_wino_run(const float* in, int64_t in_batch_stride, int in_pix_stri
 #endif
 #define SR_WINO_LAUNCH_IO(NTV, IOV)                                                                              \
   {                                                                                                               \
-    hipError_t e = hipFuncSetAttribute((const void*)sr_wino_kernel<NTV, true, true, IOV>,                         \
-                                       hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);                     \
-    if (e != hipSuccess) return sr_hip_rc(e);                                                                     \
+    if (hipError_t e = sr_allow_lds((const void*)sr_wino_kernel<NTV, true, true, IOV>, lds)) return sr_hip_rc(e); \
     hipLaunchKernelGGL((sr_wino_kernel<NTV, true, true, IOV>), dim3(blocks), dim3(256), lds, stream, p);          \
   }
 #define SR_WINO_LAUNCH(NTV, V4, VO)                                                                               \
   {                                                                                                               \
-    hipError_t e = hipFuncSetAttribute((const void*)sr_wino_kernel<NTV, V4, VO>,                                  \
-                                       hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);                     \
-    if (e != hipSuccess) return sr_hip_rc(e);                                                                     \
+    if (hipError_t e = sr_allow_lds((const void*)sr_wino_kernel<NTV, V4, VO>, lds)) return sr_hip_rc(e);          \
     hipLaunchKernelGGL((sr_wino_kernel<NTV, V4, VO>), dim3(blocks), dim3(256), lds, stream, p);                   \
   }
   if (split) { const int rc = sr_wino_split_launch(p, nt, blocks, split, stream); if (rc) return rc; }

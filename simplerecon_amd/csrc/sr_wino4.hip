@@ -26,16 +26,10 @@
 #include <stdio.h>
 #include <stdlib.h>
 
-#include <atomic>
-
-#include "sr_common.h"
+#include "sr_buffer.h"
+#include "sr_view.h"
 
 namespace {
-
-typedef float w4_f4 __attribute__((ext_vector_type(4)));
-typedef unsigned int w4_u4 __attribute__((ext_vector_type(4)));
-#define W4_RSRC_FLAGS 0x00020000
-#define W4_OOB 0x7fffffffu
 
 constexpr int W4_PS = 18;                                // patch side: 16 output pixels + 2
 constexpr int W4_RS = 20;                                // floats per staged pixel (16 channels + 4 pad: tiles 4 px apart -> other banks)
@@ -87,17 +81,8 @@ struct SrWino4Params {
 #define W4_TR(code) do {} while (0)
 #endif
 
-__device__ __forceinline__ __amdgpu_buffer_rsrc_t w4_rsrc(const void* base, int64_t bytes) {
-  return __builtin_amdgcn_make_buffer_rsrc(const_cast<void*>(base), 0, (int)bytes, W4_RSRC_FLAGS);
-}
-__device__ __forceinline__ w4_f4 w4_load(__amdgpu_buffer_rsrc_t r, unsigned voff, unsigned soff) {
-  return __builtin_bit_cast(w4_f4, __builtin_amdgcn_raw_buffer_load_b128(r, (int)voff, (int)soff, 0));
-}
-// (the delta rides in the LANE offset: a 16-byte buffer store with an SGPR offset operand followed by a VALU write to its
-// data registers stores the new contents on gfx950 -- sr_wino.h, r04)
-__device__ __forceinline__ void w4_store(w4_f4 v, __amdgpu_buffer_rsrc_t r, unsigned voff) {
-  __builtin_amdgcn_raw_buffer_store_b128(__builtin_bit_cast(w4_u4, v), r, (int)voff, 0, 0);
-}
+// (buffer addressing: sr_buffer.h.  The store's delta rides in the LANE offset -- a 16-byte buffer store with an SGPR offset
+// operand followed by a VALU write to its data registers stores the new contents on gfx950; explained at sr_buf_store.)
 
 // B^T for the points (0, 1/2, -1/2, 2, -2, inf):
 //   [1 0 -17/4 0 1 0; 0 -2 -4 1/2 1 0; 0 2 -4 -1/2 1 0; 0 -1/2 -1/4 2 1 0; 0 1/2 -1/4 -2 1 0; 0 1 0 -17/4 0 1]
@@ -113,9 +98,9 @@ __device__ __forceinline__ void w4_bt(float d0, float d1, float d2, float d3, fl
   t5 = fmaf(-4.25f, d3, d1) + d5;
 }
 // A^T = [1 1 1 1 1 0; 0 1/2 -1/2 2 -2 0; 0 1/4 1/4 4 4 0; 0 1/8 -1/8 8 -8 1] on four channels at once
-__device__ __forceinline__ void w4_at(w4_f4 m0, w4_f4 m1, w4_f4 m2, w4_f4 m3, w4_f4 m4, w4_f4 m5, w4_f4& s0, w4_f4& s1,
-                                      w4_f4& s2, w4_f4& s3) {
-  const w4_f4 p = m1 + m2, q = m1 - m2, u = m3 + m4, v = m3 - m4;
+__device__ __forceinline__ void w4_at(sr_f4 m0, sr_f4 m1, sr_f4 m2, sr_f4 m3, sr_f4 m4, sr_f4 m5, sr_f4& s0, sr_f4& s1,
+                                      sr_f4& s2, sr_f4& s3) {
+  const sr_f4 p = m1 + m2, q = m1 - m2, u = m3 + m4, v = m3 - m4;
   s0 = (m0 + p) + u;
   s1 = 0.5f * q + 2.0f * v;
   s2 = 0.25f * p + 4.0f * u;
@@ -140,14 +125,14 @@ __device__ __forceinline__ W4Item w4_decode(const SrWino4Params& p, int work) {
 // every load in flight at each of those branches).
 __device__ __forceinline__ unsigned w4_sel(bool ok, unsigned off) {
   asm volatile("" : "+v"(off));
-  return ok ? off : W4_OOB;
+  return ok ? off : SR_OOB;
 }
 
 // loads of slab `s` of the patch of item `it` into st[]: out-of-image pixels and channels past Cin read 0
 __device__ __forceinline__ void w4_stage(const SrWino4Params& p, const W4Item& it, int s, int st_q, int st_pp0,
-                                         w4_f4 (&st)[W4_STAGE]) {
+                                         sr_f4 (&st)[W4_STAGE]) {
   const unsigned in_img_bytes = (unsigned)(((int64_t)(p.H * p.W - 1) * p.in_sp + p.Cin) * 4);
-  const __amdgpu_buffer_rsrc_t rs_in = w4_rsrc(p.in + (int64_t)it.b * p.in_sb, in_img_bytes);
+  const __amdgpu_buffer_rsrc_t rs_in = sr_rsrc(p.in + (int64_t)it.b * p.in_sb, in_img_bytes);
   const bool chan_ok = 16 * s + 4 * st_q + 4 <= p.Cin;
   const bool interior = (it.oy0 >= 1) & (it.ox0 >= 1) & (it.oy0 + 17 <= p.H) & (it.ox0 + 17 <= p.W);   // uniform
   const unsigned q_off = (unsigned)(16 * s + 4 * st_q) * 4u;
@@ -158,7 +143,7 @@ __device__ __forceinline__ void w4_stage(const SrWino4Params& p, const W4Item& i
       const int pp = st_pp0 + 64 * j;
       const int r = (pp * 3641) >> 16, c = pp - 18 * r;   // (recomputed per slab: six live registers less)
       const bool ok = j < W4_STAGE - 1 ? chan_ok : (chan_ok & (pp < W4_PS * W4_PS));
-      st[j] = w4_load(rs_in, w4_sel(ok, (unsigned)((r * p.W + c) * p.in_sp) * 4u + q_off), base);
+      st[j] = sr_buf_load(rs_in, w4_sel(ok, (unsigned)((r * p.W + c) * p.in_sp) * 4u + q_off), base);
     }
   } else {
 #pragma unroll
@@ -167,7 +152,7 @@ __device__ __forceinline__ void w4_stage(const SrWino4Params& p, const W4Item& i
       const int r = (pp * 3641) >> 16, c = pp - 18 * r;
       const int y = it.oy0 - 1 + r, x = it.ox0 - 1 + c;
       const bool ok = chan_ok & (pp < W4_PS * W4_PS) & (y >= 0) & (y < p.H) & (x >= 0) & (x < p.W);
-      st[j] = w4_load(rs_in, w4_sel(ok, (unsigned)((y * p.W + x) * p.in_sp) * 4u + q_off), 0u);
+      st[j] = sr_buf_load(rs_in, w4_sel(ok, (unsigned)((y * p.W + x) * p.in_sp) * 4u + q_off), 0u);
     }
   }
 }
@@ -176,7 +161,7 @@ __device__ __forceinline__ void w4_stage(const SrWino4Params& p, const W4Item& i
 // cq + r and this lane's tile), then per output row: + bias + residual, activation, 16-byte stores.  FULL: every pixel of
 // the 16 x 16 region is inside the image (no per-lane predicate).
 template <bool FULL, bool RES>
-__device__ __forceinline__ void w4_epilogue(const SrWino4Params& p, const W4Item& it, w4_f4 (&acc)[36], int cq, int m_j) {
+__device__ __forceinline__ void w4_epilogue(const SrWino4Params& p, const W4Item& it, sr_f4 (&acc)[36], int cq, int m_j) {
 #pragma unroll
   for (int j = 0; j < 6; ++j)
     w4_at(acc[j], acc[6 + j], acc[12 + j], acc[18 + j], acc[24 + j], acc[30 + j], acc[j], acc[6 + j], acc[12 + j],
@@ -184,22 +169,22 @@ __device__ __forceinline__ void w4_epilogue(const SrWino4Params& p, const W4Item
   const int oy = it.oy0 + 4 * (m_j >> 2), ox = it.ox0 + 4 * (m_j & 3);
   const bool cq_ok = cq < p.Cout;
   const unsigned out_img_bytes = (unsigned)(((int64_t)(p.H * p.W - 1) * p.out_sp + p.Cout) * 4);
-  const __amdgpu_buffer_rsrc_t rs_out = w4_rsrc(p.out + (int64_t)it.b * p.out_sb, out_img_bytes);
+  const __amdgpu_buffer_rsrc_t rs_out = sr_rsrc(p.out + (int64_t)it.b * p.out_sb, out_img_bytes);
   const unsigned res_img_bytes = RES ? (unsigned)(((int64_t)(p.H * p.W - 1) * p.res_sp + p.Cout) * 4) : 0u;
-  const __amdgpu_buffer_rsrc_t rs_res = w4_rsrc(RES ? p.res + (int64_t)it.b * p.res_sb : p.wu, res_img_bytes);
+  const __amdgpu_buffer_rsrc_t rs_res = sr_rsrc(RES ? p.res + (int64_t)it.b * p.res_sb : p.wu, res_img_bytes);
   // lane offsets of the tile's first pixel; a lane whose channel quad is past Cout is switched off for good
   const unsigned o0 = w4_sel(cq_ok, (unsigned)((oy * p.W + ox) * p.out_sp + cq) * 4u);
   const unsigned r0 = RES ? w4_sel(cq_ok, (unsigned)((oy * p.W + ox) * p.res_sp + cq) * 4u) : 0u;
-  w4_f4 bv = w4_f4{0.0f, 0.0f, 0.0f, 0.0f};
-  if (p.bias) bv = __builtin_bit_cast(w4_f4, __builtin_amdgcn_raw_buffer_load_b128(w4_rsrc(p.bias, (int64_t)p.Cout * 4),
+  sr_f4 bv = sr_f4{0.0f, 0.0f, 0.0f, 0.0f};
+  if (p.bias) bv = __builtin_bit_cast(sr_f4, __builtin_amdgcn_raw_buffer_load_b128(sr_rsrc(p.bias, (int64_t)p.Cout * 4),
                                                                                    (int)w4_sel(cq_ok, (unsigned)cq * 4u), 0, 0));
   const float slope = sr_uniform(p.slope);
-  w4_f4 rv[2][4];
+  sr_f4 rv[2][4];
   if (RES) {
 #pragma unroll
     for (int l = 0; l < 4; ++l) {
       const bool ok = FULL ? true : ((oy < p.H) & (ox + l < p.W));
-      rv[0][l] = w4_load(rs_res, FULL ? r0 + (unsigned)(l * p.res_sp) * 4u : w4_sel(ok, r0 + (unsigned)(l * p.res_sp) * 4u), 0u);
+      rv[0][l] = sr_buf_load(rs_res, FULL ? r0 + (unsigned)(l * p.res_sp) * 4u : w4_sel(ok, r0 + (unsigned)(l * p.res_sp) * 4u), 0u);
     }
   }
 #pragma unroll
@@ -209,7 +194,7 @@ __device__ __forceinline__ void w4_epilogue(const SrWino4Params& p, const W4Item
       for (int l = 0; l < 4; ++l) {
         const unsigned d = (unsigned)(((k + 1) * p.W + l) * p.res_sp) * 4u;
         const bool ok = FULL ? true : ((oy + k + 1 < p.H) & (ox + l < p.W));
-        rv[(k + 1) & 1][l] = w4_load(rs_res, FULL ? r0 + d : w4_sel(ok, r0 + d), 0u);
+        rv[(k + 1) & 1][l] = sr_buf_load(rs_res, FULL ? r0 + d : w4_sel(ok, r0 + d), 0u);
       }
     }
     w4_at(acc[6 * k], acc[6 * k + 1], acc[6 * k + 2], acc[6 * k + 3], acc[6 * k + 4], acc[6 * k + 5], acc[6 * k],
@@ -217,7 +202,7 @@ __device__ __forceinline__ void w4_epilogue(const SrWino4Params& p, const W4Item
     float o16[16];   // the row's 4 pixels x 4 channels: ONE activation-code test per row (a per-quad test is 5 scalar branches)
 #pragma unroll
     for (int l = 0; l < 4; ++l) {
-      w4_f4 y = acc[6 * k + l] + bv;
+      sr_f4 y = acc[6 * k + l] + bv;
       if (RES) y = y + rv[k & 1][l];
 #pragma unroll
       for (int r = 0; r < 4; ++r) o16[4 * l + r] = y[r];
@@ -227,7 +212,7 @@ __device__ __forceinline__ void w4_epilogue(const SrWino4Params& p, const W4Item
     for (int l = 0; l < 4; ++l) {
       const unsigned d = (unsigned)((k * p.W + l) * p.out_sp) * 4u;
       const bool ok = FULL ? true : ((oy + k < p.H) & (ox + l < p.W));
-      w4_store(w4_f4{o16[4 * l], o16[4 * l + 1], o16[4 * l + 2], o16[4 * l + 3]}, rs_out, FULL ? o0 + d : w4_sel(ok, o0 + d));
+      sr_buf_store(sr_f4{o16[4 * l], o16[4 * l + 1], o16[4 * l + 2], o16[4 * l + 3]}, rs_out, FULL ? o0 + d : w4_sel(ok, o0 + d));
     }
   }
 }
@@ -268,11 +253,11 @@ __device__ __forceinline__ void w4_transform(const float* t_rd, float* t_wr) {
 // the first W4_PD frequency pairs' weight fragments of a slab (issued a barrier ahead of the MFMA tick that uses them)
 template <int NA = W4_NA, int PD = W4_PD>
 __device__ __forceinline__ void w4_u_prefetch(__amdgpu_buffer_rsrc_t rs_u, unsigned u_voff, unsigned u_slab, unsigned u_fstride,
-                                              w4_f4 (&ua)[NA][2]) {
+                                              sr_f4 (&ua)[NA][2]) {
 #pragma unroll
   for (int fp = 0; fp < PD; ++fp) {
-    ua[fp][0] = w4_load(rs_u, u_voff, u_slab + (unsigned)(2 * fp) * u_fstride);
-    ua[fp][1] = w4_load(rs_u, u_voff, u_slab + (unsigned)(2 * fp + 1) * u_fstride);
+    ua[fp][0] = sr_buf_load(rs_u, u_voff, u_slab + (unsigned)(2 * fp) * u_fstride);
+    ua[fp][1] = sr_buf_load(rs_u, u_voff, u_slab + (unsigned)(2 * fp + 1) * u_fstride);
   }
 }
 
@@ -282,24 +267,24 @@ __device__ __forceinline__ void w4_u_prefetch(__amdgpu_buffer_rsrc_t rs_u, unsig
 // operand instead of 144 registers that somebody had to clear.
 template <bool FIRST = false, int NA = W4_NA, int PD = W4_PD>
 __device__ __forceinline__ void w4_mfma_tick(__amdgpu_buffer_rsrc_t rs_u, unsigned u_voff, unsigned u_slab, unsigned u_fstride,
-                                             const float* m_rd, w4_f4 (&ua)[NA][2], w4_f4 (&acc)[36]) {
+                                             const float* m_rd, sr_f4 (&ua)[NA][2], sr_f4 (&acc)[36]) {
   w4_prio_mfma();
-  w4_f4 vb[2][2];
-  vb[0][0] = *reinterpret_cast<const w4_f4*>(m_rd);
-  vb[0][1] = *reinterpret_cast<const w4_f4*>(m_rd + 256);
+  sr_f4 vb[2][2];
+  vb[0][0] = *reinterpret_cast<const sr_f4*>(m_rd);
+  vb[0][1] = *reinterpret_cast<const sr_f4*>(m_rd + 256);
 #pragma unroll
   for (int fp = 0; fp < 18; ++fp) {
     if (fp + PD < 18) {
-      ua[(fp + PD) % NA][0] = w4_load(rs_u, u_voff, u_slab + (unsigned)(2 * (fp + PD)) * u_fstride);
-      ua[(fp + PD) % NA][1] = w4_load(rs_u, u_voff, u_slab + (unsigned)(2 * (fp + PD) + 1) * u_fstride);
+      ua[(fp + PD) % NA][0] = sr_buf_load(rs_u, u_voff, u_slab + (unsigned)(2 * (fp + PD)) * u_fstride);
+      ua[(fp + PD) % NA][1] = sr_buf_load(rs_u, u_voff, u_slab + (unsigned)(2 * (fp + PD) + 1) * u_fstride);
     }
     if (fp + 1 < 18) {
-      vb[(fp + 1) & 1][0] = *reinterpret_cast<const w4_f4*>(m_rd + (2 * fp + 2) * 256);
-      vb[(fp + 1) & 1][1] = *reinterpret_cast<const w4_f4*>(m_rd + (2 * fp + 3) * 256);
+      vb[(fp + 1) & 1][0] = *reinterpret_cast<const sr_f4*>(m_rd + (2 * fp + 2) * 256);
+      vb[(fp + 1) & 1][1] = *reinterpret_cast<const sr_f4*>(m_rd + (2 * fp + 3) * 256);
     }
 #pragma unroll
     for (int e = 0; e < 4; ++e) {
-      const w4_f4 zero = w4_f4{0.0f, 0.0f, 0.0f, 0.0f};
+      const sr_f4 zero = sr_f4{0.0f, 0.0f, 0.0f, 0.0f};
       acc[2 * fp] = __builtin_amdgcn_mfma_f32_16x16x4f32(ua[fp % NA][0][e], vb[fp & 1][0][e], (FIRST && e == 0) ? zero : acc[2 * fp], 0, 0, 0);
       acc[2 * fp + 1] = __builtin_amdgcn_mfma_f32_16x16x4f32(ua[fp % NA][1][e], vb[fp & 1][1][e], (FIRST && e == 0) ? zero : acc[2 * fp + 1], 0, 0, 0);
       __builtin_amdgcn_sched_barrier(0);   // keep the two accumulators interleaved (left alone hipcc issues 4 dependent MFMAs in a row)
@@ -308,7 +293,7 @@ __device__ __forceinline__ void w4_mfma_tick(__amdgpu_buffer_rsrc_t rs_u, unsign
   w4_prio_other();
 }
 
-__device__ __forceinline__ void w4_finish(const SrWino4Params& p, const W4Item& it, w4_f4 (&acc)[36], int wave, int m_kq,
+__device__ __forceinline__ void w4_finish(const SrWino4Params& p, const W4Item& it, sr_f4 (&acc)[36], int wave, int m_kq,
                                           int m_j, int tid) {
   const int cq = it.co0 + 16 * wave + 4 * m_kq;                       // first of this lane's 4 output channels
   const bool full = (it.oy0 + 16 <= p.H) & (it.ox0 + 16 <= p.W);      // uniform
@@ -345,28 +330,28 @@ __global__ __launch_bounds__(256, 2) void sr_wino4_kernel(SrWino4Params p) {
   int work = blockIdx.x;
   if (work >= p.total) return;
   W4Item it = w4_decode(p, work);
-  w4_f4 st[W4_STAGE];
+  sr_f4 st[W4_STAGE];
   w4_stage(p, it, 0, st_q, st_pp0, st);
-  const __amdgpu_buffer_rsrc_t rs_u = w4_rsrc(p.wu, (int64_t)36 * p.S * 4 * p.Co_pad * 16);
+  const __amdgpu_buffer_rsrc_t rs_u = sr_rsrc(p.wu, (int64_t)36 * p.S * 4 * p.Co_pad * 16);
   for (;;) {
     const int next_work = work + (int)gridDim.x;
     const bool has_next = next_work < p.total;
     const W4Item nxt = w4_decode(p, has_next ? next_work : work);
-    w4_f4 acc[36];
+    sr_f4 acc[36];
 #pragma unroll
-    for (int f = 0; f < 36; ++f) acc[f] = w4_f4{0.0f, 0.0f, 0.0f, 0.0f};
+    for (int f = 0; f < 36; ++f) acc[f] = sr_f4{0.0f, 0.0f, 0.0f, 0.0f};
     const unsigned u_item = (unsigned)it.co0 * 16u;
     for (int s = 0; s < p.S; ++s) {
       // this slab's patch registers -> LDS; then the next slab's (or the next item's first) loads
 #pragma unroll
-      for (int j = 0; j < W4_STAGE - 1; ++j) *reinterpret_cast<w4_f4*>(st_wr + j * 64 * W4_RS) = st[j];
-      if (tid < 16) *reinterpret_cast<w4_f4*>(st_wr + (W4_STAGE - 1) * 64 * W4_RS) = st[W4_STAGE - 1];
+      for (int j = 0; j < W4_STAGE - 1; ++j) *reinterpret_cast<sr_f4*>(st_wr + j * 64 * W4_RS) = st[j];
+      if (tid < 16) *reinterpret_cast<sr_f4*>(st_wr + (W4_STAGE - 1) * 64 * W4_RS) = st[W4_STAGE - 1];
       if (s + 1 < p.S) w4_stage(p, it, s + 1, st_q, st_pp0, st);
       else if (has_next) w4_stage(p, nxt, 0, st_q, st_pp0, st);
       __syncthreads();   // raw visible; every wave is past the previous slab's V reads
       w4_transform(t_rd, t_wr);
       __syncthreads();   // V visible (and raw free for the next slab's store)
-      w4_f4 ua[W4_NA][2];
+      sr_f4 ua[W4_NA][2];
       w4_u_prefetch(rs_u, u_voff, u_item + (unsigned)s * u_sstride, u_fstride, ua);
       w4_mfma_tick(rs_u, u_voff, u_item + (unsigned)s * u_sstride, u_fstride, m_rd, ua, acc);
     }
@@ -426,20 +411,20 @@ __global__ __launch_bounds__(512, 2) void sr_wino4pp_kernel(SrWino4Params p) {
   if (n_mine > 0) {
     int work = slot;
     W4Item it = w4_decode(p, work);
-    w4_f4 st[W4_STAGE];
-    w4_f4 acc[36];
+    sr_f4 st[W4_STAGE];
+    sr_f4 acc[36];
 #pragma unroll
-    for (int f = 0; f < 36; ++f) acc[f] = w4_f4{0.0f, 0.0f, 0.0f, 0.0f};
-    w4_f4 ua[W4_NA][2];
-    const __amdgpu_buffer_rsrc_t rs_u = w4_rsrc(p.wu, (int64_t)36 * p.S * 4 * p.Co_pad * 16);
+    for (int f = 0; f < 36; ++f) acc[f] = sr_f4{0.0f, 0.0f, 0.0f, 0.0f};
+    sr_f4 ua[W4_NA][2];
+    const __amdgpu_buffer_rsrc_t rs_u = sr_rsrc(p.wu, (int64_t)36 * p.S * 4 * p.Co_pad * 16);
     if (grp == 1) { __syncthreads(); ++bars; }   // one tick late
     // first patch: slab 0 -> raw (this group's own buffer, nobody else reads it: no barrier needed before its own T ... but the
     // writers are 4 waves and the readers other threads of the group: the tick barrier below comes AFTER T, so synchronise the
     // group here through a workgroup barrier that the other group matches with one of its own ticks)
     w4_stage(p, it, 0, st_q, st_pp0, st);
 #pragma unroll
-    for (int j = 0; j < W4_STAGE - 1; ++j) *reinterpret_cast<w4_f4*>(st_wr + j * 64 * W4_RS) = st[j];
-    if (tid < 16) *reinterpret_cast<w4_f4*>(st_wr + (W4_STAGE - 1) * 64 * W4_RS) = st[W4_STAGE - 1];
+    for (int j = 0; j < W4_STAGE - 1; ++j) *reinterpret_cast<sr_f4*>(st_wr + j * 64 * W4_RS) = st[j];
+    if (tid < 16) *reinterpret_cast<sr_f4*>(st_wr + (W4_STAGE - 1) * 64 * W4_RS) = st[W4_STAGE - 1];
     {
       const bool more = p.S > 1 || n_mine > 1;
       if (more) {
@@ -465,8 +450,8 @@ __global__ __launch_bounds__(512, 2) void sr_wino4pp_kernel(SrWino4Params p) {
         const bool last = s + 1 == p.S;
         if (!last || has_next) {
 #pragma unroll
-          for (int j = 0; j < W4_STAGE - 1; ++j) *reinterpret_cast<w4_f4*>(st_wr + j * 64 * W4_RS) = st[j];
-          if (tid < 16) *reinterpret_cast<w4_f4*>(st_wr + (W4_STAGE - 1) * 64 * W4_RS) = st[W4_STAGE - 1];
+          for (int j = 0; j < W4_STAGE - 1; ++j) *reinterpret_cast<sr_f4*>(st_wr + j * 64 * W4_RS) = st[j];
+          if (tid < 16) *reinterpret_cast<sr_f4*>(st_wr + (W4_STAGE - 1) * 64 * W4_RS) = st[W4_STAGE - 1];
           if (s + 2 < p.S) w4_stage(p, it, s + 2, st_q, st_pp0, st);
           else if (!last && has_next) w4_stage(p, nxt, 0, st_q, st_pp0, st);                  // s + 2 == S: the next item's slab 0
           else if (last && has_next) {                                                         // the next item's slab 1 / its successor's slab 0
@@ -490,7 +475,7 @@ __global__ __launch_bounds__(512, 2) void sr_wino4pp_kernel(SrWino4Params p) {
       w4_finish(p, it, acc, wave, m_kq, m_j, tid);
       W4_TR(7);
 #pragma unroll
-      for (int f = 0; f < 36; ++f) acc[f] = w4_f4{0.0f, 0.0f, 0.0f, 0.0f};
+      for (int f = 0; f < 36; ++f) acc[f] = sr_f4{0.0f, 0.0f, 0.0f, 0.0f};
       if (has_next) {
         w4_transform(t_rd, t_wr);
         w4_u_prefetch(rs_u, u_voff, (unsigned)nxt.co0 * 16u, u_fstride, ua);
@@ -574,16 +559,16 @@ __device__ __forceinline__ void w4_at2(w4_f2 m0, w4_f2 m1, w4_f2 m2, w4_f2 m3, w
   s2 = w4_fma2(0.25f, p, 4.0f * u);
   s3 = w4_fma2(0.125f, q, w4_fma2(8.0f, v, m5));
 }
-__device__ __forceinline__ void w4_at_pk(w4_f4& a0, w4_f4& a1, w4_f4& a2, w4_f4& a3, const w4_f4& a4, const w4_f4& a5) {
+__device__ __forceinline__ void w4_at_pk(sr_f4& a0, sr_f4& a1, sr_f4& a2, sr_f4& a3, const sr_f4& a4, const sr_f4& a5) {
   w4_f2 lo[4], hi[4];
   w4_at2(w4_f2{a0[0], a0[1]}, w4_f2{a1[0], a1[1]}, w4_f2{a2[0], a2[1]}, w4_f2{a3[0], a3[1]}, w4_f2{a4[0], a4[1]}, w4_f2{a5[0], a5[1]},
          lo[0], lo[1], lo[2], lo[3]);
   w4_at2(w4_f2{a0[2], a0[3]}, w4_f2{a1[2], a1[3]}, w4_f2{a2[2], a2[3]}, w4_f2{a3[2], a3[3]}, w4_f2{a4[2], a4[3]}, w4_f2{a5[2], a5[3]},
          hi[0], hi[1], hi[2], hi[3]);
-  a0 = w4_f4{lo[0][0], lo[0][1], hi[0][0], hi[0][1]};
-  a1 = w4_f4{lo[1][0], lo[1][1], hi[1][0], hi[1][1]};
-  a2 = w4_f4{lo[2][0], lo[2][1], hi[2][0], hi[2][1]};
-  a3 = w4_f4{lo[3][0], lo[3][1], hi[3][0], hi[3][1]};
+  a0 = sr_f4{lo[0][0], lo[0][1], hi[0][0], hi[0][1]};
+  a1 = sr_f4{lo[1][0], lo[1][1], hi[1][0], hi[1][1]};
+  a2 = sr_f4{lo[2][0], lo[2][1], hi[2][0], hi[2][1]};
+  a3 = sr_f4{lo[3][0], lo[3][1], hi[3][0], hi[3][1]};
 }
 
 // The work-item cursor of a role: (region column, region row, image, output-channel block) of item `work`, advanced by the grid
@@ -661,19 +646,19 @@ __device__ __forceinline__ void w4_transform36_half(const float* t_rd, float* t_
 // (uniform; past the workgroup's last slab): the same six instructions with every lane switched off -- a load that is skipped on
 // SOME path makes the compiler's s_waitcnt for the loads in flight wait for everything.
 __device__ __forceinline__ void w4ws_stage(const SrWino4Params& p, const W4Item& it, int s, bool valid, int st_q, int st_pp0,
-                                           const unsigned (&st_off)[W4_STAGE], w4_f4 (&st)[W4_STAGE]) {
+                                           const unsigned (&st_off)[W4_STAGE], sr_f4 (&st)[W4_STAGE]) {
   const bool interior = (it.oy0 >= 1) & (it.ox0 >= 1) & (it.oy0 + 17 <= p.H) & (it.ox0 + 17 <= p.W);   // uniform
   const unsigned in_img_bytes = (unsigned)(((int64_t)(p.H * p.W - 1) * p.in_sp + p.Cin) * 4);
-  const __amdgpu_buffer_rsrc_t rs_in = w4_rsrc(p.in + (int64_t)it.b * p.in_sb, in_img_bytes);
+  const __amdgpu_buffer_rsrc_t rs_in = sr_rsrc(p.in + (int64_t)it.b * p.in_sb, in_img_bytes);
   const bool chan_ok = valid & (16 * s + 4 * st_q + 4 <= p.Cin);
   if (interior) {
     const unsigned base = (unsigned)(((it.oy0 - 1) * p.W + (it.ox0 - 1)) * p.in_sp + 16 * s) * 4u;   // scalar offset operand
     if (valid && 16 * s + 16 <= p.Cin) {   // (uniform) every channel quad of the slab exists
 #pragma unroll
-      for (int j = 0; j < W4_STAGE; ++j) st[j] = w4_load(rs_in, st_off[j], base);
+      for (int j = 0; j < W4_STAGE; ++j) st[j] = sr_buf_load(rs_in, st_off[j], base);
     } else {
 #pragma unroll
-      for (int j = 0; j < W4_STAGE; ++j) st[j] = w4_load(rs_in, chan_ok ? st_off[j] : W4_OOB, base);
+      for (int j = 0; j < W4_STAGE; ++j) st[j] = sr_buf_load(rs_in, chan_ok ? st_off[j] : SR_OOB, base);
     }
   } else {
     const unsigned q_off = (unsigned)(16 * s + 4 * st_q) * 4u;
@@ -683,7 +668,7 @@ __device__ __forceinline__ void w4ws_stage(const SrWino4Params& p, const W4Item&
       const int r = (pp * 3641) >> 16, c = pp - 18 * r;
       const int y = it.oy0 - 1 + r, x = it.ox0 - 1 + c;
       const bool ok = chan_ok & (pp < W4_PS * W4_PS) & (y >= 0) & (y < p.H) & (x >= 0) & (x < p.W);
-      st[j] = w4_load(rs_in, w4_sel(ok, (unsigned)((y * p.W + x) * p.in_sp) * 4u + q_off), 0u);
+      st[j] = sr_buf_load(rs_in, w4_sel(ok, (unsigned)((y * p.W + x) * p.in_sp) * 4u + q_off), 0u);
     }
   }
 }
@@ -735,7 +720,7 @@ __global__ __launch_bounds__(512, 2) void sr_wino4ws_kernel(SrWino4Params p) {
     for (int j = 0; j < W4_STAGE; ++j) {
       const int pp = st_pp0 + 64 * j;
       const int r = (pp * 3641) >> 16, c = pp - 18 * r;
-      st_off[j] = pp < W4_PS * W4_PS ? (unsigned)((r * p.W + c) * p.in_sp + 4 * st_q) * 4u : W4_OOB;
+      st_off[j] = pp < W4_PS * W4_PS ? (unsigned)((r * p.W + c) * p.in_sp + 4 * st_q) * 4u : SR_OOB;
     }
     // output role: channel quad o_c of the pixels pxl_i = (tid >> 4) + 16 i, i = 0 .. 7, of a half tile (16 tiles x 2 x 4 pixels:
     // pxl = 8 tile + 4 kk + l).  With t0 = tid >> 7, kk = (tid >> 6) & 1, l = (tid >> 4) & 3:  tile_i = t0 + 2 i, so pixel i of half h
@@ -754,9 +739,9 @@ __global__ __launch_bounds__(512, 2) void sr_wino4ws_kernel(SrWino4Params p) {
     W4Cursor ld = w4_cursor(p, first);   // the patch to load next: slab ld_s of item ld
     int ld_s = 0;
     W4Cursor ep = ld;                              // the item whose output tile comes next
-    w4_f4 st[W4_STAGE];
-    w4_f4 rv[16];
-    w4_f4 bv;
+    sr_f4 st[W4_STAGE];
+    sr_f4 rv[16];
+    sr_f4 bv;
 
     auto load_next = [&](bool valid) {
       w4ws_stage(p, w4_item(ld), ld_s, valid, st_q, st_pp0, st_off, st);
@@ -765,47 +750,47 @@ __global__ __launch_bounds__(512, 2) void sr_wino4ws_kernel(SrWino4Params p) {
     auto store_patch = [&](int par) {
       float* wr = lds + par * W4_RAW_FLOATS + st_wr_off;
 #pragma unroll
-      for (int j = 0; j < W4_STAGE - 1; ++j) *reinterpret_cast<w4_f4*>(wr + j * 64 * W4_RS) = st[j];
-      if (tid < 16) *reinterpret_cast<w4_f4*>(wr + (W4_STAGE - 1) * 64 * W4_RS) = st[W4_STAGE - 1];
+      for (int j = 0; j < W4_STAGE - 1; ++j) *reinterpret_cast<sr_f4*>(wr + j * 64 * W4_RS) = st[j];
+      if (tid < 16) *reinterpret_cast<sr_f4*>(wr + (W4_STAGE - 1) * 64 * W4_RS) = st[W4_STAGE - 1];
     };
     // residual of the whole 16 x 16 x 64 tile of item `eit` + its bias quad (an empty buffer reads 0): 17 loads
     auto residual_loads = [&](const W4Item& eit) {
       const bool cq_ok = eit.co0 + 4 * o_c < p.Cout;
-      bv = __builtin_bit_cast(w4_f4, __builtin_amdgcn_raw_buffer_load_b128(w4_rsrc(p.bias ? p.bias : p.wu, p.bias ? (int64_t)p.Cout * 4 : 0),
-                                                                          (int)(cq_ok ? (unsigned)(eit.co0 + 4 * o_c) * 4u : W4_OOB), 0, 0));
+      bv = __builtin_bit_cast(sr_f4, __builtin_amdgcn_raw_buffer_load_b128(sr_rsrc(p.bias ? p.bias : p.wu, p.bias ? (int64_t)p.Cout * 4 : 0),
+                                                                          (int)(cq_ok ? (unsigned)(eit.co0 + 4 * o_c) * 4u : SR_OOB), 0, 0));
       if (!RES) return;
       const bool full = (eit.oy0 + 16 <= p.H) & (eit.ox0 + 16 <= p.W);   // uniform
-      const __amdgpu_buffer_rsrc_t rs_res = w4_rsrc(p.res + (int64_t)eit.b * p.res_sb, res_img_bytes);
+      const __amdgpu_buffer_rsrc_t rs_res = sr_rsrc(p.res + (int64_t)eit.b * p.res_sb, res_img_bytes);
       const unsigned rbase = (unsigned)((eit.oy0 * p.W + eit.ox0) * p.res_sp + eit.co0) * 4u;   // scalar
-      const unsigned rl = cq_ok ? r_lane : W4_OOB;
+      const unsigned rl = cq_ok ? r_lane : SR_OOB;
 #pragma unroll
       for (int h = 0; h < 2; ++h)
 #pragma unroll
         for (int i = 0; i < 8; ++i) {
           const unsigned d = (unsigned)(((4 * (i >> 1) + 2 * h) * p.W + 8 * (i & 1)) * p.res_sp) * 4u;   // scalar
           if (full) {
-            rv[8 * h + i] = w4_load(rs_res, rl, rbase + d);
+            rv[8 * h + i] = sr_buf_load(rs_res, rl, rbase + d);
           } else {
             const bool ok = (eit.oy0 + 4 * (i >> 1) + 2 * h + o_kk < p.H) & (eit.ox0 + 4 * o_t0 + 8 * (i & 1) + o_l < p.W);
-            rv[8 * h + i] = w4_load(rs_res, ok ? rl : W4_OOB, rbase + d);
+            rv[8 * h + i] = sr_buf_load(rs_res, ok ? rl : SR_OOB, rbase + d);
           }
         }
     };
-    auto read_half = [&](w4_f4 (&y)[8]) {
+    auto read_half = [&](sr_f4 (&y)[8]) {
 #pragma unroll
-      for (int i = 0; i < 8; ++i) y[i] = *reinterpret_cast<const w4_f4*>(OUT + i * 16 * 64 * 4 + (o_cx ^ (32 * i)));
+      for (int i = 0; i < 8; ++i) y[i] = *reinterpret_cast<const sr_f4*>(OUT + i * 16 * 64 * 4 + (o_cx ^ (32 * i)));
     };
     // half h of the tile of item `eit`: + bias + residual, activation, stores
-    auto output_half = [&](const W4Item& eit, int h, const w4_f4 (&y)[8]) {
+    auto output_half = [&](const W4Item& eit, int h, const sr_f4 (&y)[8]) {
       const bool cq_ok = eit.co0 + 4 * o_c < p.Cout;
       const bool full = (eit.oy0 + 16 <= p.H) & (eit.ox0 + 16 <= p.W);   // uniform
-      const __amdgpu_buffer_rsrc_t rs_out = w4_rsrc(p.out + (int64_t)eit.b * p.out_sb, out_img_bytes);
+      const __amdgpu_buffer_rsrc_t rs_out = sr_rsrc(p.out + (int64_t)eit.b * p.out_sb, out_img_bytes);
       const unsigned obase = (unsigned)((eit.oy0 * p.W + eit.ox0) * p.out_sp + eit.co0) * 4u;   // scalar
-      const unsigned ol = cq_ok ? o_lane : W4_OOB;
+      const unsigned ol = cq_ok ? o_lane : SR_OOB;
       float o[32];
 #pragma unroll
       for (int i = 0; i < 8; ++i) {
-        w4_f4 v = y[i] + bv;
+        sr_f4 v = y[i] + bv;
         if (RES) v = v + rv[8 * h + i];
 #pragma unroll
         for (int e = 0; e < 4; ++e) o[4 * i + e] = v[e];
@@ -823,14 +808,14 @@ __global__ __launch_bounds__(512, 2) void sr_wino4ws_kernel(SrWino4Params p) {
       if (full) {
 #pragma unroll
         for (int i = 0; i < 8; ++i)
-          w4_store(w4_f4{o[4 * i], o[4 * i + 1], o[4 * i + 2], o[4 * i + 3]}, rs_out,
+          sr_buf_store(sr_f4{o[4 * i], o[4 * i + 1], o[4 * i + 2], o[4 * i + 3]}, rs_out,
                    ol + obase + (unsigned)(((4 * (i >> 1) + 2 * h) * p.W + 8 * (i & 1)) * p.out_sp) * 4u);
       } else {
 #pragma unroll
         for (int i = 0; i < 8; ++i) {
           const bool ok = (eit.oy0 + 4 * (i >> 1) + 2 * h + o_kk < p.H) & (eit.ox0 + 4 * o_t0 + 8 * (i & 1) + o_l < p.W);
           const unsigned voff = ol + obase + (unsigned)(((4 * (i >> 1) + 2 * h) * p.W + 8 * (i & 1)) * p.out_sp) * 4u;
-          w4_store(w4_f4{o[4 * i], o[4 * i + 1], o[4 * i + 2], o[4 * i + 3]}, rs_out, ok ? voff : W4_OOB);
+          sr_buf_store(sr_f4{o[4 * i], o[4 * i + 1], o[4 * i + 2], o[4 * i + 3]}, rs_out, ok ? voff : SR_OOB);
         }
       }
     };
@@ -845,7 +830,7 @@ __global__ __launch_bounds__(512, 2) void sr_wino4ws_kernel(SrWino4Params p) {
       const bool closing = k >= 1 && cs == 0;                  // (uniform) the M waves close an item in THIS tick
       cs = cs + 1 == p.S ? 0 : cs + 1;
       const W4Item eit = w4_item(ep);
-      w4_f4 y[8];
+      sr_f4 y[8];
       W4_TR(1);
       if (ep_now) {
         read_half(y);
@@ -881,7 +866,7 @@ __global__ __launch_bounds__(512, 2) void sr_wino4ws_kernel(SrWino4Params p) {
     }
     {   // the last item closed in tick K
       const W4Item eit = w4_item(ep);
-      w4_f4 y[8];
+      sr_f4 y[8];
       read_half(y);
       __syncthreads();   // B2
       __syncthreads();   // B3
@@ -897,11 +882,11 @@ __global__ __launch_bounds__(512, 2) void sr_wino4ws_kernel(SrWino4Params p) {
     const unsigned u_voff = (unsigned)(m_kq * p.Co_pad + 16 * wave + m_j) * 16u;
     const unsigned u_fstride = (unsigned)p.S * 4u * (unsigned)p.Co_pad * 16u;
     const unsigned u_sstride = 4u * (unsigned)p.Co_pad * 16u;
-    const __amdgpu_buffer_rsrc_t rs_u = w4_rsrc(p.wu, (int64_t)36 * p.S * 4 * p.Co_pad * 16);
+    const __amdgpu_buffer_rsrc_t rs_u = sr_rsrc(p.wu, (int64_t)36 * p.S * 4 * p.Co_pad * 16);
     // this lane's 16-byte chunk (output channels 16 wave + 4 m_kq ...) of the 8 pixel records of its tile's half
     float* const OUT = lds + W4_WS_OUT + m_j * 8 * 64 + 4 * ((4 * wave + m_kq) ^ m_j);
-    w4_f4 acc[36];
-    w4_f4 ua[W4WS_NA][2];
+    sr_f4 acc[36];
+    sr_f4 ua[W4WS_NA][2];
     W4Cursor cur = w4_cursor(p, first);
     int s = 0;
     w4_u_prefetch<W4WS_NA, W4WS_PD>(rs_u, u_voff, (unsigned)(64 * cur.cb) * 16u, u_fstride, ua);
@@ -929,7 +914,7 @@ __global__ __launch_bounds__(512, 2) void sr_wino4ws_kernel(SrWino4Params p) {
 #pragma unroll
         for (int r = 0; r < 2; ++r)
 #pragma unroll
-          for (int l = 0; l < 4; ++l) *reinterpret_cast<w4_f4*>(OUT + (4 * r + l) * 64) = acc[6 * r + l];
+          for (int l = 0; l < 4; ++l) *reinterpret_cast<sr_f4*>(OUT + (4 * r + l) * 64) = acc[6 * r + l];
         W4_TR(7);
         __syncthreads();   // ---- F: end of tick k (half 0 visible)
         W4_TR(12);
@@ -941,7 +926,7 @@ __global__ __launch_bounds__(512, 2) void sr_wino4ws_kernel(SrWino4Params p) {
 #pragma unroll
         for (int r = 2; r < 4; ++r)
 #pragma unroll
-          for (int l = 0; l < 4; ++l) *reinterpret_cast<w4_f4*>(OUT + (4 * (r - 2) + l) * 64) = acc[6 * r + l];
+          for (int l = 0; l < 4; ++l) *reinterpret_cast<sr_f4*>(OUT + (4 * (r - 2) + l) * 64) = acc[6 * r + l];
         __syncthreads();   // B3: half 1 visible
         W4_TR(11);
       } else {
@@ -988,28 +973,12 @@ __global__ void sr_wino4_pack_kernel(const float* __restrict__ w, float* __restr
   }
 }
 
-// CU count of the CURRENT device (cached per device id; -1 = not asked yet)
-constexpr int W4_MAX_DEVICES = 64;
-int w4_current_device() {
-  int dev = 0;
-  return hipGetDevice(&dev) == hipSuccess && dev >= 0 && dev < W4_MAX_DEVICES ? dev : 0;
+// A device that refuses the kernel's dynamic LDS answers SR_ERR_UNSUPPORTED (the caller falls back to the F(2x2) kernel).
+int w4_allow_lds(const void* kernel, int bytes) {
+  if (sr_allow_lds(kernel, (size_t)bytes) == hipSuccess) return SR_OK;
+  (void)hipGetLastError();
+  return SR_ERR_UNSUPPORTED;
 }
-int w4_num_cus() { return sr_device_cus(); }
-// hipFuncAttributeMaxDynamicSharedMemorySize once per (kernel, device) instead of once per launch; a device that refuses the
-// size answers SR_ERR_UNSUPPORTED (the caller falls back to the F(2x2) kernel) -- ADVICE r05.
-int w4_allow_lds(const void* kernel, int slot, int bytes) {
-  static std::atomic<int> state[8][W4_MAX_DEVICES];   // 0: not set, 1: ok, 2: refused
-  const int dev = w4_current_device();
-  int st = state[slot][dev].load(std::memory_order_acquire);
-  if (st == 0) {
-    st = hipFuncSetAttribute(kernel, hipFuncAttributeMaxDynamicSharedMemorySize, bytes) == hipSuccess ? 1 : 2;
-    if (st == 2) (void)hipGetLastError();
-    state[slot][dev].store(st, std::memory_order_release);
-  }
-  return st == 1 ? SR_OK : SR_ERR_UNSUPPORTED;
-}
-
-inline bool w4_al16(const void* ptr) { return (((uintptr_t)ptr) & 15) == 0; }
 
 }  // namespace
 
@@ -1049,7 +1018,7 @@ extern "C" int sr_conv_prefers_wino4(int B, int H, int W, int Cin, int Cout, int
   const int co_blocks = (Cout + 63) / 64;
   const double co_util = (double)Cout / (double)(co_blocks * 64);
   const long items = regions * B * co_blocks;
-  const long cus = w4_num_cus();
+  const long cus = sr_device_cus();
   if (co_util < 0.99 || Cin < 16) return 0;
   if (items >= 2 * cus) {
     const long rounds = (items + cus - 1) / cus;
@@ -1106,13 +1075,14 @@ static int w4_run(const float* in, int64_t in_batch_stride, int in_pix_stride, c
   if (B == 0) return SR_OK;
   if (!in || !packed_u || !out) return SR_ERR_INVALID_ARGUMENT;
   // 16-byte channel quads everywhere (the vector staging / epilogue is the only instantiation)
-  if (Cin % 4 != 0 || Cout % 4 != 0 || !w4_al16(in) || !w4_al16(out) || in_pix_stride % 4 != 0 || in_batch_stride % 4 != 0 ||
-      out_pix_stride % 4 != 0 || out_batch_stride % 4 != 0 || (bias && !w4_al16(bias)) ||
-      (residual && (!w4_al16(residual) || res_pix_stride % 4 != 0 || res_batch_stride % 4 != 0)))
+  if (Cin % 4 != 0 || Cout % 4 != 0 || !sr_rows_aligned(in, in_batch_stride, in_pix_stride, 15, 4) ||
+      !sr_rows_aligned(out, out_batch_stride, out_pix_stride, 15, 4) || (bias && !sr_ptr_aligned(bias, 15)) ||
+      (residual && !sr_rows_aligned(residual, res_batch_stride, res_pix_stride, 15, 4)))
     return SR_ERR_UNSUPPORTED;
   const int64_t lim = (int64_t)1 << 31;   // per-image byte offsets are 32-bit (buffer addressing)
-  if (((int64_t)(H * (int64_t)W - 1) * in_pix_stride + Cin) * 4 >= lim || ((int64_t)(H * (int64_t)W - 1) * out_pix_stride + Cout) * 4 >= lim ||
-      (residual && ((int64_t)(H * (int64_t)W - 1) * res_pix_stride + Cout) * 4 >= lim))
+  const int64_t HW = (int64_t)H * W;
+  if (!sr_view_fits32(HW, in_pix_stride, Cin, 4) || !sr_view_fits32(HW, out_pix_stride, Cout, 4) ||
+      (residual && !sr_view_fits32(HW, res_pix_stride, Cout, 4)))
     return SR_ERR_UNSUPPORTED;
   SrWino4Params p;
   p.in = in; p.in_sb = in_batch_stride; p.in_sp = in_pix_stride;
@@ -1131,12 +1101,12 @@ static int w4_run(const float* in, int64_t in_batch_stride, int in_pix_stride, c
   p.total = (int)total;
   p.slope = leaky_slope;
   if (variant == 3) {   // wave-specialised: 4 MFMA waves + 4 transform waves, one workgroup per CU
-    int blocks = w4_num_cus();
+    int blocks = sr_device_cus();
     if (blocks > p.total) blocks = p.total;
     const bool generic_act = !((leaky_slope >= 0.0f && leaky_slope <= 1.0f) || (leaky_slope < 0.0f && leaky_slope > -1.5f));
     auto kernel = generic_act ? (residual ? sr_wino4ws_kernel<true, true> : sr_wino4ws_kernel<true, false>)
                               : (residual ? sr_wino4ws_kernel<false, true> : sr_wino4ws_kernel<false, false>);
-    if (int rc = w4_allow_lds((const void*)kernel, (generic_act ? 2 : 0) + (residual ? 1 : 0), W4_WS_LDS_BYTES)) return rc;
+    if (int rc = w4_allow_lds((const void*)kernel, W4_WS_LDS_BYTES)) return rc;
 #ifdef SR_W4_TRACE
     w4_trace_begin(p, (hipStream_t)stream_);
 #endif
@@ -1147,18 +1117,18 @@ static int w4_run(const float* in, int64_t in_batch_stride, int in_pix_stride, c
     return sr_hip_rc(hipGetLastError());
   }
   if (variant != 2) {   // two independent 4-wave workgroups per CU
-    int blocks = 2 * w4_num_cus();
+    int blocks = 2 * sr_device_cus();
     if (blocks > p.total) blocks = p.total;
-    if (int rc = w4_allow_lds((const void*)sr_wino4_kernel, 4, W4_LDS_BYTES)) return rc;
+    if (int rc = w4_allow_lds((const void*)sr_wino4_kernel, W4_LDS_BYTES)) return rc;
     hipLaunchKernelGGL(sr_wino4_kernel, dim3(blocks), dim3(256), W4_LDS_BYTES, (hipStream_t)stream_, p);
     return sr_hip_rc(hipGetLastError());
   }
-  int blocks = w4_num_cus();
+  int blocks = sr_device_cus();
   if (blocks > (p.total + 1) / 2) blocks = (p.total + 1) / 2;
 #ifdef SR_W4_TRACE
   w4_trace_begin(p, (hipStream_t)stream_);
 #endif
-  if (int rc = w4_allow_lds((const void*)sr_wino4pp_kernel, 5, 2 * W4_LDS_BYTES)) return rc;
+  if (int rc = w4_allow_lds((const void*)sr_wino4pp_kernel, 2 * W4_LDS_BYTES)) return rc;
   hipLaunchKernelGGL(sr_wino4pp_kernel, dim3(blocks), dim3(512), 2 * W4_LDS_BYTES, (hipStream_t)stream_, p);
 #ifdef SR_W4_TRACE
   w4_trace_end(blocks, (hipStream_t)stream_);

@@ -16,8 +16,6 @@
 
 #include "sr_wino.h"
 
-typedef unsigned ws_u4 __attribute__((ext_vector_type(4)));
-
 // WS_USCALE: the packed weight pieces hold U * 2^k (exact), the epilogue multiplies by 2^-k where it adds the bias.  fp16
 // pieces of |x| < 2^-2 have a denormal low piece (absolute resolution 2^-25 instead of relative 2^-24): typical weights
 // (|U| ~ 0.05) would lose 3-4 bits; scaled by 2^8 every |U| >= 2^-10 keeps full precision and |U| < 255 stays in range.
@@ -32,7 +30,7 @@ template <> struct WsFmt<1> {
     const wn_f2 v0 = {__uint_as_float(hi << 16), __uint_as_float(hi & 0xffff0000u)};
     lo = __builtin_bit_cast(unsigned, __builtin_convertvector(v - v0, e2));
   }
-  static __device__ __forceinline__ f32x16 mfma(ws_u4 a, ws_u4 b, f32x16 c) {
+  static __device__ __forceinline__ f32x16 mfma(sr_u4 a, sr_u4 b, f32x16 c) {
     return __builtin_amdgcn_mfma_f32_32x32x16_bf16(__builtin_bit_cast(e8, a), __builtin_bit_cast(e8, b), c, 0, 0, 0);
   }
 };
@@ -46,7 +44,7 @@ template <> struct WsFmt<2> {   // fp16 pieces: 22-24 bits inside 2^-14 <= |x| <
     hi = __builtin_bit_cast(unsigned, h);
     lo = __builtin_bit_cast(unsigned, __builtin_convertvector(v - __builtin_convertvector(h, wn_f2), e2));
   }
-  static __device__ __forceinline__ f32x16 mfma(ws_u4 a, ws_u4 b, f32x16 c) {
+  static __device__ __forceinline__ f32x16 mfma(sr_u4 a, sr_u4 b, f32x16 c) {
     return __builtin_amdgcn_mfma_f32_32x32x16_f16(__builtin_bit_cast(e8, a), __builtin_bit_cast(e8, b), c, 0, 0, 0);
   }
 };
@@ -135,12 +133,12 @@ __global__ __launch_bounds__(256, NT == 1 ? SR_WS_NT1_WGS : 2) void sr_wino_spli
   // ---- staging: global -> registers -> LDS (the vector path of sr_wino_kernel) ----
   int offs[WN_STAGE_PER_THREAD];
   unsigned s_org = 0;
-  __amdgpu_buffer_rsrc_t rs_in = wn_rsrc(p.in, 0);
+  __amdgpu_buffer_rsrc_t rs_in = sr_rsrc(p.in, 0);
   const int64_t in_img_bytes = ((int64_t)(p.H * p.W - 1) * p.in_sp + p.Cin) * ES;
   const int c_quad = 4 * (tid & 3);
   auto aim = [&](const Region& r) {
     const char* in_b = reinterpret_cast<const char*>(p.in) + (int64_t)r.b * p.in_sb * ES;
-    rs_in = wn_rsrc(in_b, in_img_bytes);
+    rs_in = sr_rsrc(in_b, in_img_bytes);
     const bool interior = (r.oy0 >= 1) & (r.oy0 + 2 * WN_TR + 1 <= p.H) & (r.ox0 >= 1) & (r.ox0 + 2 * WN_TC + 1 <= p.W);
     if (interior) {
       s_org = (unsigned)(((r.oy0 - 1) * p.W + (r.ox0 - 1)) * p.in_sp) * ES;
@@ -150,7 +148,7 @@ __global__ __launch_bounds__(256, NT == 1 ? SR_WS_NT1_WGS : 2) void sr_wino_spli
         const int px = e >> 2;
         const int py = px / WN_PW, pxx = px - py * WN_PW;
         offs[it] = (it < WN_STAGE_PER_THREAD - 1 || e < WN_STAGE_ELEMS) ? (int)(((py * p.W + pxx) * p.in_sp + c_quad) * ES)
-                                                                        : (int)WN_OOB;
+                                                                        : (int)SR_OOB;
       }
     } else {
       s_org = 0;
@@ -161,7 +159,7 @@ __global__ __launch_bounds__(256, NT == 1 ? SR_WS_NT1_WGS : 2) void sr_wino_spli
         const int py = px / WN_PW, pxx = px - py * WN_PW;
         const int iy = r.oy0 - 1 + py, ix = r.ox0 - 1 + pxx;
         const bool ok = (e < WN_STAGE_ELEMS) & (iy >= 0) & (iy < p.H) & (ix >= 0) & (ix < p.W);
-        offs[it] = ok ? (int)(((iy * p.W + ix) * p.in_sp + c_quad) * ES) : (int)WN_OOB;
+        offs[it] = ok ? (int)(((iy * p.W + ix) * p.in_sp + c_quad) * ES) : (int)SR_OOB;
       }
     }
   };
@@ -174,7 +172,7 @@ __global__ __launch_bounds__(256, NT == 1 ? SR_WS_NT1_WGS : 2) void sr_wino_spli
     } else {
 #pragma unroll
       for (int it = 0; it < WN_STAGE_PER_THREAD; ++it)
-        stg[it] = wn_buf_load(rs_in, (unsigned)offs[it], so);
+        stg[it] = wn_io_load<0>(rs_in, (unsigned)offs[it], so);
     }
   };
   static_assert(WN_STAGE_PER_THREAD == 3 && 2 * 256 < WN_STAGE_ELEMS, "only the third slot of a thread can be a spare");
@@ -187,11 +185,11 @@ __global__ __launch_bounds__(256, NT == 1 ? SR_WS_NT1_WGS : 2) void sr_wino_spli
   };
   // weight fragments: step s = (uc = s >> 1, piece = s & 1) -> record (xi = 4 wave + uc, 2 ch + piece)
   unsigned wu_lane = 0;
-  auto load_b = [&](int ch, int s, ws_u4 (&dst)[NT]) {
+  auto load_b = [&](int ch, int s, sr_u4 (&dst)[NT]) {
     const int xi = 4 * wave + (s >> 1), g = s & 1;
     const char* wrec = reinterpret_cast<const char*>(reinterpret_cast<const float4*>(p.wu) + (int64_t)(xi * p.G + 2 * ch + g) * rec);
 #pragma unroll
-    for (int n = 0; n < NT; ++n) dst[n] = *reinterpret_cast<const ws_u4*>(wrec + (wu_lane + 512u * n));
+    for (int n = 0; n < NT; ++n) dst[n] = *reinterpret_cast<const sr_u4*>(wrec + (wu_lane + 512u * n));
   };
   auto rv_fma = [&](const float4 da, const float4 db) {
     const wn_f2 sg = {t_sign, t_sign};
@@ -211,7 +209,7 @@ __global__ __launch_bounds__(256, NT == 1 ? SR_WS_NT1_WGS : 2) void sr_wino_spli
   float4 stg[WN_STAGE_PER_THREAD];
   const bool chain = !(chunks & 1);
   bool staged = false;
-  ws_u4 b_f[4][NT];
+  sr_u4 b_f[4][NT];
   float4 av[2][4];
   float4 wq[4];
   Region reg = decode(blockIdx.x < (unsigned)p.total ? (int)blockIdx.x : 0), nxt = reg;
@@ -260,7 +258,7 @@ __global__ __launch_bounds__(256, NT == 1 ? SR_WS_NT1_WGS : 2) void sr_wino_spli
         S::split(av[0][uc].z, av[0][uc].w, h1, l1);
         S::split(av[1][uc].x, av[1][uc].y, h2, l2);
         S::split(av[1][uc].z, av[1][uc].w, h3, l3);
-        const ws_u4 ah = {h0, h1, h2, h3}, al = {l0, l1, l2, l3};
+        const sr_u4 ah = {h0, h1, h2, h3}, al = {l0, l1, l2, l3};
         const int sh = (2 * uc) & 3, sl = (2 * uc + 1) & 3;
 #pragma unroll
         for (int n = 0; n < NT; ++n) {
@@ -305,11 +303,11 @@ __global__ __launch_bounds__(256, NT == 1 ? SR_WS_NT1_WGS : 2) void sr_wino_spli
       const int cg = tid % CG;
       const int tile0 = tid / CG;
       const int tr0 = tile0 >> 3, tc0 = tile0 & 7;
-      const __amdgpu_buffer_rsrc_t rs_out = wn_rsrc(outp, ((int64_t)(p.H * p.W - 1) * out_sp + p.Cout) * ES);
+      const __amdgpu_buffer_rsrc_t rs_out = sr_rsrc(outp, ((int64_t)(p.H * p.W - 1) * out_sp + p.Cout) * ES);
       const __amdgpu_buffer_rsrc_t rs_res =
-          wn_rsrc(resp ? (const void*)resp : (const void*)p.wu,
+          sr_rsrc(resp ? (const void*)resp : (const void*)p.wu,
                   resp ? ((int64_t)(p.H * p.W - 1) * p.res_sp + p.Cout) * ES : (int64_t)0);
-      const __amdgpu_buffer_rsrc_t rs_bias = wn_rsrc(bias_p ? (const void*)bias_p : (const void*)p.wu,
+      const __amdgpu_buffer_rsrc_t rs_bias = sr_rsrc(bias_p ? (const void*)bias_p : (const void*)p.wu,
                                                      bias_p ? (int64_t)p.Cout * 4 : (int64_t)0);
       const bool okc = co0 + 4 * cg < p.Cout;
       const bool full = (oy0 + 2 * WN_TR <= p.H) & (ox0 + 2 * WN_TC <= p.W) & (co0 + CO <= p.Cout);
@@ -341,16 +339,16 @@ __global__ __launch_bounds__(256, NT == 1 ? SR_WS_NT1_WGS : 2) void sr_wino_spli
               okm |= (unsigned)(okc & (oy < p.H) & (ox < p.W)) << (4 * it + q);
             }
         }
-        auto lane_off = [&](unsigned v, int it, int q) { return (FULL || ((okm >> (4 * it + q)) & 1u)) ? v : WN_OOB; };
+        auto lane_off = [&](unsigned v, int it, int q) { return (FULL || ((okm >> (4 * it + q)) & 1u)) ? v : SR_OOB; };
         float4 rv[UNITS][4];
         if (RES) {
 #pragma unroll
           for (int it = 0; it < UNITS; ++it)
 #pragma unroll
             for (int q = 0; q < 4; ++q)
-              rv[it][q] = wn_buf_load(rs_res, lane_off(v_res, it, q), s_res0 + d_pix(it, q) * rsp4);
+              rv[it][q] = wn_io_load<0>(rs_res, lane_off(v_res, it, q), s_res0 + d_pix(it, q) * rsp4);
         }
-        const float4 bv = wn_buf_load(rs_bias, (FULL || okc) ? 16u * cg : WN_OOB, (unsigned)co0 * 4u);
+        const float4 bv = wn_io_load<0>(rs_bias, (FULL || okc) ? 16u * cg : SR_OOB, (unsigned)co0 * 4u);
 #pragma unroll
         for (int n = 0; n < NT; ++n) {
 #pragma unroll
@@ -398,7 +396,7 @@ __global__ __launch_bounds__(256, NT == 1 ? SR_WS_NT1_WGS : 2) void sr_wino_spli
           if (!fast_leaky) sr_activate_group(o16, slope);
 #pragma unroll
           for (int q = 0; q < 4; ++q)
-            wn_buf_store(make_float4(o16[4 * q], o16[4 * q + 1], o16[4 * q + 2], o16[4 * q + 3]), rs_out,
+            sr_buf_store(sr_f4{o16[4 * q], o16[4 * q + 1], o16[4 * q + 2], o16[4 * q + 3]}, rs_out,
                          lane_off(v_out, it, q), s_out0 + d_pix(it, q) * osp4);
         }
       };
@@ -431,9 +429,7 @@ int sr_wino_split_launch(const SrWinoParams& p, int nt, int blocks, int mode, hi
   }
 #define WS_LAUNCH(NTV, FMTV)                                                                                      \
   {                                                                                                               \
-    hipError_t e = hipFuncSetAttribute((const void*)sr_wino_split_kernel<NTV, FMTV>,                              \
-                                       hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);                     \
-    if (e != hipSuccess) return sr_hip_rc(e);                                                                     \
+    if (hipError_t e = sr_allow_lds((const void*)sr_wino_split_kernel<NTV, FMTV>, lds)) return sr_hip_rc(e);      \
     hipLaunchKernelGGL((sr_wino_split_kernel<NTV, FMTV>), dim3(blocks), dim3(256), lds, stream, p);               \
   }
   if (mode == 1 && nt == 2) WS_LAUNCH(2, 1)

@@ -133,6 +133,35 @@ def test_mlp_volume_other_view_counts(K):
     assert mismatch_fraction(mask, mask_o) == 0.0
 
 
+def _sweep_vs_oracle(K):
+    case = dict(B=1, K=K, C=16, D=8, h=12, w=16, seed=80 + K)
+    inp = synthetic.cost_volume_inputs(1, K, 16, 12, 16, seed=case["seed"])
+    mgr = _manager(case)
+    vol, lowest, planes, mask = _run(mgr, inp)
+    planes_np = planes[:, :, 0, 0].cpu().numpy()
+    cv_o, low_o, mask_o = _oracle(mgr, inp, planes_np)
+    assert_close(vol, cv_o, tol=2e-5, what=f"K={K} vs oracle")
+    assert mismatch_fraction(mask, mask_o) == 0.0
+
+
+def test_lds_grant_grows_with_the_view_count():
+    """K = 1, then K = 7, in one FRESH process on one device: both take sr_mlp_volume_kernel<true, true>, whose dynamic LDS
+    grows with K (the depth-variant part of W1).  The library remembers the largest size it was granted per (kernel,
+    device) and must ask again for the larger one: a grant that does not grow makes the second launch return an error code
+    (HipLibraryError in the child, a non-zero exit here).  A child process, because in this one earlier tests have already
+    been granted the K = 7 size and the order would grow nothing."""
+    import os
+    import subprocess
+    import sys
+    here = os.path.dirname(os.path.abspath(__file__))
+    code = ("import sys; sys.path[:0] = [%r, %r, %r]\n"
+            "import test_gpu_mlp_volume as t\n"
+            "t._sweep_vs_oracle(1); t._sweep_vs_oracle(7); print('grant grew')\n"
+            % (os.path.dirname(here), here, os.path.join(os.path.dirname(here), "oracle")))
+    r = subprocess.run([sys.executable, "-c", code], capture_output=True, text=True, timeout=120)
+    assert r.returncode == 0 and "grant grew" in r.stdout, r.stdout[-2000:] + r.stderr[-2000:]
+
+
 def test_cfg3_batch8_full_size_all_frames():
     """BASELINE.json configs[2] at the BENCHMARKED batch: 8 frames, 7 views, 64 planes, 120x160, 202-channel MLP; all 8
     frames against the oracle on a plane subset (the oracle's cost is per (pixel, plane)), masks of all frames exactly."""
