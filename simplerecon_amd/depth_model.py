@@ -253,11 +253,17 @@ class DepthModel(nn.Module):
         return hit[1], hit[2]
 
     def graphed(self, cur_image, src_image, cur_feats, src_cam_T_cur_cam, cur_cam_T_src_cam, src_K, cur_invK,
-                return_mask=False):
+                return_mask=False, check_weights=False):
         """HIP-graph version of `forward_tensors` for fixed shapes: returns a `graph.GraphedCallable` taking
         (cur_image, src_image, cur_feats, src_cam_T_cur_cam, cur_cam_T_src_cam, src_K, cur_invK).  cur_feats=None:
         the image-prior encoder runs inside the graph (the whole model, ~430 launches, in one submission per keyframe
-        batch); cur_feats = a pyramid list: it is an input and only matching encoder -> hot_path are captured."""
+        batch); cur_feats = a pyramid list: it is an input and only matching encoder -> hot_path are captured.
+        The graph reads the weights as they were PACKED at capture (and biases and the sweep's MLP weights live): after a
+        weight update, capture again.  check_weights=True enforces that: (version, address) of every parameter and buffer
+        of the model is recorded at capture, and a replay after a change (optimizer step, load_state_dict, .to()) raises
+        graph.StaleGraphError.  Off by default: comparing the model's 1124 tensors costs about 0.2 ms of host time per replay
+        ("Memory outside the logical operands").  Either way the graph keeps the packed weights it reads alive,
+        and refuses to replay after ops.forget_packed()."""
         from .graph import GraphedCallable
 
         def step(cur_image, src_image, cur_feats, src_T_cur, cur_T_src, src_K, cur_invK):
@@ -268,7 +274,8 @@ class DepthModel(nn.Module):
             return self.hot_path(list(cur_feats), mc, ms, src_T_cur, cur_T_src, src_K, cur_invK,
                                  return_mask=return_mask)
         return GraphedCallable(step, cur_image, src_image, None if cur_feats is None else list(cur_feats),
-                               src_cam_T_cur_cam, cur_cam_T_src_cam, src_K, cur_invK)
+                               src_cam_T_cur_cam, cur_cam_T_src_cam, src_K, cur_invK, modules=[self],
+                               check_weights=check_weights)
 
     def _sweep_reserve(self, cur_feats, matching_cur_feats):
         """CUs the plane sweep leaves to the image-prior encoder (0: none).  While the encoder is still running on its side

@@ -8,8 +8,39 @@ step, no per-launch host work, back-to-back kernels on the device.
 Everything the HIP path launches goes to torch's current stream (`_lib.stream_ptr`), so capture needs no special
 casing; the library itself never allocates or synchronises.  Packed-weight caches and workspaces are filled by the
 warm-up runs before the capture, inside it they are only read.
+
+The graph bakes in the ADDRESSES of those packed weights, which live outside its memory pool: the GraphedCallable keeps a
+reference to every payload cached at capture time, so that an eager call which re-packs after a weight update (and drops the
+cache's own reference) cannot leave a replay reading recycled memory.  A replay still computes with the weights as they were
+packed at capture -- mixed with whatever the graph reads live (biases, the sweep's MLP weights) -- so with `check_weights`
+a replay after any change of a parameter or buffer raises instead.
 """
 import torch
+
+from . import ops
+
+
+class StaleGraphError(RuntimeError):
+    """A captured graph was replayed after the weights it was captured with changed."""
+
+
+def _weight_state(modules):
+    """[(the module's own dict, name, qualified name, version, address)] of every parameter and buffer of `modules` (roots),
+    each once.  The qualified name (`ClassOfTheRoot.path.to.module.weight`) is for the error message only."""
+    state, seen = [], set()
+    for root in modules:
+        for path, m in root.named_modules():
+            for d in (m._parameters, m._buffers):
+                for name, t in d.items():
+                    if t is None or id(t) in seen:
+                        continue
+                    seen.add(id(t))
+                    try:
+                        version = t._version
+                    except RuntimeError:   # a tensor made in inference mode carries no version counter: address only
+                        version = None
+                    state.append((d, name, ".".join(filter(None, (type(root).__name__, path, name))), version, t.data_ptr()))
+    return state
 
 
 def _flatten(x, out):
@@ -40,9 +71,19 @@ class GraphedCallable:
     """`g = GraphedCallable(fn, *example_inputs)`; `out = g(*inputs)` copies `inputs` into the captured input
     buffers (device-to-device, skipped for tensors that already ARE those buffers: see `static_inputs`) and replays the
     graph.  The returned tensors are the graph's static output buffers: they are overwritten by the next call.
-    Shapes, dtypes, devices and non-tensor arguments are frozen at capture time."""
+    Shapes, dtypes, devices and non-tensor arguments are frozen at capture time.
 
-    def __init__(self, fn, *example_inputs, warmup=3):
+    `modules`: the nn.Modules `fn` runs (roots).  The payloads the packed-weight cache holds for them after the capture are
+    kept alive with the graph.  With modules=None that is every payload of the process-wide cache, whichever module it
+    belongs to: harmless for the result, but the packed weights of unrelated models then stay allocated for as long as this
+    graph lives -- name the modules where that matters (DepthModel.graphed does).  check_weights=True (needs `modules`): (version, address) of
+    every parameter and buffer is recorded at capture and compared before each replay; a difference raises StaleGraphError
+    -- capture again.  check_weights=False replays whatever was packed at capture."""
+
+    def __init__(self, fn, *example_inputs, warmup=3, modules=None, check_weights=False):
+        if check_weights and modules is None:
+            raise ValueError("check_weights needs the `modules` whose weights the graph reads")
+        modules = None if modules is None else list(modules)
         flat = _flatten(example_inputs, [])
         if not flat or not all(t.is_cuda for t in flat):
             raise ValueError("GraphedCallable needs device tensors as inputs")
@@ -61,11 +102,27 @@ class GraphedCallable:
             self.graph = torch.cuda.CUDAGraph()
             with torch.cuda.graph(self.graph):
                 self.static_outputs = fn(*self.static_inputs)
+        self._pinned = ops.packed_payloads(modules)
+        self._forget_epoch = ops._FORGET_EPOCH
+        self._weights = _weight_state(modules) if check_weights else None
+
+    def _check_weights(self):
+        for d, name, qualified, version, address in self._weights:
+            t = d.get(name)
+            if t is None or t.data_ptr() != address or (version is not None and t._version != version):
+                raise StaleGraphError(f"parameter or buffer `{qualified}` changed since this graph was captured: a replay would "
+                                      "compute with the weights packed at capture.  Capture again (DepthModel.graphed / "
+                                      "GraphedCallable), or pass check_weights=False to replay the captured weights")
 
     def __call__(self, *inputs):
         flat = _flatten(inputs, [])
         if len(flat) != len(self._static_flat):
             raise ValueError(f"expected {len(self._static_flat)} input tensors, got {len(flat)}")
+        if self._forget_epoch != ops._FORGET_EPOCH:
+            raise StaleGraphError("ops.forget_packed() was called since this graph was captured: it still reads the payloads "
+                                  "packed before.  Capture again")
+        if self._weights is not None:
+            self._check_weights()
         with torch.inference_mode():
             for dst, src, (shape, dtype) in zip(self._static_flat, flat, self._shapes):
                 if src is dst:

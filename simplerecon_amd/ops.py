@@ -24,6 +24,11 @@ PROFILE = None
 # (event recorded behind the pack, its stream handle, device), or None once the event has completed.
 _PACKED = weakref.WeakKeyDictionary()
 _NO_ENTRIES = {}   # (read only: what a module without entries looks up)
+# The state key of an entry is (version counter, address) of every tensor the payload is derived from (_state_key).  It sees
+# what bumps a version counter: in-place updates under no_grad (optimizer steps), load_state_dict, nn.init.*, writes through
+# detach(), and a parameter replaced by a new tensor (module.to(...), assignment).  It does NOT see writes through `.data`
+# (`w.data.mul_()`, `w.data.copy_()` leave `w._version` unchanged): whoever writes that way calls forget_packed(module).
+_FORGET_EPOCH = 0   # bumped by forget_packed: a captured HIP graph (graph.GraphedCallable) refuses to replay across it
 
 
 def _cached(mod, tag, key, build, *args):
@@ -45,6 +50,26 @@ def _cached(mod, tag, key, build, *args):
         fence = (ev, st.cuda_stream, device)
     _PACKED.setdefault(mod, {})[tag] = [key, payload, fence]
     return payload
+
+
+def forget_packed(module):
+    """Drops every cached payload (packed weights, folded biases) of `module` and its submodules, so that the next call packs
+    again from the current parameters.  For code that writes parameters through `.data`, which the cache key cannot see; a
+    HIP graph captured before the call bakes the old payloads in and refuses to replay afterwards (capture again)."""
+    global _FORGET_EPOCH
+    for m in module.modules():
+        _PACKED.pop(m, None)
+    _FORGET_EPOCH += 1
+
+
+def packed_payloads(modules=None):
+    """The payloads currently cached for `modules` (roots; their submodules included) -- for every module when None.  A
+    captured HIP graph holds on to them: it bakes their addresses in, while a later eager call that re-packs drops them."""
+    if modules is None:
+        entries = list(_PACKED.values())
+    else:
+        entries = [_PACKED[m] for root in modules for m in root.modules() if m in _PACKED]
+    return [e[1] for entry in entries for e in entry.values()]
 
 
 def _await_pack(e):

@@ -134,3 +134,76 @@ def test_graph_replay_survives_larger_eager_calls():
     torch.cuda.synchronize()
     for k in ref:
         assert torch.equal(out[k], ref[k]), k
+
+
+# ---- replay and packed weights ------------------------------------------------------------------------------------------
+# The graph bakes in the addresses of the weights packed during warm-up.  They live outside its memory pool; the packed-weight
+# cache drops them when a later eager call re-packs.
+
+def _reseeded_state(model, only_conv_weights):
+    """A state dict with other values: every floating tensor, or only the convolution weights of CVEncoder and the decoder
+    (tensors of which a graph reads the PACKED form only; biases, the sweep's MLP weights and the matching encoder's 1x1
+    convolution are read live on every replay)."""
+    sd = {}
+    for i, (k, v) in enumerate(model.state_dict().items()):
+        change = v.is_floating_point() and (not only_conv_weights or (
+            v.dim() == 4 and k.startswith(("cost_volume_net.", "depth_decoder."))))
+        sd[k] = v * (1.0 + 0.05 * torch.cos(torch.arange(v.numel(), device=v.device, dtype=v.dtype) + i).view(v.shape)) \
+            if change and v.dim() > 0 else v.clone()
+    return sd
+
+
+def test_replay_after_a_weight_update_raises():
+    from simplerecon_amd import ops
+    from simplerecon_amd.graph import StaleGraphError
+    K, D, h, w = 2, 8, 24, 32
+    model = _model(h, w, K, D)
+    a = _inputs(1, K, h, w, 8)
+    graphed = model.graphed(*a, return_mask=True, check_weights=True)
+    graphed(*a)
+    model.load_state_dict(_reseeded_state(model, False))
+    with pytest.raises(StaleGraphError, match="[Cc]apture again"):
+        graphed(*a)
+    graphed = model.graphed(*a, return_mask=True, check_weights=True)      # capturing again is the cure
+    with torch.inference_mode():
+        mc, ms = model.compute_matching_feats(a[0], a[1], False)
+        ref = {k: v.clone() for k, v in model.hot_path(list(a[2]), mc, ms, *a[3:], return_mask=True).items()}
+    out = graphed(*a)
+    torch.cuda.synchronize()
+    for k in ref:
+        assert torch.equal(out[k], ref[k]), k
+    with torch.no_grad():
+        model.depth_decoder.parameters().__next__().mul_(1.5)     # an optimizer-style in-place step
+    with pytest.raises(StaleGraphError):
+        graphed(*a)
+    graphed = model.graphed(*a, return_mask=True)                 # (the check is opt-in; this one is always made)
+    ops.forget_packed(model)                                      # what a `.data` writer calls
+    with pytest.raises(StaleGraphError, match="forget_packed"):
+        graphed(*a)
+
+
+def test_unchecked_replay_reads_the_weights_it_pinned():
+    """check_weights=False: the replay computes with the payloads packed at capture.  New convolution weights + one eager call
+    make the cache re-pack and drop its references to the old payloads; junk allocations then recycle whatever was freed, as
+    NaN.  The graph holds its own references, so the replay still equals the old-weight result bit for bit.  (Only
+    convolution weights of CVEncoder and the decoder change: what a replay reads live follows the module at once.)"""
+    K, D, h, w = 2, 8, 24, 32
+    model = _model(h, w, K, D)
+    a = _inputs(1, K, h, w, 9)
+
+    def eager():
+        with torch.inference_mode():
+            mc, ms = model.compute_matching_feats(a[0], a[1], False)
+            return {k: (v.clone() if v is not None else None)
+                    for k, v in model.hot_path(list(a[2]), mc, ms, *a[3:], return_mask=True).items()}
+    old = eager()
+    graphed = model.graphed(*a, return_mask=True, check_weights=False)
+    model.load_state_dict(_reseeded_state(model, True))
+    new = eager()                                                 # re-packs every convolution, frees the old payloads
+    assert not torch.equal(new["depth_pred_s0_b1hw"], old["depth_pred_s0_b1hw"])
+    junk = [torch.full((n,), float("nan"), device=DEV) for n in (1 << 12, 1 << 14, 1 << 16, 1 << 18, 1 << 20, 1 << 22) for _ in range(4)]
+    out = graphed(*a)
+    torch.cuda.synchronize()
+    for k in old:
+        assert old[k] is None and out[k] is None or torch.equal(out[k], old[k]), k
+    del junk

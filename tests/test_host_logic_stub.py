@@ -370,6 +370,111 @@ def test_packed_weights_are_cached_until_a_parameter_changes(stub, monkeypatch, 
         assert packs() == 4
 
 
+def test_what_the_cache_key_can_and_cannot_see():
+    """The eager cache key is (version, address): in-place updates under no_grad, load_state_dict, nn.init.* and writes through
+    detach() bump the version counter; writes through `.data` do not -- the documented blind spot ops.forget_packed is for."""
+    from torch import nn
+
+    from simplerecon_amd import ops
+    conv = nn.Conv2d(4, 4, 3, padding=1)
+    key = lambda: ops._state_key(conv, None)
+    for write in (lambda: conv.weight.data.mul_(2.0), lambda: conv.weight.data.copy_(torch.ones_like(conv.weight)),
+                  lambda: conv.bias.data.add_(1.0)):
+        before = key()
+        write()
+        assert key() == before
+    bumps = [lambda: conv.weight.mul_(2.0), lambda: conv.load_state_dict({k: v.clone() for k, v in conv.state_dict().items()}),
+             lambda: nn.init.ones_(conv.weight), lambda: conv.weight.detach().mul_(0.5), lambda: conv.bias.detach().zero_()]
+    for write in bumps:
+        before = key()
+        with torch.no_grad():
+            write()
+        assert key() != before
+
+
+@pytest.mark.parametrize("name", _CACHED)
+def test_forget_packed_makes_a_data_write_visible(stub, monkeypatch, name):
+    """A `.data` write leaves the cached payload in place (the key cannot see it); after ops.forget_packed -- on the module or
+    on any module above it -- the next call packs again, from the weights as they are then."""
+    from torch import nn
+
+    from simplerecon_amd import ops
+    monkeypatch.setattr(ops, "_PACKED", weakref.WeakKeyDictionary())
+    mod, bn, use = _cached_entry_points()[name]
+    builds, cached = [], ops._cached
+
+    def counting(m, tag, key, build, *args):
+        def build_(*a):
+            payload = build(*a)
+            builds.append((tag, payload))
+            return payload
+        return cached(m, tag, key, build_, *args)
+    monkeypatch.setattr(ops, "_cached", counting)
+
+    def packs():
+        with torch.no_grad():
+            use(mod, bn)
+            use(mod, bn)
+        return len(builds)
+    assert packs() == 1
+    mod.weight.data.mul_(3.0)
+    assert packs() == 1                                  # stale: nothing told the cache
+    epoch = ops._FORGET_EPOCH
+    ops.forget_packed(mod)
+    assert ops._FORGET_EPOCH == epoch + 1 and mod not in ops._PACKED
+    assert packs() == 2
+    if bn is not None:
+        bn.running_var.data.mul_(4.0)
+        assert packs() == 2
+        ops.forget_packed(nn.Sequential(nn.Sequential(mod), bn))   # from a root two levels up
+        assert packs() == 3
+    if name == "dw":    # (a payload built by torch rather than the stubbed library: its values are those of the new weights)
+        w9c = builds[-1][1][0]
+        scale = ops.bn_affine(bn)[0]
+        assert torch.allclose(w9c, (mod.weight.detach() * scale.view(-1, 1, 1, 1)).reshape(16, 9).t())
+    assert all(p is not None for p in ops.packed_payloads([mod])) and len(ops.packed_payloads([mod])) == 1
+    assert ops.packed_payloads([nn.Conv2d(1, 1, 1)]) == []
+
+
+def test_graph_weight_check_sees_what_changes_a_weight():
+    """graph._weight_state / GraphedCallable._check_weights (the replay check of DepthModel.graphed) on the CPU: silent while
+    nothing changed; raises after an in-place update, load_state_dict, a replaced parameter, a moved buffer."""
+    from torch import nn
+
+    from simplerecon_amd import graph
+
+    def checker(model):
+        g = graph.GraphedCallable.__new__(graph.GraphedCallable)
+        g._weights = graph._weight_state([model])
+        return g._check_weights
+    model = nn.Sequential(nn.Conv2d(3, 4, 3), nn.BatchNorm2d(4), nn.Sequential(nn.Linear(4, 2)))
+    assert len(graph._weight_state([model])) == 2 + 5 + 2 and len(graph._weight_state([model, model[2]])) == 9
+    check = checker(model)
+    check()
+    check()
+    with torch.no_grad():
+        model[0].weight.mul_(2.0)
+    with pytest.raises(graph.StaleGraphError, match="capture") as err:
+        check()
+    assert "`Sequential.0.weight`" in str(err.value)     # which module's weight, not only its local name
+    check = checker(model)
+    model[2][0].bias.detach().zero_()
+    with pytest.raises(graph.StaleGraphError, match=r"`Sequential\.2\.0\.bias`"):
+        check()
+    for change in (lambda: model.load_state_dict({k: v.clone() for k, v in model.state_dict().items()}),
+                   lambda: setattr(model[2][0], "weight", nn.Parameter(model[2][0].weight.detach().clone())),
+                   lambda: model[1].running_mean.add_(1.0),
+                   lambda: model.double()):
+        check = checker(model)
+        check()
+        change()
+        with pytest.raises(graph.StaleGraphError):
+            check()
+    check = checker(model)
+    model[0].weight.data.mul_(2.0)       # the blind spot: ops.forget_packed() is what invalidates a graph then
+    check()
+
+
 @pytest.mark.parametrize("name", _CACHED)
 def test_packed_weights_are_fenced_for_other_streams(stub, monkeypatch, name):
     """A payload packed on stream A is waited for once by a use on stream B while the pack has not completed, never by a use
