@@ -41,11 +41,13 @@ extern "C" {
  * launch path, no setenv() by any host.  The table is PROCESS-WIDE: a value set while another thread is launching applies to
  * that thread's next launch, and a HIP graph captured under a mode keeps the kernels of that mode.  Integer options take the
  * integer; the split modes take 0 = off (fp32 MFMA: the product path), 1 = bf16 pieces, 2 = f16 pieces (-1 = the unknown
- * string an environment variable held: the entry points that honour the mode return SR_ERR_INVALID_ARGUMENT). */
+ * string an environment variable held: the entry points that honour the mode return SR_ERR_INVALID_ARGUMENT); SR_MLP_TILE
+ * takes the codes listed at sr_mlp_volume_tile_shape (environment: auto, flat, 2x32, 4x16, 8x8; -1 as above). */
 enum {
   SR_OPT_MLP_SPLIT = 0, SR_OPT_WINO_SPLIT, SR_OPT_WINO_XCD, SR_OPT_WINO_NT, SR_OPT_WINO_KSPLIT, SR_OPT_CONV_WINO,
   SR_OPT_CONV_TILE, SR_OPT_CONV_KSPLIT, SR_OPT_PW_NT, SR_OPT_PW_KS, SR_OPT_PT_CFG, SR_OPT_PT_KS, SR_OPT_DOT_LDS,
   SR_OPT_DOT_LDS_G, SR_OPT_DOT_LDS_CULL, SR_OPT_DOT_LDS_CAP, SR_OPT_UPSAMPLE_QUAD, SR_OPT_POOL_STREAM,
+  SR_OPT_MLP_TILE,
   SR_OPT_COUNT
 };
 int sr_option_count(void);
@@ -233,6 +235,15 @@ int sr_mlp_volume_sweep(const float* cur, const float* invK_cur, const float* pl
                         int C, int h, int w, int D, float* out_cv, int64_t cv_sb, int64_t cv_sd,
                         int64_t cv_sp, float* out_lowest, uint8_t* out_mask, void* workspace,
                         size_t workspace_bytes, void* stream);
+
+/* Which 64 pixels of the h x w map one wave of the sweep works on, under the current SR_MLP_TILE: a th x tw tile (th * tw =
+ * 64; tiles row-major, lane l of tile (ty, tx) at y = ty*th + l / tw, x = tx*tw + l % tw, lanes past the image idle), or
+ * th = 1, tw = 64 for 64 consecutive pixels of the flattened map.  A source view none of whose taps, over the wave's
+ * pixels, lies inside the source image is skipped at that plane, and compact tiles are skipped more often than strips;
+ * results do not depend on the shape, bit for bit.  Option SR_MLP_TILE (read per call): 0 "auto" (default) = the squarest of
+ * 8x8, 4x16, 2x32 whose tile count is at most 1 % above ceil(h*w / 64), else the strip; 1 "flat" = the strip; 2 "2x32",
+ * 3 "4x16", 4 "8x8" = that shape whatever it pads; anything else: SR_ERR_INVALID_ARGUMENT here and from the sweep. */
+int sr_mlp_volume_tile_shape(int h, int w, int* th, int* tw);
 
 /* = sr_volume_prepare + sr_mlp_pack_weights + sr_mlp_volume_sweep, with a CU reserve for this call:
  * reserve_cus = 0 runs the sweep on the whole chip; n > 0 makes its persistent grid leave n CUs to other streams, with the

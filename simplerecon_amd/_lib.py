@@ -64,6 +64,7 @@ SIGNATURES = {
     "sr_mlp_pack_weights": (_i, [_p, _p, _p, _p, _p, _p, _i, _i, _i, _i, _i, _i, _p, _sz, _p]),
     "sr_mlp_volume_sweep": (_i, [_p, _p, _p, _i64, _i64, _i64, _i64, _f, _i, _i, _i, _i, _i, _i,
                                  _p, _i64, _i64, _i64, _p, _p, _p, _sz, _p]),
+    "sr_mlp_volume_tile_shape": (_i, [_i, _i, C.POINTER(C.c_int), C.POINTER(C.c_int)]),
     "sr_mlp_volume_fwd": (_i, [_p, _p, _p, _p, _p, _p, _p, _i64, _i64, _i64, _i64, _p, _p, _p, _p, _p, _p, _i,
                                _f, _i, _i, _i, _i, _i, _i, _p, _i64, _i64, _i64, _p, _p, _i, _p, _sz, _p]),
     "sr_conv_packed_weight_floats": (_sz, [_i, _i, _i]),
@@ -255,7 +256,10 @@ def check(rc, what):
 # the library never reads the environment again and hosts change a switch through these calls.  Process-wide.
 SPLIT_MODES = {"": 0, "0": 0, "off": 0, "fp32": 0, "bf16": 1, "f16": 2, "fp16": 2}
 _SPLIT_NAMES = {0: "", 1: "bf16", 2: "f16"}
-SPLIT_OPTION_NAMES = ("SR_MLP_SPLIT", "SR_WINO_SPLIT")   # the options that take a mode NAME; every other option is an integer
+SPLIT_OPTION_NAMES = ("SR_MLP_SPLIT", "SR_WINO_SPLIT")   # the options that take a split-mode NAME
+TILE_MODES = {"auto": 0, "flat": 1, "2x32": 2, "4x16": 3, "8x8": 4}   # SR_MLP_TILE (sr_mlp_volume_tile_shape)
+_NAMED_VALUES = {"SR_MLP_SPLIT": SPLIT_MODES, "SR_WINO_SPLIT": SPLIT_MODES, "SR_MLP_TILE": TILE_MODES}   # every other option is
+                                                                                                       # an integer
 # The split modes are read by the weight-packing AND by the launching entry points: a change between the two would feed one
 # format's packed weights to the other format's kernel.  Changing them and [pack + launch] hold this lock.
 import threading  # noqa: E402
@@ -290,12 +294,12 @@ def refresh_options():
 
 
 def set_option(name, value):
-    """Sets option `name` (an int; the split modes also take 'bf16' / 'f16' / '' / an unknown string = -1: refused by the
-    entry points).  Returns the previous value."""
+    """Sets option `name` (an int; the split modes also take 'bf16' / 'f16' / '', SR_MLP_TILE 'auto' / 'flat' / '2x32' /
+    '4x16' / '8x8'; an unknown string = -1: refused by the entry points).  Returns the previous value."""
     if isinstance(value, str):
-        if name not in SPLIT_OPTION_NAMES:
+        if name not in _NAMED_VALUES:
             raise ValueError(f"option {name} takes an integer, got {value!r}")   # (ADVICE r05: a typo used to become -1 silently)
-        value = SPLIT_MODES.get(value, -1)
+        value = _NAMED_VALUES[name].get(value, -1)
     prev = C.c_int(0)
     # a split mode's library value, mirror and listeners change together under the guard: a pack + launch in between would
     # see the library in one mode and key its cache on the other

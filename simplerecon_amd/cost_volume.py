@@ -328,6 +328,31 @@ def mlp_input_channels(matching_dim_size, num_source_views):
     return c * (1 + k) + (1 + k) + 3 * (1 + k) + k + k + k + 3 * k
 
 
+def mlp_tile_shape(h, w):
+    """(th, tw) of the 64 pixels one wave of the metadata-MLP sweep owns on an h x w map under the current SR_MLP_TILE, as
+    the library answers it (sr_mlp_volume_tile_shape, include/simplerecon_hip.h); (1, 64) is the flattened strip."""
+    import ctypes
+    th, tw = ctypes.c_int(0), ctypes.c_int(0)
+    _lib.check(_lib.lib().sr_mlp_volume_tile_shape(int(h), int(w), ctypes.byref(th), ctypes.byref(tw)),
+               "sr_mlp_volume_tile_shape")
+    return th.value, tw.value
+
+
+def mlp_wave_pixels(h, w, shape=None):
+    """The sweep's lane -> pixel map (csrc/sr_mlp_volume.hip, sr_mlp_lane_pixel) as an int array [waves, 64] of flattened
+    pixel indices y * w + x, -1 for the lanes that lie past the image.  `shape` = (th, tw), default mlp_tile_shape(h, w)."""
+    import numpy as np
+    th, tw = shape or mlp_tile_shape(h, w)
+    if th == 1:
+        pix = np.arange(-(-h * w // 64) * 64).reshape(-1, 64)
+        return np.where(pix < h * w, pix, -1)
+    lane = np.arange(64)
+    ty, tx = np.divmod(np.arange(-(-h // th) * -(-w // tw)), -(-w // tw))
+    y = ty[:, None] * th + lane[None] // tw
+    x = tx[:, None] * tw + lane[None] % tw
+    return np.where((y < h) & (x < w), y * w + x, -1)
+
+
 class FeatureVolumeManager(CostVolumeManager):
     """Metadata-MLP feature volume (reference cost_volume.py:383-746).
 

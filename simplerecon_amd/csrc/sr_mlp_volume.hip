@@ -3,7 +3,8 @@
 // Replaces FeatureVolumeManager.build_cost_volume / FastFeatureVolumeManager of the reference
 // (modules/cost_volume.py:451-736, 967-1164): per depth plane ~40 ATen launches, a 202-channel
 // concat tensor and two [B*N,128] hidden tensors (or, in the "fast" variant, 7.9 GB of them at
-// batch 8).  Here a wavefront owns 64 points (64 pixels of one depth plane):
+// batch 8).  Here a wavefront owns 64 points (64 pixels of one depth plane: an 8x8, 4x16 or 2x32 tile, or 64 consecutive
+// pixels of the flattened map -- sr_mlp_lane_pixel):
 //   * VALU part: homography, 4-tap bilinear gather of the channels-last source features,
 //     dot / mask / depth / rays / ray angle -- each lane builds the MLP input vector of ITS point
 //     in registers, never in memory;
@@ -114,13 +115,37 @@ struct SrMlpParams {
   SrPlanes planes;
   SrVolumeOut out;
   int B, K, h, w, D;
-  int tiles;              // ceil(h*w / 64)
+  int tiles;              // 64-pixel tiles per image: tiles_x * ceil(h / th), or ceil(h*w / 64) for the flattened strip
+  int tiles_x;            // th x tw tiles per tile row, ceil(w / tw); 0: the flattened strip (sr_mlp_lane_pixel)
+  int th_log2, tw_log2;   // th * tw = 64
   int chunk, chunks;      // planes per work unit, ceil(D / chunk)
   int vec_store;          // channels-last volume (plane stride 1): a lane keeps the costs of its unit's planes and
                           // stores them as 16-byte pieces at the end of the unit (instead of one 4-byte store per plane
                           // into 64 different 256-byte rows: r02 PMC counted 6.7x the volume's bytes in WRITE_SIZE)
   float inv_w, inv_h, slope;
 };
+
+// Which pixel a lane of the wave that owns `tile` works on.  Whether a view is dead for a wave (below) is a spatial
+// property -- the live region is the source image shifted along the epipolar line -- so a compact th x tw tile (th * tw =
+// 64, tiles row-major over (ty, tx)) is dead far more often than 64 consecutive pixels of the flattened map, a 64 x 1 strip
+// wrapped over two rows.  Every cost is computed per pixel by its own lane, so the map changes no bit of any result.
+// Lanes past the image (a ragged right / bottom tile; the tail of the flattened map) are inactive: their x and y are
+// clamped separately for their loads, they do not vote in the dead-view ballot and they store nothing.
+__device__ __forceinline__ bool sr_mlp_lane_pixel(const SrMlpParams& p, int tile, int lane, int& y, int& x) {
+  if (p.tiles_x) {
+    const int ty = tile / p.tiles_x, tx = tile - ty * p.tiles_x;   // wave-uniform
+    const int ly = (ty << p.th_log2) + (lane >> p.tw_log2);
+    const int lx = (tx << p.tw_log2) + (lane & ((1 << p.tw_log2) - 1));
+    y = min(ly, p.h - 1);
+    x = min(lx, p.w - 1);
+    return ly < p.h && lx < p.w;
+  }
+  const int N = p.h * p.w, pix = tile * 64 + lane;
+  const int pc = min(pix, N - 1);
+  y = pc / p.w;
+  x = pc - y * p.w;
+  return pix < N;
+}
 
 __device__ __forceinline__ void sr_swap_halves(float fa, float fb, float& bP, float& bQ) {
   // vdst lanes 32-63 <-> src lanes 0-31: bP = [fa(0..31) | fb(0..31)], bQ = [fa(32..63) | fb(32..63)]
@@ -229,10 +254,11 @@ __global__ __launch_bounds__(256, 1) void sr_mlp_volume_kernel(SrMlpParams p) {
     const int tile = (int)(tb % p.tiles);
     const int b = (int)(tb / p.tiles);
     const int j0 = chunk * p.chunk, j1 = min(p.D, j0 + p.chunk);
-    const int pix = tile * 64 + lane;
-    const bool active = pix < N;
-    const int pc = active ? pix : N - 1;
-    const int y = pc / p.w, x = pc - y * p.w;
+    int y, x;
+    const bool in_image = sr_mlp_lane_pixel(p, tile, lane, y, x);
+    const int pc = y * p.w + x;             // this lane's pixel, clamped into the image: what it loads from
+    const int pix = in_image ? pc : -1;     // ... and what it stores to; one register carries both pixel and activity
+    const bool active = pix >= 0;
     const float* plane_ptr = p.planes.ptr + b * p.planes.sb + y * p.planes.sy + x * p.planes.sx;
     const float* geom_b = p.geom + (size_t)b * p.K * SR_GEOM_STRIDE;
     const float* src_b = p.src_nhwc + (size_t)b * p.K * N * C;
@@ -296,8 +322,8 @@ __global__ __launch_bounds__(256, 1) void sr_mlp_volume_kernel(SrMlpParams p) {
     // warped channels and dot * mask are exact zeros (zeros padding), so its feature k-steps 0..7 would add W . 0 and its
     // tap loads, interpolation and dot product would only produce those zeros.  Wave-uniform (a ballot), keyed on the
     // tap validity tests and not on z' > 0: a point behind the camera has mask 0, but its mirrored taps can be in the
-    // image and the reference does not mask the warped features by depth.  The clamped lanes of a ragged last tile
-    // (pix >= N) do not vote; what they compute is never stored.
+    // image and the reference does not mask the warped features by depth.  The clamped lanes of a ragged tile
+    // (sr_mlp_lane_pixel) do not vote; what they compute is never stored.
     // (the view's camera centre is read here, in front of its tap loads: vector loads return in order, and read behind
     // them it made the first k-step wait for all 16 taps)
     float gt0, gt1, gt2;
@@ -781,10 +807,11 @@ __global__ __launch_bounds__(256, 1) void sr_mlp_volume_split_kernel(SrMlpParams
     const int tile = (int)(tb % p.tiles);
     const int b = (int)(tb / p.tiles);
     const int j0 = chunk * p.chunk, j1 = min(p.D, j0 + p.chunk);
-    const int pix = tile * 64 + lane;
-    const bool active = pix < N;
-    const int pc = active ? pix : N - 1;
-    const int y = pc / p.w, x = pc - y * p.w;
+    int y, x;
+    const bool in_image = sr_mlp_lane_pixel(p, tile, lane, y, x);
+    const int pc = y * p.w + x;             // this lane's pixel, clamped into the image: what it loads from
+    const int pix = in_image ? pc : -1;     // ... and what it stores to; one register carries both pixel and activity
+    const bool active = pix >= 0;
     const float* plane_ptr = p.planes.ptr + b * p.planes.sb + y * p.planes.sy + x * p.planes.sx;
     const float* geom_b = p.geom + (size_t)b * p.K * SR_GEOM_STRIDE;
     const float* src_b = p.src_nhwc + (size_t)b * p.K * N * C;
@@ -1016,6 +1043,26 @@ extern "C" size_t sr_mlp_volume_workspace_bytes(int B, int K, int C, int h, int 
   return sr_volume_workspace_bytes(B, K, C, h, w) + sr_align_up(sr_mlp_packed_floats(K) * sizeof(float), 256) + 256;
 }
 
+// The 64 pixels of a wave (sr_mlp_lane_pixel).  Option SR_OPT_MLP_TILE: 0 = auto, 1 = the flattened strip, 2..4 = 2x32, 4x16,
+// 8x8 whatever they pad, -1 = unknown (refused).  auto takes the squarest shape whose tile count is at most 1 % above
+// ceil(h*w / 64), else the strip: a ragged tile is a whole wave's work for a part of its pixels, and in a scene without
+// dead views there is nothing to win it back with (the project's bar for such scenes is 1 %).  The strip is th = 1, tw = 64.
+extern "C" int sr_mlp_volume_tile_shape(int h, int w, int* th, int* tw) {
+  if (h <= 0 || w <= 0 || !th || !tw) return SR_ERR_INVALID_ARGUMENT;
+  const int mode = sr_opt(SR_OPT_MLP_TILE);
+  if (mode < 0 || mode > 4) return SR_ERR_INVALID_ARGUMENT;
+  *th = 1; *tw = 64;
+  if (mode >= 2) { *th = 1 << (mode - 1); *tw = 64 >> (mode - 1); }
+  if (mode == 0) {
+    const int64_t flat = ((int64_t)h * w + 63) / 64;
+    for (int t = 8; t >= 2; t >>= 1) {
+      const int64_t tiles = (int64_t)((h + t - 1) / t) * ((w + 64 / t - 1) / (64 / t));
+      if (100 * tiles <= 101 * flat) { *th = t; *tw = 64 / t; break; }
+    }
+  }
+  return SR_OK;
+}
+
 static float* sr_ws_packed(void* workspace, int B, int K, int C, int h, int w) {
   return (float*)sr_align_up((size_t)workspace + sr_volume_workspace_bytes(B, K, C, h, w), 256);
 }
@@ -1046,7 +1093,11 @@ static int sr_mlp_volume_sweep_reserved(const float* cur, const float* invK_cur,
   p.planes = {planes, ps_b, ps_d, ps_y, ps_x};
   p.out = {out_cv, cv_sb, cv_sd, cv_sp, out_lowest, out_mask};
   p.B = B; p.K = K; p.h = h; p.w = w; p.D = D;
-  p.tiles = (N + 63) / 64;
+  int th, tw;
+  if (sr_mlp_volume_tile_shape(h, w, &th, &tw)) return SR_ERR_INVALID_ARGUMENT;   // unknown SR_MLP_TILE
+  p.th_log2 = __builtin_ctz(th); p.tw_log2 = __builtin_ctz(tw);
+  p.tiles_x = th == 1 ? 0 : (w + tw - 1) / tw;
+  p.tiles = th == 1 ? (N + 63) / 64 : p.tiles_x * ((h + th - 1) / th);
   p.inv_w = (float)(1.0 / (double)w);
   p.inv_h = (float)(1.0 / (double)h);
   p.slope = leaky_slope;

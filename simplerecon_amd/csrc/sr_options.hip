@@ -18,13 +18,13 @@
 
 namespace {
 
-struct OptDef { const char* name; int dflt; int kind; };   // kind 0: integer, 1: split-precision mode string
+struct OptDef { const char* name; int dflt; int kind; };   // kind 0: integer, 1: split-precision mode string, 2: MLP tile shape
 const OptDef kDefs[SR_OPT_COUNT] = {
     {"SR_MLP_SPLIT", 0, 1},       {"SR_WINO_SPLIT", 0, 1},     {"SR_WINO_XCD", 1, 0},        {"SR_WINO_NT", 0, 0},
     {"SR_WINO_KSPLIT", 0, 0},     {"SR_CONV_WINO", 1, 0},      {"SR_CONV_TILE", 0, 0},       {"SR_CONV_KSPLIT", 1, 0},
     {"SR_PW_NT", 0, 0},           {"SR_PW_KS", 0, 0},          {"SR_PT_CFG", -1, 0},         {"SR_PT_KS", 0, 0},
     {"SR_DOT_LDS", 1, 0},         {"SR_DOT_LDS_G", 0, 0},      {"SR_DOT_LDS_CULL", 1, 0},    {"SR_DOT_LDS_CAP", 634, 0},
-    {"SR_UPSAMPLE_QUAD", 1, 0},   {"SR_POOL_STREAM", 1, 0},
+    {"SR_UPSAMPLE_QUAD", 1, 0},   {"SR_POOL_STREAM", 1, 0},    {"SR_MLP_TILE", 0, 2},
 };
 std::atomic<int> g_val[SR_OPT_COUNT];
 std::once_flag g_once;
@@ -35,6 +35,13 @@ int parse(const OptDef& d, const char* e) {
     if (!strcmp(e, "bf16")) return 1;
     if (!strcmp(e, "f16") || !strcmp(e, "fp16")) return 2;
     return -1;   // unknown: the entry points that honour the mode refuse to run (SR_ERR_INVALID_ARGUMENT)
+  }
+  if (d.kind == 2) {   // sr_mlp_volume_tile_shape
+    static const char* const names[] = {"auto", "flat", "2x32", "4x16", "8x8"};
+    if (!e || !*e) return d.dflt;
+    for (int i = 0; i < 5; ++i)
+      if (!strcmp(e, names[i])) return i;
+    return -1;   // unknown: the sweep refuses to run
   }
   return (e && *e) ? atoi(e) : d.dflt;
 }
