@@ -1392,6 +1392,50 @@ int sr_conv16_nhwc_fwd(const void* in, int64_t in_batch_stride, int in_pix_strid
                        int64_t out_batch_stride, int out_pix_stride, int B, int H, int W, int Cin, int Cout, int k, int stride,
                        float leaky_slope, int io_dtype, int out_dtype, void* stream);
 
+/* ---- 16-bit-operand weight gradient and elementwise backward of the same path (csrc/sr_conv16_wgrad.hip; opt-in:
+ * SR_AUTOCAST_MFMA16_WGRAD) --------------------------------------------------------------------------------------------
+ * sr_conv16_wgrad_nhwc: d_weight[co][ci][ky][kx] = sum over b, y, x of grad_out[b,y,x,co] * in[b, s y + ky - p, s x + kx - p, ci]
+ * for 3x3 at stride 1 or 2 with zero padding 1 and 1x1 at stride 1 (the forms sr_conv16_supported accepts), on
+ * v_mfma_f32_32x32x16_{f16,bf16} with M = co, N = ci, K = output pixels.  `in` [B,H,W,Cin] and `grad_out` [B,Ho,Wo,Cout] are
+ * fp16 (io_dtype = 1) or bf16 (io_dtype = 2) channels-last views (strides in ELEMENTS; arbitrary batch / pixel strides, so
+ * channel slices of wider buffers work); d_weight is fp32, dense [Cout][Cin][k][k], WRITTEN, not accumulated.
+ * Numeric contract: products of two 16-bit values are exact and are summed in fp32 on the matrix pipe, in an order that is a
+ * function of the shape only -- a workgroup adds its (image, output row, 32-pixel segment) items in index order into one
+ * partial slab, a second kernel adds the slabs of a (co, ci) block in index order; no atomics, two runs give the same bits.
+ * The output is NOT rounded.  Subnormal operands: as for sr_conv16_nhwc_fwd.  Padding taps, pixels past Wo and channels past
+ * Cin / Cout inside a 64-channel block enter the sum as exact zeros on BOTH sides: no result depends on memory outside the
+ * operands or on the previous contents of `d_weight` / `workspace`.
+ * Workspace: sr_conv16_wgrad_workspace_bytes = blocks x slabs x k k x 64 x 64 x 4 bytes with
+ *     blocks = ceil(Cout / 64) ceil(Cin / 64),   slabs (per block) = min(ceil(512 / blocks), B Ho ceil(Wo / 32)),
+ * a multiple of 16; 0 for a shape sr_conv16_wgrad_supported refuses.
+ * Requirements (SR_ERR_UNSUPPORTED otherwise, nothing is launched): Cin % 8 == 0 and Cout % 8 == 0, every batch and pixel
+ * stride a multiple of 8 elements, pixel strides >= the channel count, 16-byte aligned `in` and `grad_out`, a 16-byte aligned
+ * `workspace` of at least sr_conv16_wgrad_workspace_bytes bytes.  SR_ERR_INVALID_ARGUMENT: a NULL in / grad_out / d_weight /
+ * workspace, io_dtype outside {1, 2}, k outside {1, 3}, stride outside {1, 2} or 2 with k = 1, B <= 0.  Index arithmetic across
+ * images is 64-bit.
+ * sr_conv16_wgrad_supported: the shape test alone (sr_conv16_supported's forms and channel rules; 0 for B <= 0); pure host
+ * function, like sr_conv16_wgrad_workspace_bytes.  sr_conv16_wgrad_prefers: the routing rule of SR_AUTOCAST_MFMA16_WGRAD=1 --
+ * 1 for the shape classes where this path measured faster than the fp32 one around its casts (profiles/r08_conv16_wgrad.txt:
+ * every conv-stack class measured, 0.25 - 0.86 x the time), 0 for every class nobody measured.
+ * sr_act_bwd_bias16_nhwc: sr_act_bwd_bias_nhwc without casts, one pass over a dense [pixels, C] gradient, C % 8 == 0, 16-byte
+ * accesses: `grad` is fp32 (grad_dtype = 0: heads that feed fp32 losses) or the layer's 16-bit type (grad_dtype = io_dtype),
+ * `out_saved` 16-bit or NULL (no activation), grad_pre (16-bit; may be NULL without an activation: then only d_bias is
+ * computed) = round_to(io_dtype, grad * LeakyReLU'(out_saved)), the product in fp32 with ONE rounding to nearest even;
+ * d_bias (fp32, or NULL) = the sum over pixels of the UNROUNDED fp32 products, per-block partial sums in `workspace`
+ * (sr_act_bwd_bias16_workspace_bytes; SR_ERR_WORKSPACE_TOO_SMALL) added in block order: deterministic.  SR_ERR_UNSUPPORTED:
+ * C % 8 != 0 or a pointer that is not 16-byte aligned; SR_ERR_INVALID_ARGUMENT: io_dtype outside {1, 2}, grad_dtype outside
+ * {0, io_dtype}, a NULL grad, out_saved without grad_pre, a negative slope. */
+int sr_conv16_wgrad_supported(int B, int H, int W, int Cin, int Cout, int k, int stride);
+int sr_conv16_wgrad_prefers(int B, int H, int W, int Cin, int Cout, int k, int stride);
+size_t sr_conv16_wgrad_workspace_bytes(int B, int H, int W, int Cin, int Cout, int k, int stride);
+int sr_conv16_wgrad_nhwc(const void* in, int64_t in_batch_stride, int in_pix_stride, const void* grad_out,
+                         int64_t g_batch_stride, int g_pix_stride, float* d_weight, int B, int H, int W, int Cin, int Cout,
+                         int k, int stride, int io_dtype, void* workspace, size_t workspace_bytes, void* stream);
+size_t sr_act_bwd_bias16_workspace_bytes(int64_t pixels, int C);
+int sr_act_bwd_bias16_nhwc(const void* grad, int grad_dtype, const void* out_saved, void* grad_pre, float* d_bias,
+                           int64_t pixels, int C, float leaky_slope, int io_dtype, void* workspace, size_t workspace_bytes,
+                           void* stream);
+
 #ifdef __cplusplus
 }
 #endif

@@ -1,8 +1,10 @@
-"""The whole training step (scripts/train_step_micro.py's model, inputs and loss) in four configurations, side by side in ONE process,
+"""The whole training step (scripts/train_step_micro.py's model, inputs and loss) in five configurations, side by side in ONE process,
 alternating: fp32; bf16 autocast with the 16-bit switches off (fp32 kernels); HALF_IO + STORE_HALF; experimental.autocast_mfma16
-(HALF_IO + STORE_HALF + the 16-bit MFMA convolutions where SR_TRAIN_MFMA16_MODE, default 1 = the measured rule, selects them).
+(HALF_IO + STORE_HALF + the 16-bit MFMA convolutions where SR_TRAIN_MFMA16_MODE, default 1 = the measured rule, selects them); the
+same with the 16-bit weight gradient and cast-free elementwise backward (wgrad = SR_TRAIN_MFMA16_WGRAD, default 2 = every supported
+layer whose forward ran on the 16-bit kernel).
 Time per step (host clock around steps that end in a device synchronise) and peak memory per configuration.
-    [SR_TRAIN_AUTOCAST=bf16|fp16] [SR_TRAIN_MFMA16_MODE=1|2] python scripts/train_step_mfma16.py [batch] [views] [rounds] [steps]"""
+    [SR_TRAIN_AUTOCAST=bf16|fp16] [SR_TRAIN_MFMA16_MODE=1|2] [SR_TRAIN_MFMA16_WGRAD=1|2] python scripts/train_step_mfma16.py [batch] [views] [rounds] [steps]"""
 import contextlib
 import os
 import sys
@@ -19,6 +21,7 @@ STEPS = int(sys.argv[4]) if len(sys.argv) > 4 else 3
 AMP = os.environ.get("SR_TRAIN_AUTOCAST", "bf16")
 AMP_DT = {"fp16": torch.float16, "bf16": torch.bfloat16}[AMP]
 MODE = int(os.environ.get("SR_TRAIN_MFMA16_MODE", "1"))
+WGRAD = int(os.environ.get("SR_TRAIN_MFMA16_WGRAD", "2"))
 D, H, W = 64, 480, 640
 dev = torch.device("cuda", 0)
 opts = dm.default_options(image_width=W, image_height=H, model_num_views=K + 1, matching_num_depth_bins=D)
@@ -38,18 +41,19 @@ src = {"image_b3hw": torch.from_numpy(rng.standard_normal((B, K, 3, H, W)).astyp
 
 @contextlib.contextmanager
 def switches(half_io, store_half):
-    saved = (autograd_ops.HALF_IO, autograd_ops.STORE_HALF, autograd_ops.MFMA16)
-    autograd_ops.HALF_IO, autograd_ops.STORE_HALF, autograd_ops.MFMA16 = half_io, store_half, 0
+    saved = (autograd_ops.HALF_IO, autograd_ops.STORE_HALF, autograd_ops.MFMA16, autograd_ops.MFMA16_WGRAD)
+    autograd_ops.HALF_IO, autograd_ops.STORE_HALF, autograd_ops.MFMA16, autograd_ops.MFMA16_WGRAD = half_io, store_half, 0, 0
     try:
         yield
     finally:
-        autograd_ops.HALF_IO, autograd_ops.STORE_HALF, autograd_ops.MFMA16 = saved
+        autograd_ops.HALF_IO, autograd_ops.STORE_HALF, autograd_ops.MFMA16, autograd_ops.MFMA16_WGRAD = saved
 
 
 CONFIGS = [("fp32", False, lambda: switches(False, False)),
            (f"{AMP} autocast, switches off", True, lambda: switches(False, False)),
            (f"{AMP} HALF_IO + STORE_HALF", True, lambda: switches(True, True)),
-           (f"{AMP} autocast_mfma16(mode={MODE})", True, lambda: experimental.autocast_mfma16(mode=MODE))]
+           (f"{AMP} autocast_mfma16(mode={MODE})", True, lambda: experimental.autocast_mfma16(mode=MODE)),
+           (f"{AMP} autocast_mfma16(mode={MODE}, wgrad={WGRAD})", True, lambda: experimental.autocast_mfma16(mode=MODE, wgrad=WGRAD))]
 
 
 def step(autocast):
@@ -83,5 +87,5 @@ print(f"# batch {B}, {K} views, 64 planes, 640x480, encoders trained; {ROUNDS} a
       f"spread = (max - min) / median over the rounds")
 for name, _, _ in CONFIGS:
     t = times[name]
-    print(f"  {name:40s} {np.median(t) * 1e3:7.1f} ms/step  spread {(max(t) - min(t)) / np.median(t):.3f}  peak {peak[name]:.2f} GiB  "
+    print(f"  {name:48s} {np.median(t) * 1e3:7.1f} ms/step  spread {(max(t) - min(t)) / np.median(t):.3f}  peak {peak[name]:.2f} GiB  "
           f"loss {losses[name]:.5f}", flush=True)

@@ -45,6 +45,12 @@ SIGNATURES = {
     "sr_conv16_supported": (_i, [_i, _i, _i, _i, _i, _i, _i]),
     "sr_conv16_prefers": (_i, [_i, _i, _i, _i, _i, _i, _i]),
     "sr_conv16_nhwc_fwd": (_i, [_p, _i64, _i, _p, _p, _p, _i64, _i, _p, _i64, _i, _i, _i, _i, _i, _i, _i, _i, _f, _i, _i, _p]),
+    "sr_conv16_wgrad_supported": (_i, [_i, _i, _i, _i, _i, _i, _i]),
+    "sr_conv16_wgrad_prefers": (_i, [_i, _i, _i, _i, _i, _i, _i]),
+    "sr_conv16_wgrad_workspace_bytes": (_sz, [_i, _i, _i, _i, _i, _i, _i]),
+    "sr_conv16_wgrad_nhwc": (_i, [_p, _i64, _i, _p, _i64, _i, _p, _i, _i, _i, _i, _i, _i, _i, _i, _p, _sz, _p]),
+    "sr_act_bwd_bias16_workspace_bytes": (_sz, [_i64, _i]),
+    "sr_act_bwd_bias16_nhwc": (_i, [_p, _i, _p, _p, _p, _i64, _i, _f, _i, _p, _sz, _p]),
     "sr_pw_conv_tiled_workspace_bytes": (_sz, [_i, _i, _i]),
     "sr_pw_conv_tiled_plan": (_i, [_i, _i, _i, _i, _p, _p]),
     "sr_pw_conv_tiled_nhwc_fwd": (_i, [_p, _i, _p, _p, _p, _p, _i, _p, _i, _i, _i, _i, _i, _f, _p, _sz, _p]),

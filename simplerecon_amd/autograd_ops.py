@@ -74,6 +74,15 @@ _IO_CODE = {torch.float16: 1, torch.bfloat16: 2}
 # supported layer (tests, A/B runs).  Read at call time, like HALF_IO.  fp16 (not bf16) needs a loss scaler: the 16-bit data
 # gradient underflows otherwise.
 MFMA16 = int(os.environ.get("SR_AUTOCAST_MFMA16", "0") or 0)
+# 16-bit weight gradient (r08; SR_AUTOCAST_MFMA16_WGRAD, default 0 = off: exactly the backward above).  A layer whose forward ran on
+# the 16-bit MFMA kernel saved a 16-bit input and output; its post-activation gradient is rounded to 16 bits for the data gradient
+# anyway.  With the switch on, the backward of such a layer makes no fp32 copy of them: sr_act_bwd_bias16_nhwc reads the
+# arriving gradient (fp32 or 16-bit) and the saved output and writes the 16-bit post-activation gradient and the fp32 bias
+# gradient, sr_conv16_wgrad_nhwc multiplies the saved input with it on the 16-bit matrix pipe (csrc/sr_conv16_wgrad.hip: exact
+# products, fp32 accumulation, deterministic), and the data gradient consumes the same 16-bit gradient.  A stride-2 data gradient
+# keeps the fp32 zero-stuffing kernel around it.  1 = the layers sr_conv16_wgrad_supported AND sr_conv16_wgrad_prefers accept (the
+# measured rule, profiles/r08_conv16_wgrad.txt), 2 = every supported layer.  Read at call time, like MFMA16.
+MFMA16_WGRAD = int(os.environ.get("SR_AUTOCAST_MFMA16_WGRAD", "0") or 0)
 
 
 def _amp_state_fwd(fwd):
@@ -202,9 +211,10 @@ class _Holder:
         self._modules = {"self": m}
 
 
-def _dense_nhwc(t):
-    """Channels-last, dense (pixel stride = C): what the elementwise backward kernels and the wgrad staging expect."""
-    t = as_nhwc(t, "gradient")
+def _dense_nhwc(t, any_dtype=False):
+    """Channels-last, dense (pixel stride = C): what the elementwise backward kernels and the wgrad staging expect.  fp32, or
+    (any_dtype) any of the I/O dtypes."""
+    t = _nhwc_any(t, "gradient") if any_dtype else as_nhwc(t, "gradient")
     c, h, w = t.shape[1], t.shape[2], t.shape[3]
     if t.stride(1) != 1 or t.stride(3) != c or t.stride(2) != w * c or (t.shape[0] > 1 and t.stride(0) != h * w * c):
         t = t.contiguous(memory_format=torch.channels_last)
@@ -232,6 +242,17 @@ def _mfma16_selects(b, h, w, ci, co, k, stride, pads):
     if not lib.sr_conv16_supported(b, h, w, ci, co, k, stride):
         return False
     return mode >= 2 or bool(lib.sr_conv16_prefers(b, h, w, ci, co, k, stride))
+
+
+def _wgrad16_selects(b, h, w, ci, co, k, stride, pads):
+    """The routing predicate of MFMA16_WGRAD on a layer's shape: never with the switch at 0, never for explicit `pads`."""
+    mode = MFMA16_WGRAD
+    if not mode or pads is not None or b <= 0:
+        return False
+    lib = _lib.lib()
+    if not lib.sr_conv16_wgrad_supported(b, h, w, ci, co, k, stride):
+        return False
+    return mode >= 2 or bool(lib.sr_conv16_wgrad_prefers(b, h, w, ci, co, k, stride))
 
 
 def _conv16_routes(x, weight, stride, residual, pads):
@@ -365,6 +386,12 @@ class _ConvBiasAct(torch.autograd.Function):
     @_amp_state_bwd
     def backward(ctx, g):
         x, weight, out = _unstash(ctx)
+        if MFMA16_WGRAD and ctx.mfma16 and x.dtype in _IO_CODE and g.dtype in (torch.float32, x.dtype) and \
+                (out is None or out.dtype == x.dtype) and \
+                _wgrad16_selects(x.shape[0], x.shape[2], x.shape[3], x.shape[1], weight.shape[0], weight.shape[2], ctx.stride, ctx.pads):
+            g16 = _dense_nhwc(g, any_dtype=True)
+            if _aligned16(x) and _aligned16(g16):
+                return _ConvBiasAct._backward_wgrad16(ctx, g16, x, weight, out)
         # (16-bit I/O: the backward kernels take fp32 copies of what the forward saved in 16 bits)
         dt16 = x.dtype if ctx.mfma16 else None   # the layer's 16-bit dtype when its forward ran on the 16-bit MFMA kernel
         x = x if x.dtype == torch.float32 else x.float()
@@ -442,6 +469,62 @@ class _ConvBiasAct(torch.autograd.Function):
                     d_x = _conv_raw(src, wt, None, 1, pads=(k - 1 - pads[0], k - 1 - pads[1], k - 1 - pads[2], k - 1 - pads[3]))
                 else:          # the stuffed gradient lives on the input's H x W grid: output H x W needs (k-1-pt, k-1-pl, pt, pl)
                     d_x = _conv_raw(src, wt, None, 1, pads=(k - 1 - pads[0], k - 1 - pads[1], pads[0], pads[1]))
+        d_r = gp if (ctx.has_res and need_r) else None
+        xdt, rdt = ctx.in_dtypes
+        if d_x is not None and d_x.dtype != xdt:
+            d_x = d_x.to(xdt)
+        if d_r is not None and d_r.dtype != rdt:
+            d_r = d_r.to(rdt)
+        return d_x, d_w, d_b, d_r, None, None, None
+
+    @staticmethod
+    def _backward_wgrad16(ctx, g, x, weight, out):
+        """The backward of a layer whose forward ran on sr_conv16_nhwc_fwd, on 16-bit operands throughout (MFMA16_WGRAD): `x` and
+        `out` are the saved 16-bit tensors, `g` the dense channels-last gradient in its arriving dtype (fp32 or the layer's)."""
+        lib = _lib.lib()
+        dev, dt16 = x.device, x.dtype
+        io = _IO_CODE[dt16]
+        b, ci, h, w = x.shape
+        co, _, k, _ = weight.shape
+        s = ctx.stride
+        ho, wo = g.shape[2], g.shape[3]
+        need_x, need_w, need_b, need_r = ctx.needs_input_grad[:4]
+        want_b = ctx.has_bias and need_b
+        act = ctx.slope is not None
+        d_x = d_w = d_b = None
+        with _lib.on_device(dev):
+            # one 16-byte pass: LeakyReLU' of the saved 16-bit output, the rounding to the layer's dtype, the bias gradient
+            write_gp = act or g.dtype != dt16
+            gp = torch.empty((b, co, ho, wo), dtype=dt16, device=dev, memory_format=torch.channels_last) if write_gp else g
+            if write_gp or want_b:
+                px = b * ho * wo
+                nws = lib.sr_act_bwd_bias16_workspace_bytes(px, co) if want_b else 0
+                ws = _workspace(dev, "bias_grad", nws) if want_b else None
+                if want_b:
+                    d_b = torch.empty((co,), dtype=torch.float32, device=dev)
+                _lib.call("sr_act_bwd_bias16_nhwc", dev, g, 0 if g.dtype == torch.float32 else io,
+                          _dense_nhwc(out, any_dtype=True) if act else None, gp if write_gp else None, d_b, px, co,
+                          float(ctx.slope) if act else 0.0, io, ws, nws)
+            gsb, gsp = _strides(gp)
+            if need_w:
+                d_w = torch.empty(weight.shape, dtype=torch.float32, device=dev)   # dense [Co][Ci][k][k]
+                nws = lib.sr_conv16_wgrad_workspace_bytes(b, h, w, ci, co, k, s)
+                ws = _workspace(dev, "wgrad", nws)
+                _lib.call("sr_conv16_wgrad_nhwc", dev, x, *_strides(x), gp, gsb, gsp, d_w, b, h, w, ci, co, k, s, io, ws, nws)
+            if need_x:
+                wt = torch.empty((ci, co, k, k), dtype=torch.float32, device=dev)
+                _lib.call("sr_conv_flip_transpose_weights", dev, weight.detach().contiguous(), co, ci, k, wt)
+                if s == 1:
+                    src = gp
+                else:   # stride 2: the fp32 zero-stuffing kernel and the casts around it stay (a 16-bit one is not built)
+                    stuffed = empty_nhwc(b, co, h, w, dev)
+                    gp32 = gp.float()
+                    _lib.call("sr_zero_stuff2x_nhwc", dev, gp32, *_strides(gp32), stuffed, b, ho, wo, h, w, co)
+                    src = stuffed.to(dt16)
+                if _conv16_routes(src, wt, 1, None, None):
+                    d_x = _conv16(src, wt, None, 1, None, None, out_f32=ctx.in_dtypes[0] == torch.float32)
+                else:   # (MFMA16 = 1 and the rule declines the transposed shape, or the switch changed since the forward)
+                    d_x = _conv_raw(src, wt, None, 1)
         d_r = gp if (ctx.has_res and need_r) else None
         xdt, rdt = ctx.in_dtypes
         if d_x is not None and d_x.dtype != xdt:

@@ -25,6 +25,13 @@ int sr_device_cus();
 // runtime is asked once and again only for a larger size; a refusal is not remembered.  Returns the runtime's error.
 hipError_t sr_allow_lds(const void* kernel, size_t bytes);
 
+// Second stages of the deterministic backward sums (sr_conv_bwd.hip), shared with their 16-bit forms (sr_conv16_wgrad.hip):
+// d_weight[co][ci][tap] = the `per` partial [tap][64 co][64 ci] slabs of each (co, ci) block added in index order, and
+// d_bias[c] = the [blocks][C] partial sums added in block order.  Each returns the launch's error code.
+int sr_wgrad_reduce_launch(const float* part, float* d_weight, int Cout, int Cin, int taps, int ci_blocks, int per, int blocks,
+                           hipStream_t stream);
+int sr_bias_partial_reduce_launch(const float* partial, int blocks, int C, float* d_bias, hipStream_t stream);
+
 static inline int sr_hip_rc(hipError_t e) { return e == hipSuccess ? SR_OK : SR_ERR_HIP_BASE + (int)e; }
 
 static inline size_t sr_align_up(size_t v, size_t a) { return (v + a - 1) / a * a; }

@@ -214,6 +214,16 @@ __global__ __launch_bounds__(256) void sr_conv_wgrad_reduce_kernel(const float* 
   }
 }
 
+int sr_wgrad_reduce_launch(const float* part, float* d_weight, int Cout, int Cin, int taps, int ci_blocks, int per, int blocks,
+                           hipStream_t stream) {
+  const long total = (long)blocks * taps * WG_CT * WG_CT;
+  int rblocks = (int)((total + 255) / 256);
+  if (rblocks > 4096) rblocks = 4096;
+  hipLaunchKernelGGL(sr_conv_wgrad_reduce_kernel, dim3(rblocks), dim3(256), 0, stream, part, d_weight, Cout, Cin, taps,
+                     ci_blocks, per, blocks);
+  return sr_hip_rc(hipGetLastError());
+}
+
 static void sr_wgrad_plan(int B, int Ho, int Wo, int Cin, int Cout, int& blocks, int& per, int& items) {
   blocks = ((Cout + WG_CT - 1) / WG_CT) * ((Cin + WG_CT - 1) / WG_CT);
   items = B * Ho * ((Wo + WG_P - 1) / WG_P);
@@ -283,12 +293,7 @@ extern "C" int sr_conv_wgrad_padded_nhwc(const float* in, int64_t in_batch_strid
 #undef SR_WGRAD_LAUNCH
   int rc = sr_hip_rc(hipGetLastError());
   if (rc != SR_OK) return rc;
-  const long total = (long)blocks * ksize * ksize * WG_CT * WG_CT;
-  int rblocks = (int)((total + 255) / 256);
-  if (rblocks > 4096) rblocks = 4096;
-  hipLaunchKernelGGL(sr_conv_wgrad_reduce_kernel, dim3(rblocks), dim3(256), 0, stream, (const float*)workspace, d_weight,
-                     Cout, Cin, ksize * ksize, p.ci_blocks, per, blocks);
-  return sr_hip_rc(hipGetLastError());
+  return sr_wgrad_reduce_launch((const float*)workspace, d_weight, Cout, Cin, ksize * ksize, p.ci_blocks, per, blocks, stream);
 }
 
 extern "C" int sr_conv_wgrad_nhwc(const float* in, int64_t in_batch_stride, int in_pix_stride, const float* grad_out,
@@ -439,6 +444,11 @@ __global__ __launch_bounds__(256) void sr_bias_partial_reduce_kernel(const float
   }
 }
 
+int sr_bias_partial_reduce_launch(const float* partial, int blocks, int C, float* d_bias, hipStream_t stream) {
+  hipLaunchKernelGGL(sr_bias_partial_reduce_kernel, dim3((C + 15) / 16), dim3(256), 0, stream, partial, blocks, C, d_bias);
+  return sr_hip_rc(hipGetLastError());
+}
+
 static int sr_act_bwd_bias_blocks(int64_t pixels, int C) {
   const int CQ = C / 4, LQ = CQ < 256 ? CQ : 256, PB = 256 / LQ;
   int64_t blocks = (pixels + (int64_t)PB * 16 - 1) / ((int64_t)PB * 16);   // >= 16 pixels (two trips) per lane
@@ -471,9 +481,7 @@ extern "C" int sr_act_bwd_bias_nhwc(const float* grad, const float* out_saved, f
   hipLaunchKernelGGL(sr_act_bwd_bias_kernel, dim3(blocks), dim3(256), 0, stream, (const float4*)grad,
                      (const float4*)out_saved, (float4*)grad_pre, d_bias ? (float4*)workspace : (float4*)nullptr, pixels, CQ,
                      LQ, PB, leaky_slope);
-  if (d_bias)
-    hipLaunchKernelGGL(sr_bias_partial_reduce_kernel, dim3((C + 15) / 16), dim3(256), 0, stream, (const float*)workspace,
-                       blocks, C, d_bias);
+  if (d_bias) return sr_bias_partial_reduce_launch((const float*)workspace, blocks, C, d_bias, stream);
   return sr_hip_rc(hipGetLastError());
 }
 

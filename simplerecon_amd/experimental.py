@@ -35,7 +35,7 @@ def split_precision(mode="f16", sweep=True, convs=True):
 
 
 @contextlib.contextmanager
-def autocast_mfma16(mode=1, storage=True):
+def autocast_mfma16(mode=1, storage=True, wgrad=0):
     """16-bit MFMA convolutions for the training steps made inside the block, to be combined with torch.autocast:
 
         with torch.autocast("cuda", dtype=torch.bfloat16), experimental.autocast_mfma16():
@@ -43,18 +43,23 @@ def autocast_mfma16(mode=1, storage=True):
 
     Sets `autograd_ops.HALF_IO` (16-bit activations between the conv-stack layers), `autograd_ops.MFMA16 = mode` (1: the
     layers the measured rule sr_conv16_prefers accepts, 2: every layer sr_conv16_supported accepts) and, with `storage`,
-    `autograd_ops.STORE_HALF` (saved activations in 16 bits); restores the three previous values on exit.  The backward pass
-    must run inside the block too (the data gradient reads the switch).  fp16, unlike bf16, needs a loss scaler.
+    `autograd_ops.STORE_HALF` (saved activations in 16 bits) and `autograd_ops.MFMA16_WGRAD = wgrad` (0: weight / bias
+    gradients and the activation derivative on fp32 copies, as before the switch existed; 1: the 16-bit weight gradient
+    sr_conv16_wgrad_nhwc and the cast-free elementwise pass for the layers the rule sr_conv16_wgrad_prefers accepts, 2: for
+    every layer sr_conv16_wgrad_supported accepts); restores the four previous values on exit.  The backward pass
+    must run inside the block too (it reads the switches).  fp16, unlike bf16, needs a loss scaler.
     The switches are module attributes, hence process-wide: forward / backward passes that OTHER threads run while the block
     is open take the 16-bit paths as well."""
     from . import autograd_ops
     if mode not in (0, 1, 2):
         raise ValueError(f"autocast_mfma16 mode must be 0, 1 or 2, got {mode!r}")
-    saved = (autograd_ops.HALF_IO, autograd_ops.MFMA16, autograd_ops.STORE_HALF)
+    if wgrad not in (0, 1, 2):
+        raise ValueError(f"autocast_mfma16 wgrad must be 0, 1 or 2, got {wgrad!r}")
+    saved = (autograd_ops.HALF_IO, autograd_ops.MFMA16, autograd_ops.STORE_HALF, autograd_ops.MFMA16_WGRAD)
     try:
-        autograd_ops.HALF_IO, autograd_ops.MFMA16 = True, mode
+        autograd_ops.HALF_IO, autograd_ops.MFMA16, autograd_ops.MFMA16_WGRAD = True, mode, wgrad
         if storage:
             autograd_ops.STORE_HALF = True
         yield
     finally:
-        autograd_ops.HALF_IO, autograd_ops.MFMA16, autograd_ops.STORE_HALF = saved
+        autograd_ops.HALF_IO, autograd_ops.MFMA16, autograd_ops.STORE_HALF, autograd_ops.MFMA16_WGRAD = saved
