@@ -1436,6 +1436,50 @@ int sr_act_bwd_bias16_nhwc(const void* grad, int grad_dtype, const void* out_sav
                            int64_t pixels, int C, float leaky_slope, int io_dtype, void* workspace, size_t workspace_bytes,
                            void* stream);
 
+/* ------------------------------------------------------------------ optimiser ----------
+ *
+ * sr_adamw_step: one AdamW step (decoupled weight decay) on every parameter tensor of a model, two launches whatever the
+ * number of tensors.  The rule is torch/optim/adam.py, _single_tensor_adam, non-capturable branch with
+ * decoupled_weight_decay=True, per element in fp32 with the roundings of torch's CPU kernels: IEEE sqrt and division,
+ * every operation rounded separately except the two marked fma, which ATen's lerp and addcmul fuse as well:
+ *     g  = grad / grad_scale                         only when grad_scale is given
+ *     p  = p * float(1 - lr * wd)
+ *     m  = lerp(m, g, w = float(1 - beta1))          w < 0.5 ? fma(w, g - m, m) : fma(w - 1, g - m, g)
+ *     v  = v * float(beta2);  v = fma(float(1 - beta2) * g, g, v)
+ *     p  = p + (-float(lr / bc1) * m) / (sqrt(v) / float(sqrt(bc2)) + float(eps))
+ *     bc1 = 1 - beta1^step, bc2 = 1 - beta2^step     in double, step = the TENSOR's own count after this step
+ * Scalars in float(...) are computed in double and rounded once, as torch rounds a Python float.
+ *
+ * Tables, all on the device, T = num_tensors entries each: p_ptrs / g_ptrs / m_ptrs / v_ptrs 64-bit addresses of fp32
+ * arrays of numel[t] elements (4-byte aligned at least; m and v must not overlap anything else); g_ptrs[t] = 0 says the
+ * tensor has no gradient this step: it is not touched and its step count does not advance.  chunk_start int32 [T + 1] =
+ * prefix sums of ceil(numel[t] / SR_ADAMW_CHUNK), num_chunks = chunk_start[T]; group int32 [T] = index into the group
+ * table; steps fp32 [T] the per-tensor step counts (whole numbers), scalars fp32 [T][2] scratch the call owns.  The
+ * kernels trust the tables.  groups_host: num_groups records of SR_ADAMW_GROUP_DOUBLES doubles (lr, beta1, beta2, eps,
+ * weight_decay) in HOST memory, read before the call returns and handed to the kernels by value.
+ *
+ * Launch 1, one thread per tensor with a gradient: steps[t] += 1, scalars[t] = (float(lr / bc1), float(sqrt(bc2))).
+ * Launch 2, one workgroup per chunk: finds its tensor by bisecting chunk_start, updates SR_ADAMW_CHUNK consecutive
+ * elements (fewer in a tensor's last chunk).  A tensor whose four arrays are all 16-byte aligned moves 16 bytes per lane
+ * and access and the last numel % 4 elements as single floats; any other tensor (a slice of a larger buffer, a gradient
+ * bucket view) moves single floats throughout.  Same values either way.  The step reads p, g, m, v and writes p, m, v:
+ * 28 bytes per element.  Gradients are only read: the unscaled gradient is NOT written back.
+ *
+ * grad_scale / found_inf: device fp32 scalars or NULL (torch.amp.GradScaler's).  With *found_inf != 0 both launches
+ * leave at once: no parameter, moment or step count changes.
+ * SR_ERR_INVALID_ARGUMENT: a NULL table, a misaligned table, num_tensors < 1, num_chunks < 0 (0: only launch 1 runs),
+ * num_groups < 1, a group with a negative or NaN lr / eps / weight_decay or a beta outside [0, 1).  SR_ERR_UNSUPPORTED:
+ * num_tensors above SR_ADAMW_MAX_TENSORS, num_groups above SR_ADAMW_MAX_GROUPS.  No call allocates or synchronises with
+ * the host; results are elementwise and equal bit for bit on every run. */
+#define SR_ADAMW_CHUNK 4096
+#define SR_ADAMW_MAX_GROUPS 16
+#define SR_ADAMW_MAX_TENSORS (1 << 20)
+#define SR_ADAMW_GROUP_DOUBLES 5
+int sr_adamw_step(const void* p_ptrs, const void* g_ptrs, const void* m_ptrs, const void* v_ptrs, const int64_t* numel,
+                  const int32_t* chunk_start, const int32_t* group, float* steps, float* scalars, int num_tensors,
+                  int num_chunks, const double* groups_host, int num_groups, const float* grad_scale,
+                  const float* found_inf, void* stream);
+
 #ifdef __cplusplus
 }
 #endif

@@ -222,6 +222,7 @@ SIGNATURES = {
     "sr_viz_range": (_i, [_p, _p, _i, _i, _i64, _i, _p, _p, _sz, _p]),
     "sr_viz_colormap": (_i, [_p, _p, _i, _i, _i64, _p, _p, _i64, _p, _i64, _f, _f, _f, _f, _f, _p, _p, _p]),
     "sr_viz_unit": (_i, [_p, _i, _i64, _i, _p, _p, _p]),
+    "sr_adamw_step": (_i, [_p, _p, _p, _p, _p, _p, _p, _p, _p, _i, _i, _p, _i, _p, _p, _p]),
 }
 
 

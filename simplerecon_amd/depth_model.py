@@ -44,6 +44,9 @@ class Options:
     min_matching_depth: float = 0.25
     max_matching_depth: float = 5.0
     loss_type: str = "log_l1"
+    lr: float = 1e-4                      # options.py:82-104: AdamW, stepped schedule (configure_optimizers)
+    wd: float = 1e-4
+    lr_steps: tuple = (70000, 80000)
 
 
 def default_options(**kw):
@@ -412,6 +415,16 @@ class DepthModel(nn.Module):
         cur_data["normals_b3hw"] = self.compute_normals(cur_data["depth_b1hw"], cur_data["invK_s0_b44"])
         outputs["normals_pred_b3hw"] = self.compute_normals(outputs["depth_pred_s0_b1hw"], cur_data["invK_s0_b44"])
         return self.compute_losses(cur_data, src_data, outputs)["loss"]
+
+    def configure_optimizers(self):
+        """The reference's optimiser and schedule (depth_model.py:615-633) in its dictionary: AdamW(lr, wd) on the HIP step
+        (optim.AdamW) and a LambdaLR with the factors 1 / 0.1 / 0.01 at lr_steps, stepped once per optimiser step."""
+        from . import optim, training
+        opts = self.run_opts
+        lr_steps = tuple(getattr(opts, "lr_steps", training.DEFAULT_LR_STEPS))
+        optimizer = optim.AdamW(self.parameters(), lr=getattr(opts, "lr", 1e-4), weight_decay=getattr(opts, "wd", 1e-4))
+        lr_scheduler = torch.optim.lr_scheduler.LambdaLR(optimizer, lambda step: training.lr_factor(step, lr_steps))
+        return {"optimizer": optimizer, "lr_scheduler": {"scheduler": lr_scheduler, "interval": "step"}}
 
     def training_images(self, cur_data, outputs, count=4):
         """The pictures the reference's training step logs every log_every_n_steps (depth_model.py:542-562), from

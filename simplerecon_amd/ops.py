@@ -28,6 +28,10 @@ _NO_ENTRIES = {}   # (read only: what a module without entries looks up)
 # what bumps a version counter: in-place updates under no_grad (optimizer steps), load_state_dict, nn.init.*, writes through
 # detach(), and a parameter replaced by a new tensor (module.to(...), assignment).  It does NOT see writes through `.data`
 # (`w.data.mul_()`, `w.data.copy_()` leave `w._version` unchanged): whoever writes that way calls forget_packed(module).
+# Nor does it see a kernel that writes a parameter through its raw address.  optim.AdamW does exactly that, so its step() bumps
+# the counter itself (torch.autograd.graph.increment_version) for every parameter that had a gradient, also when the device
+# skips the step on a found-inf flag the host cannot see: the entry is then packed again from unchanged weights, which costs
+# time and changes nothing.  Any other code that updates weights from a kernel owes the cache the same call.
 _FORGET_EPOCH = 0   # bumped by forget_packed: a captured HIP graph (graph.GraphedCallable) refuses to replay across it
 
 
