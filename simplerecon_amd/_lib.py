@@ -440,5 +440,5 @@ def call(name, device, *args, allow=()):
 def refuse_autograd(*tensors):
     if torch.is_grad_enabled() and any(isinstance(t, torch.Tensor) and t.requires_grad for t in tensors):
         raise NotImplementedError(
-            "simplerecon_amd implements the inference hot path only; run under torch.inference_mode() / "
-            "no_grad() (the backward pass is listed as a 'next' component, SURVEY.md §8f)")
+            "this entry point is an inference launcher and records no autograd graph: run it under torch.inference_mode() / "
+            "no_grad(), or use the differentiable operators of simplerecon_amd.autograd_ops, train_ops and cost_volume")

@@ -1,14 +1,19 @@
 """Differentiable conv-stack operators: the training path of BasicBlock / CVEncoder / DepthDecoderPP (reference
-train.py:126-145 runs autograd through modules/layers.py:24-85 and modules/networks.py:20-127).
+train.py:126-145 runs autograd through modules/layers.py:24-85 and modules/networks.py:20-127), and the convolution layer
+(`_ConvBiasAct`) the two encoders train through as well (train_ops.conv; their normalisation, pooling, depthwise and
+squeeze-excite operators are in train_ops).
 
 torch.autograd is the tape (plumbing); every arithmetic step, forward and backward, is a HIP kernel:
   forward        the same MFMA kernels as inference (direct / Winograd), weights packed per call (they change every step);
   data gradient  the forward kernels on the flipped, transposed weight (stride 2: on the zero-stuffed output gradient);
   weight / bias  csrc/sr_conv_bwd.hip (MFMA split over pixels, partial slabs + ordered reduce: deterministic);
   LeakyReLU      from the saved output; bilinear x2: its adjoint kernel.
-Gradients are pinned to the reference's own autograd (tests/golden/grad_block_*.npz, grad_cv_encoder_narrow.npz,
-grad_decoder_narrow.npz).  Not covered yet: the two encoders (no BatchNorm / InstanceNorm backward) -- DepthModel treats
-their outputs as constants."""
+Under torch.autocast the layer stays on fp32 kernels unless the switches below put 16-bit storage, 16-bit kernel I/O
+(sr_conv3x3_wino_io_nhwc_fwd, sr_pw_conv_io_nhwc_fwd) or the 16-bit MFMA kernels (csrc/sr_conv16.hip, csrc/sr_conv16_wgrad.hip)
+on its path.  Gradients are pinned to the reference's own autograd (tests/golden/grad_block_*.npz, grad_cv_encoder_narrow.npz,
+grad_decoder_narrow.npz); which kernels the layer launches, for every setting of the switches, to
+tests/golden/conv_layer_trace.json.gz."""
+import functools
 import os
 
 import torch
@@ -18,92 +23,85 @@ from . import _lib
 from .ops import _act_code, _conv_direct, _conv_wino, _is_nhwc_view, _pack, _strides, _workspace, as_nhwc, empty_nhwc
 
 
-# torch.autocast compatibility (the reference trains under 16-bit autocast, options.py:100-101, train.py:132): every
-# differentiable operator here runs its fp32 HIP kernels whatever the autocast state -- floating-point CUDA inputs that
-# arrive in fp16 / bf16 are cast to fp32 at the operator's entry (a differentiable cast: gradients go back in the caller's
-# dtype) and autocast is off inside.  fp32 compute and fp32 storage: more accurate than the reference's half-precision
-# convolutions, without their memory saving (an fp16-storage variant of the kernels is not built).
+# torch.autocast compatibility (the reference trains under 16-bit autocast, options.py:100-101, train.py:132).  Every
+# differentiable operator runs with autocast off inside and records on ctx whether its caller was inside an autocast region.
+# `_amp_fwd` / `_amp_bwd` (every operator but the conv layer) cast floating-point CUDA inputs that arrive in fp16 / bf16 to
+# fp32 at the operator's entry (a differentiable cast: gradients go back in the caller's dtype): fp32 kernels whatever the
+# autocast state.  `_amp_state_fwd` / `_amp_state_bwd` (`_ConvBiasAct`) leave the inputs alone: the layer decides what its
+# kernels read and write.
 _amp_cast_fwd = torch.amp.custom_fwd(device_type="cuda", cast_inputs=torch.float32)
 _amp_bwd = torch.amp.custom_bwd(device_type="cuda")
 
 
-def _amp_fwd(fwd):
-    """custom_fwd(cast_inputs=fp32) that also records on ctx whether the caller was inside an autocast region (and its
-    dtype): `_stash` then keeps the saved activations in that 16-bit dtype."""
-    cast = _amp_cast_fwd(fwd)
+def _autocast_off(fn):
+    @functools.wraps(fn)
+    def wrapper(ctx, *args, **kwargs):
+        with torch.autocast(device_type="cuda", enabled=False):
+            return fn(ctx, *args, **kwargs)
+    return wrapper
 
+
+def _recording_autocast(body):
+    """`body` (a forward with autocast already dealt with) behind a note on ctx of the caller's autocast state and dtype: what
+    `_stash` and `_ConvBiasAct` go by."""
+    @functools.wraps(body)
     def wrapper(ctx, *args, **kwargs):
         on = torch.is_autocast_enabled("cuda")
         ctx._sr_autocast = on
         ctx._sr_autocast_dtype = torch.get_autocast_dtype("cuda") if on else None
-        return cast(ctx, *args, **kwargs)
-    wrapper.__name__, wrapper.__doc__ = getattr(fwd, "__name__", "forward"), fwd.__doc__
+        return body(ctx, *args, **kwargs)
     return wrapper
 
 
-# fp16 / bf16 STORAGE of the saved activations under torch.autocast (SR_AUTOCAST_HALF_STORAGE=1; default since r06: fp32).  The
-# reference's autocast keeps activations in half precision (options.py:100-101); here the kernels compute and hand over
-# fp32, but what autograd SAVES for the backward pass -- the bulk of a training step's memory -- is stored in the autocast
-# dtype and widened again when the backward kernel needs it.  A tensor saved by several operators (a producer saves its
-# output for the activation's derivative, the consumer saves it as its input) is narrowed once and shared.
-#
-# r06: both 16-bit switches are OFF by default.  They buy memory (3.8 instead of 5.9 GiB peak at batch 2, 640x480, 7 views) and
-# cost time: the backward kernels are fp32, so every saved tensor is narrowed once and widened once by cast kernels (892 + 593
-# launches per step).  Measured training step (scripts/train_step_micro.py 2, profiles/r06_train_autocast.txt): fp32 77.7 ms;
-# bf16 autocast with storage + I/O 87.0, storage only 85.8, I/O only 83.1, neither (fp32 kernels under autocast) 78.4.  Until the
-# backward kernels read 16-bit operands themselves, "autocast is not slower than fp32" (VERDICT r05, f3) is the default and the
-# memory saving is opt-in: SR_AUTOCAST_HALF_STORAGE=1 SR_AUTOCAST_HALF_IO=1.
-STORE_HALF = os.environ.get("SR_AUTOCAST_HALF_STORAGE", "0") != "0"
-# 16-bit KERNEL I/O under torch.autocast (r04; SR_AUTOCAST_HALF_IO=1; default since r06: fp32 kernels).  Inside an
-# autocast region the convolutions of the conv stack (BasicBlock / CVEncoder / DepthDecoderPP: _ConvBiasAct) read and write
-# their activations in the autocast dtype -- the Winograd and pointwise kernels load four fp16 / bf16 channels as one 8-byte
-# access, widen them on the way into LDS / registers, accumulate in fp32 (fp32 weights, fp32 MFMA) and round the result once
-# on the way out (sr_conv3x3_wino_io_nhwc_fwd, sr_pw_conv_io_nhwc_fwd); what flows between the layers and what autograd saves
-# is 16-bit, like the reference's `precision: 16` training (options.py:100-101, train.py:132), with fp32 instead of fp16
-# accumulation inside a layer.  The backward kernels (weight / bias gradients, activation derivative, data gradient) run on
-# fp32 copies of the saved tensors; stride-2 and explicitly padded convolutions convert at their boundary.
-HALF_IO = os.environ.get("SR_AUTOCAST_HALF_IO", "0") != "0"
-_IO_CODE = {torch.float16: 1, torch.bfloat16: 2}
-# 16-bit MFMA convolutions (r07; SR_AUTOCAST_MFMA16, default 0 = off: exactly the paths above).  Where HALF_IO has put 16-bit
-# activations on the path, the convolutions of the conv stack -- 3x3 at stride 1 and 2, 1x1 -- multiply on the 16-bit matrix pipe
-# (csrc/sr_conv16.hip: weights rounded once to the activation dtype, fp32 accumulation, bias / residual / LeakyReLU in fp32,
-# one rounding on the way out): the arithmetic of the reference's `precision: 16` convolutions, with an fp32 instead of a 16-bit
-# result before the activation.  A layer whose forward ran there takes its data gradient there as well (the post-activation
-# gradient is cast to the layer's dtype); weight / bias gradients and the activation derivative stay fp32.
-# 1 = the layers sr_conv16_supported AND sr_conv16_prefers (the measured rule, profiles/r07_conv16.txt) accept, 2 = every
-# supported layer (tests, A/B runs).  Read at call time, like HALF_IO.  fp16 (not bf16) needs a loss scaler: the 16-bit data
-# gradient underflows otherwise.
-MFMA16 = int(os.environ.get("SR_AUTOCAST_MFMA16", "0") or 0)
-# 16-bit weight gradient (r08; SR_AUTOCAST_MFMA16_WGRAD, default 0 = off: exactly the backward above).  A layer whose forward ran on
-# the 16-bit MFMA kernel saved a 16-bit input and output; its post-activation gradient is rounded to 16 bits for the data gradient
-# anyway.  With the switch on, the backward of such a layer makes no fp32 copy of them: sr_act_bwd_bias16_nhwc reads the
-# arriving gradient (fp32 or 16-bit) and the saved output and writes the 16-bit post-activation gradient and the fp32 bias
-# gradient, sr_conv16_wgrad_nhwc multiplies the saved input with it on the 16-bit matrix pipe (csrc/sr_conv16_wgrad.hip: exact
-# products, fp32 accumulation, deterministic), and the data gradient consumes the same 16-bit gradient.  A stride-2 data gradient
-# keeps the fp32 zero-stuffing kernel around it.  1 = the layers sr_conv16_wgrad_supported AND sr_conv16_wgrad_prefers accept (the
-# measured rule, profiles/r08_conv16_wgrad.txt), 2 = every supported layer.  Read at call time, like MFMA16.
-MFMA16_WGRAD = int(os.environ.get("SR_AUTOCAST_MFMA16_WGRAD", "0") or 0)
+def _amp_fwd(fwd):
+    return _recording_autocast(_amp_cast_fwd(fwd))
 
 
 def _amp_state_fwd(fwd):
-    """Like `_amp_fwd` but WITHOUT casting the inputs: records the caller's autocast state on ctx and runs the body with
-    autocast off; the operator decides what dtype its kernels read and write."""
-    def wrapper(ctx, *args, **kwargs):
-        on = torch.is_autocast_enabled("cuda")
-        ctx._sr_autocast = on
-        ctx._sr_autocast_dtype = torch.get_autocast_dtype("cuda") if on else None
-        with torch.autocast(device_type="cuda", enabled=False):
-            return fwd(ctx, *args, **kwargs)
-    wrapper.__name__, wrapper.__doc__ = getattr(fwd, "__name__", "forward"), fwd.__doc__
-    return wrapper
+    return _recording_autocast(_autocast_off(fwd))
 
 
-def _amp_state_bwd(bwd):
-    def wrapper(ctx, *grads):
-        with torch.autocast(device_type="cuda", enabled=False):
-            return bwd(ctx, *grads)
-    wrapper.__name__, wrapper.__doc__ = getattr(bwd, "__name__", "backward"), bwd.__doc__
-    return wrapper
+_amp_state_bwd = _autocast_off
+
+
+# The four 16-bit switches of the layer under torch.autocast.  All are read at call time (tests, scripts and
+# experimental.autocast_mfma16 set the module attributes) and all default to off: an autocast step then runs the fp32 step's
+# kernels.
+#
+# STORE_HALF (SR_AUTOCAST_HALF_STORAGE): what autograd SAVES for the backward pass -- the bulk of a training step's memory -- is
+# stored in the autocast dtype and widened again when a backward kernel needs fp32 (`_stash` / `_unstash`, shared with
+# train_ops).  A tensor saved by several operators (a producer saves its output for the activation's derivative, the consumer
+# saves it as its input) is narrowed once and shared.  Tensors below 4096 elements and parameters are left alone.
+STORE_HALF = os.environ.get("SR_AUTOCAST_HALF_STORAGE", "0") != "0"
+# HALF_IO (SR_AUTOCAST_HALF_IO): inside an autocast region `_ConvBiasAct` reads and writes its activations in the autocast
+# dtype, like the reference's `precision: 16` training (options.py:100-101, train.py:132).  The Winograd and pointwise kernels
+# load four 16-bit channels as one 8-byte access, widen them, accumulate in fp32 (fp32 weights, fp32 MFMA) and round once on
+# the way out; stride-2 and explicitly padded convolutions convert at the boundary of the fp32 kernel.  The backward kernels
+# run on fp32 copies of the saved tensors.
+# Why both are opt-in: together they bring the peak from 5.9 to 3.8 GiB (batch 2, 640x480, 7 views) and cost time, because
+# every saved tensor is narrowed once and widened once by cast kernels (892 + 593 launches per step).  Training step
+# (scripts/train_step_micro.py 2, profiles/r06_train_autocast.txt): fp32 77.7 ms; bf16 autocast with storage + I/O 87.0,
+# storage only 85.8, I/O only 83.1, neither 78.4.
+HALF_IO = os.environ.get("SR_AUTOCAST_HALF_IO", "0") != "0"
+_IO_CODE = {torch.float16: 1, torch.bfloat16: 2}
+# MFMA16 (SR_AUTOCAST_MFMA16): where HALF_IO has put 16-bit activations on the path, 3x3 convolutions at stride 1 and 2 and 1x1
+# convolutions multiply on the 16-bit matrix pipe (csrc/sr_conv16.hip: weights rounded once to the activation dtype, fp32
+# accumulation, bias / residual / LeakyReLU in fp32, one rounding on the way out).  A layer whose forward ran there takes its
+# data gradient there as well, on the post-activation gradient cast to the layer's dtype.  1 = the layers sr_conv16_supported
+# AND sr_conv16_prefers accept (the measured rule, profiles/r07_conv16.txt), 2 = every supported layer (tests, A/B runs).
+# fp16 (not bf16) needs a loss scaler: the 16-bit data gradient underflows otherwise.
+MFMA16 = int(os.environ.get("SR_AUTOCAST_MFMA16", "0") or 0)
+# MFMA16_WGRAD (SR_AUTOCAST_MFMA16_WGRAD): the backward of a layer whose forward ran on the 16-bit MFMA kernel makes no fp32
+# copy of the saved input and output.  sr_act_bwd_bias16_nhwc reads the arriving gradient (fp32 or 16-bit) and the saved
+# output and writes the 16-bit post-activation gradient and the fp32 bias gradient; sr_conv16_wgrad_nhwc multiplies the saved
+# input with it on the 16-bit matrix pipe (csrc/sr_conv16_wgrad.hip: exact products, fp32 accumulation, deterministic); the
+# data gradient consumes the same 16-bit gradient (stride 2: around the fp32 zero-stuffing kernel).  1 = the layers
+# sr_conv16_wgrad_supported AND sr_conv16_wgrad_prefers accept (the measured rule, profiles/r08_conv16_wgrad.txt), 2 = every
+# supported layer.
+MFMA16_WGRAD = int(os.environ.get("SR_AUTOCAST_MFMA16_WGRAD", "0") or 0)
+# FUSED_ACT_BIAS (SR_FUSED_ACT_BIAS, default on): LeakyReLU' and the bias gradient of the fp32 backward in one float4 pass
+# (sr_act_bwd_bias_nhwc); 0, or Cout % 4 != 0: separate sr_act_bwd and sr_bias_grad_nhwc launches.
+FUSED_ACT_BIAS = os.environ.get("SR_FUSED_ACT_BIAS", "1") != "0"
 
 
 def _nhwc_any(t, name):
@@ -140,8 +138,6 @@ def _stash(ctx, *tensors):
 
 def _unstash(ctx):
     return tuple(t.float() if (f and t is not None) else t for t, f in zip(ctx.saved_tensors, ctx._sr_stash_flags))
-
-FUSED_ACT_BIAS = os.environ.get("SR_FUSED_ACT_BIAS", "1") != "0"   # 0: separate sr_act_bwd + sr_bias_grad_nhwc launches (r02 a/b)
 
 
 def grad_wanted(*tensors_or_modules):
@@ -223,14 +219,9 @@ def _dense_nhwc(t, any_dtype=False):
     return t
 
 
-def _aligned8(t):
-    """None, or a 16-bit channels-last view whose pixel rows all start 8-byte aligned (four channels per access)."""
-    return t is None or (t.data_ptr() % 8 == 0 and all(s % 4 == 0 for s in _strides(t)))
-
-
-def _aligned16(t):
-    """None, or a 16-bit channels-last view whose pixel rows all start 16-byte aligned (eight channels per access)."""
-    return t is None or (t.data_ptr() % 16 == 0 and all(s % 8 == 0 for s in _strides(t)))
+def _rows_aligned(t, nbytes):
+    """None, or a channels-last view whose pixel rows all start `nbytes`-aligned (nbytes / element size channels per access)."""
+    return t is None or (t.data_ptr() % nbytes == 0 and all(st % (nbytes // t.element_size()) == 0 for st in _strides(t)))
 
 
 def _mfma16_selects(b, h, w, ci, co, k, stride, pads):
@@ -259,8 +250,8 @@ def _conv16_routes(x, weight, stride, residual, pads):
     """True when _conv_raw_io takes this call (16-bit channels-last views `x`, `residual`) to the 16-bit MFMA kernel."""
     b, ci, h, w = x.shape
     co, _, k, _ = weight.shape
-    return x.dtype in _IO_CODE and _mfma16_selects(b, h, w, ci, co, k, stride, pads) and _aligned16(x) and \
-        (residual is None or (residual.dtype == x.dtype and _aligned16(residual)))
+    return x.dtype in _IO_CODE and _mfma16_selects(b, h, w, ci, co, k, stride, pads) and _rows_aligned(x, 16) and \
+        (residual is None or (residual.dtype == x.dtype and _rows_aligned(residual, 16)))
 
 
 def _conv16(x, weight, bias, stride, residual, slope, out_f32=False):
@@ -282,10 +273,11 @@ def _conv16(x, weight, bias, stride, residual, slope, out_f32=False):
     return out
 
 
-def _conv_raw_io(x, weight, bias, stride, residual, slope, pads):
-    """_conv_raw on fp16 / bf16 activations: the 16-bit MFMA kernel where MFMA16 selects the layer (3x3 at stride 1 and 2, 1x1);
-    else 16-bit kernel I/O where the kernel has it (3x3 / stride 1 through Winograd, 1x1 / stride 1 through the pointwise
-    GEMM), boundary conversion around the fp32 kernel otherwise."""
+def _conv_raw_io(x, weight, bias, stride, residual, slope, pads, mfma16=None):
+    """_conv_raw on fp16 / bf16 activations: the 16-bit MFMA kernel where MFMA16 selects the layer (3x3 at stride 1 and 2, 1x1;
+    `mfma16`: that decision, for a caller that has made it on these channels-last views already); else 16-bit kernel I/O where
+    the kernel has it (3x3 / stride 1 through Winograd, 1x1 / stride 1 through the pointwise GEMM), boundary conversion around
+    the fp32 kernel otherwise."""
     dt = x.dtype
     x = _nhwc_any(x, "conv input")
     b, ci, h, w = x.shape
@@ -294,12 +286,12 @@ def _conv_raw_io(x, weight, bias, stride, residual, slope, pads):
         raise ValueError(f"conv weight expects {ci_w} input channels, got {ci}")
     if residual is not None:
         residual = _nhwc_any(residual if residual.dtype == dt else residual.to(dt), "residual")
-    if MFMA16 and _conv16_routes(x, weight, stride, residual, pads):
+    if _conv16_routes(x, weight, stride, residual, pads) if mfma16 is None else mfma16:
         return _conv16(x, weight, bias, stride, residual, slope)
     wino = pads is None and stride == 1 and k == 3 and b > 0 and ci % 4 == 0 and co % 4 == 0 and \
         bool(_lib.lib().sr_conv_prefers_wino(b, h, w, ci, co, k, stride))
     pw = pads is None and stride == 1 and k == 1 and b > 0 and ci % 4 == 0
-    if not ((wino or pw) and _aligned8(x) and _aligned8(residual)):
+    if not ((wino or pw) and _rows_aligned(x, 8) and _rows_aligned(residual, 8)):
         y = _conv_raw(x.float(), weight, bias, stride, residual.float() if residual is not None else None, slope, pads)
         return y.to(dt)
     out = torch.empty((b, co, h, w), dtype=dt, device=x.device, memory_format=torch.channels_last)
@@ -346,6 +338,105 @@ def _conv_raw(x, weight, bias, stride, residual=None, slope=None, pads=None):
     return out
 
 
+def _grad16(ctx, g, x, weight, out):
+    """The predicate of the backward on 16-bit operands (MFMA16_WGRAD): the arriving gradient (fp32 or the layer's dtype) as a dense
+    channels-last tensor when the layer's forward ran on sr_conv16_nhwc_fwd, what it saved is 16-bit, the switch selects its shape
+    and the rows are 16-byte aligned; None when the backward takes fp32 copies."""
+    if not (MFMA16_WGRAD and ctx.mfma16 and x.dtype in _IO_CODE and g.dtype in (torch.float32, x.dtype) and
+            (out is None or out.dtype == x.dtype) and
+            _wgrad16_selects(x.shape[0], x.shape[2], x.shape[3], x.shape[1], weight.shape[0], weight.shape[2], ctx.stride, ctx.pads)):
+        return None
+    g = _dense_nhwc(g, any_dtype=True)
+    return g if _rows_aligned(x, 16) and _rows_aligned(g, 16) else None
+
+
+def _post_act_grad(g, out, slope, want_b, dt16):
+    """Backward step 1, in one pass where a kernel has it: gp = g * LeakyReLU'(out) (g itself without an activation) and the bias
+    gradient -> (gp, d_b or None).  fp32 operands (dt16 None): sr_act_bwd_bias_nhwc, or sr_act_bwd alone (FUSED_ACT_BIAS = 0,
+    Cout % 4 != 0, no pixels: the caller then takes the bias gradient from gp).  16-bit operands: sr_act_bwd_bias16_nhwc, which
+    also rounds an fp32 `g` to the layer's dtype `dt16`."""
+    dev = g.device
+    b, co, ho, wo = g.shape
+    px = b * ho * wo
+    act = slope is not None
+    if dt16 is not None:
+        write_gp = act or g.dtype != dt16
+    elif FUSED_ACT_BIAS and co % 4 == 0 and b > 0:
+        write_gp = act
+    else:
+        if not act:
+            return g, None
+        gp = torch.empty_like(g)
+        _lib.call("sr_act_bwd", dev, g, _dense_nhwc(out), gp, g.numel(), float(slope))
+        return gp, None
+    if not (write_gp or want_b):
+        return g, None
+    gp = torch.empty_like(g, dtype=dt16 or torch.float32) if write_gp else g
+    kernel = "sr_act_bwd_bias16" if dt16 is not None else "sr_act_bwd_bias"
+    # (the bias gradient is a deterministic two-stage sum through a workspace)
+    nws = getattr(_lib.lib(), kernel + "_workspace_bytes")(px, co) if want_b else 0
+    ws = _workspace(dev, "bias_grad", nws) if want_b else None
+    d_b = torch.empty((co,), dtype=torch.float32, device=dev) if want_b else None
+    out = _dense_nhwc(out, any_dtype=dt16 is not None) if act else None
+    tail = (gp if write_gp else None, d_b, px, co, float(slope) if act else 0.0)
+    if dt16 is None:
+        _lib.call("sr_act_bwd_bias_nhwc", dev, g, out, *tail, ws, nws)
+    else:
+        io = _IO_CODE[dt16]
+        _lib.call("sr_act_bwd_bias16_nhwc", dev, g, 0 if g.dtype == torch.float32 else io, out, *tail, io, ws, nws)
+    return gp, d_b
+
+
+def _weight_grad(x, gp, weight, stride, pads):
+    """Backward step 2: dL/dW as a dense fp32 [Co][Ci][k][k] tensor from the saved input and the post-activation gradient, both
+    fp32 (sr_conv_wgrad_nhwc, or sr_conv_wgrad_padded_nhwc for explicit `pads`) or both 16-bit (sr_conv16_wgrad_nhwc)."""
+    lib = _lib.lib()
+    dev = x.device
+    b, ci, h, w = x.shape
+    co, _, k, _ = weight.shape
+    ho, wo = gp.shape[2], gp.shape[3]
+    if b == 0:
+        return torch.zeros(weight.shape, dtype=torch.float32, device=dev)
+    d_w = torch.empty(weight.shape, dtype=torch.float32, device=dev)   # (NOT empty_like: a channels_last weight's strides)
+    head = (x, *_strides(x), gp, *_strides(gp), d_w, b, h, w, ci, co, k, stride)
+    if x.dtype in _IO_CODE:
+        nws = lib.sr_conv16_wgrad_workspace_bytes(b, h, w, ci, co, k, stride)
+        _lib.call("sr_conv16_wgrad_nhwc", dev, *head, _IO_CODE[x.dtype], _workspace(dev, "wgrad", nws), nws)
+    elif pads is None:
+        nws = lib.sr_conv_wgrad_workspace_bytes(b, h, w, ci, co, k, stride)
+        _lib.call("sr_conv_wgrad_nhwc", dev, *head, _workspace(dev, "wgrad", nws), nws)
+    else:
+        nws = lib.sr_conv_wgrad_padded_workspace_bytes(b, ho, wo, ci, co, k)
+        _lib.call("sr_conv_wgrad_padded_nhwc", dev, *head, pads[0], pads[1], ho, wo, _workspace(dev, "wgrad", nws), nws)
+    return d_w
+
+
+def _data_grad(gp, weight, x_shape, stride, pads, dt16, out_f32):
+    """Backward step 3: dL/dx = conv_s1(gp, flip(W)^T), at stride 2 on the zero-stuffed gp (the fp32 stuffing kernel, whatever gp's
+    dtype).  `dt16`: the layer's dtype when its forward ran on the 16-bit MFMA kernel -- so does the data gradient, on the
+    gradient cast to it, with d_x in fp32 when the caller's x was (`out_f32`: no cast behind the kernel)."""
+    dev = gp.device
+    b, ci, h, w = x_shape
+    co, _, k, _ = weight.shape
+    ho, wo = gp.shape[2], gp.shape[3]
+    wt = torch.empty((ci, co, k, k), dtype=torch.float32, device=dev)
+    _lib.call("sr_conv_flip_transpose_weights", dev, weight.detach().contiguous(), co, ci, k, wt)
+    src = gp
+    if stride != 1:   # the stuffed gradient lives on the input's H x W grid
+        src = empty_nhwc(b, co, h, w, dev)
+        if b > 0:
+            g32 = gp.float()
+            _lib.call("sr_zero_stuff2x_nhwc", dev, g32, *_strides(g32), src, b, ho, wo, h, w, co)
+    if dt16 is not None and b > 0:
+        src = src.to(dt16)
+        if _conv16_routes(src, wt, 1, None, None):
+            return _conv16(src, wt, None, 1, None, None, out_f32=out_f32)
+        # (MFMA16 = 1 and the rule declines the transposed shape, or the switch changed since the forward)
+    if pads is not None:   # full correlation: pads k-1-p on the opposite roles; stuffed: output H x W needs (k-1-pt, k-1-pl, pt, pl)
+        pads = (k - 1 - pads[0], k - 1 - pads[1]) + ((k - 1 - pads[2], k - 1 - pads[3]) if stride == 1 else (pads[0], pads[1]))
+    return _conv_raw(src, wt, None, 1, pads=pads)
+
+
 class _ConvBiasAct(torch.autograd.Function):
     """y = act(conv(x, W, stride, pad = k // 2 or explicit `pads`) + b [+ residual]), act = LeakyReLU(slope) or identity
     (slope None).  `pads` = (top, left, bottom, right) zero padding (TF-"SAME" convolutions of the image-prior encoder,
@@ -371,12 +462,13 @@ class _ConvBiasAct(torch.autograd.Function):
             for name, t in (("conv input", x), ("conv weight", weight)):
                 _lib.require_device_f32(name, t)
             x = as_nhwc(x, "conv input")
-        ctx.mfma16 = False
-        if MFMA16 and dt != torch.float32:   # (the same test _conv_raw_io makes, on the same views: the backward follows it)
+            ctx.mfma16 = False
+            out = _conv_raw(x, weight, bias, stride, residual, slope, pads)
+        else:   # whether the layer runs on the 16-bit MFMA kernel is decided here, once: the launch and the backward follow it
             x = _nhwc_any(x, "conv input")
             residual = _nhwc_any(residual, "residual") if residual is not None else None
             ctx.mfma16 = _conv16_routes(x, weight, stride, residual, pads)
-        out = _conv_raw(x, weight, bias, stride, residual, slope, pads)
+            out = _conv_raw_io(x, weight, bias, stride, residual, slope, pads, mfma16=ctx.mfma16)
         ctx.stride, ctx.slope, ctx.pads = stride, slope, pads
         ctx.has_bias, ctx.has_res = bias is not None, residual is not None
         _stash(ctx, x, weight, out if slope is not None else None)
@@ -386,145 +478,26 @@ class _ConvBiasAct(torch.autograd.Function):
     @_amp_state_bwd
     def backward(ctx, g):
         x, weight, out = _unstash(ctx)
-        if MFMA16_WGRAD and ctx.mfma16 and x.dtype in _IO_CODE and g.dtype in (torch.float32, x.dtype) and \
-                (out is None or out.dtype == x.dtype) and \
-                _wgrad16_selects(x.shape[0], x.shape[2], x.shape[3], x.shape[1], weight.shape[0], weight.shape[2], ctx.stride, ctx.pads):
-            g16 = _dense_nhwc(g, any_dtype=True)
-            if _aligned16(x) and _aligned16(g16):
-                return _ConvBiasAct._backward_wgrad16(ctx, g16, x, weight, out)
-        # (16-bit I/O: the backward kernels take fp32 copies of what the forward saved in 16 bits)
         dt16 = x.dtype if ctx.mfma16 else None   # the layer's 16-bit dtype when its forward ran on the 16-bit MFMA kernel
-        x = x if x.dtype == torch.float32 else x.float()
-        out = out if (out is None or out.dtype == torch.float32) else out.float()
-        lib = _lib.lib()
-        dev = x.device
-        b, ci, h, w = x.shape
-        co, _, k, _ = weight.shape
-        s = ctx.stride
-        ho, wo = g.shape[2], g.shape[3]
-        g = _dense_nhwc(g if g.dtype == torch.float32 else g.float())
+        g16 = _grad16(ctx, g, x, weight, out)
+        if g16 is not None:
+            g, op16 = g16, dt16
+        else:   # the backward kernels take fp32 copies of what the forward saved in 16 bits
+            x = x if x.dtype == torch.float32 else x.float()
+            out = out if (out is None or out.dtype == torch.float32) else out.float()
+            g, op16 = _dense_nhwc(g if g.dtype == torch.float32 else g.float()), None
         need_x, need_w, need_b, need_r = ctx.needs_input_grad[:4]
         want_b = ctx.has_bias and need_b
-        fused = FUSED_ACT_BIAS and co % 4 == 0 and b > 0 and (ctx.slope is not None or want_b)
-        d_b = None
-        with _lib.on_device(dev):
-            if fused:
-                # one float4 pass: LeakyReLU' of the saved output and / or the bias gradient (deterministic two-stage sum)
-                gp = torch.empty_like(g) if ctx.slope is not None else g
-                px = b * ho * wo
-                nws = lib.sr_act_bwd_bias_workspace_bytes(px, co) if want_b else 0
-                ws = _workspace(dev, "bias_grad", nws) if want_b else None
-                if want_b:
-                    d_b = torch.empty((co,), dtype=torch.float32, device=dev)
-                _lib.call("sr_act_bwd_bias_nhwc", dev, g, _dense_nhwc(out) if ctx.slope is not None else None,
-                          gp if ctx.slope is not None else None, d_b, px, co,
-                          float(ctx.slope) if ctx.slope is not None else 0.0, ws, nws)
-            elif ctx.slope is not None:
-                gp = torch.empty_like(g)
-                _lib.call("sr_act_bwd", dev, g, _dense_nhwc(out), gp, g.numel(), float(ctx.slope))
-            else:
-                gp = g
-            d_x = d_w = None
-            gsb, gsp = _strides(gp)
-            pads = ctx.pads
-            if need_w and b > 0:
-                # dense [Co][Ci][k][k]: what sr_conv_wgrad_nhwc writes -- NOT empty_like (a channels_last weight's strides)
-                d_w = torch.empty(weight.shape, dtype=torch.float32, device=dev)
-                xsb, xsp = _strides(x)
-                if pads is None:
-                    nws = lib.sr_conv_wgrad_workspace_bytes(b, h, w, ci, co, k, s)
-                    ws = _workspace(dev, "wgrad", nws)
-                    _lib.call("sr_conv_wgrad_nhwc", dev, x, xsb, xsp, gp, gsb, gsp, d_w, b, h, w, ci, co, k, s, ws, nws)
-                else:
-                    nws = lib.sr_conv_wgrad_padded_workspace_bytes(b, ho, wo, ci, co, k)
-                    ws = _workspace(dev, "wgrad", nws)
-                    _lib.call("sr_conv_wgrad_padded_nhwc", dev, x, xsb, xsp, gp, gsb, gsp, d_w, b, h, w, ci, co, k, s,
-                              pads[0], pads[1], ho, wo, ws, nws)
-            elif need_w:
-                d_w = torch.zeros(weight.shape, dtype=torch.float32, device=dev)
-            if want_b and d_b is None:
-                d_b = torch.empty((co,), dtype=torch.float32, device=dev)
-                _lib.call("sr_bias_grad_nhwc", dev, gp, gsb, gsp, d_b, b, ho, wo, co)
-            if need_x:
-                wt = torch.empty((ci, co, k, k), dtype=torch.float32, device=dev)
-                _lib.call("sr_conv_flip_transpose_weights", dev, weight.detach().contiguous(), co, ci, k, wt)
-                if s == 1:
-                    src = gp
-                else:  # stride 2: dL/dx = conv_s1(zero-stuffed dL/dy, flip(W)^T) on the input's grid
-                    src = empty_nhwc(b, co, h, w, dev)
-                    if b > 0:
-                        _lib.call("sr_zero_stuff2x_nhwc", dev, gp, gsb, gsp, src, b, ho, wo, h, w, co)
-                if dt16 is not None and b > 0:
-                    # the forward ran on the 16-bit MFMA kernel: so does the data gradient, on the gradient cast to the layer's
-                    # dtype (stride 2: the fp32 stuffing kernel first -- either order is two launches); d_x comes out in
-                    # the caller's dtype when that is fp32 (no cast behind the kernel)
-                    src = src.to(dt16)
-                    if _conv16_routes(src, wt, 1, None, None):
-                        d_x = _conv16(src, wt, None, 1, None, None, out_f32=ctx.in_dtypes[0] == torch.float32)
-                    else:   # (MFMA16 = 1 and the rule declines the transposed shape, or the switch changed since the forward)
-                        d_x = _conv_raw(src, wt, None, 1)
-                elif pads is None:
-                    d_x = _conv_raw(src, wt, None, 1)
-                elif s == 1:   # full correlation: pads k-1-p on the opposite roles
-                    d_x = _conv_raw(src, wt, None, 1, pads=(k - 1 - pads[0], k - 1 - pads[1], k - 1 - pads[2], k - 1 - pads[3]))
-                else:          # the stuffed gradient lives on the input's H x W grid: output H x W needs (k-1-pt, k-1-pl, pt, pl)
-                    d_x = _conv_raw(src, wt, None, 1, pads=(k - 1 - pads[0], k - 1 - pads[1], pads[0], pads[1]))
-        d_r = gp if (ctx.has_res and need_r) else None
-        xdt, rdt = ctx.in_dtypes
-        if d_x is not None and d_x.dtype != xdt:
-            d_x = d_x.to(xdt)
-        if d_r is not None and d_r.dtype != rdt:
-            d_r = d_r.to(rdt)
-        return d_x, d_w, d_b, d_r, None, None, None
-
-    @staticmethod
-    def _backward_wgrad16(ctx, g, x, weight, out):
-        """The backward of a layer whose forward ran on sr_conv16_nhwc_fwd, on 16-bit operands throughout (MFMA16_WGRAD): `x` and
-        `out` are the saved 16-bit tensors, `g` the dense channels-last gradient in its arriving dtype (fp32 or the layer's)."""
-        lib = _lib.lib()
-        dev, dt16 = x.device, x.dtype
-        io = _IO_CODE[dt16]
-        b, ci, h, w = x.shape
-        co, _, k, _ = weight.shape
-        s = ctx.stride
-        ho, wo = g.shape[2], g.shape[3]
-        need_x, need_w, need_b, need_r = ctx.needs_input_grad[:4]
-        want_b = ctx.has_bias and need_b
-        act = ctx.slope is not None
-        d_x = d_w = d_b = None
-        with _lib.on_device(dev):
-            # one 16-byte pass: LeakyReLU' of the saved 16-bit output, the rounding to the layer's dtype, the bias gradient
-            write_gp = act or g.dtype != dt16
-            gp = torch.empty((b, co, ho, wo), dtype=dt16, device=dev, memory_format=torch.channels_last) if write_gp else g
-            if write_gp or want_b:
-                px = b * ho * wo
-                nws = lib.sr_act_bwd_bias16_workspace_bytes(px, co) if want_b else 0
-                ws = _workspace(dev, "bias_grad", nws) if want_b else None
-                if want_b:
-                    d_b = torch.empty((co,), dtype=torch.float32, device=dev)
-                _lib.call("sr_act_bwd_bias16_nhwc", dev, g, 0 if g.dtype == torch.float32 else io,
-                          _dense_nhwc(out, any_dtype=True) if act else None, gp if write_gp else None, d_b, px, co,
-                          float(ctx.slope) if act else 0.0, io, ws, nws)
-            gsb, gsp = _strides(gp)
+        d_x = d_w = None
+        with _lib.on_device(x.device):
+            gp, d_b = _post_act_grad(g, out, ctx.slope, want_b, op16)
             if need_w:
-                d_w = torch.empty(weight.shape, dtype=torch.float32, device=dev)   # dense [Co][Ci][k][k]
-                nws = lib.sr_conv16_wgrad_workspace_bytes(b, h, w, ci, co, k, s)
-                ws = _workspace(dev, "wgrad", nws)
-                _lib.call("sr_conv16_wgrad_nhwc", dev, x, *_strides(x), gp, gsb, gsp, d_w, b, h, w, ci, co, k, s, io, ws, nws)
+                d_w = _weight_grad(x, gp, weight, ctx.stride, ctx.pads)
+            if want_b and d_b is None:   # (behind the unfused sr_act_bwd)
+                d_b = torch.empty((weight.shape[0],), dtype=torch.float32, device=x.device)
+                _lib.call("sr_bias_grad_nhwc", x.device, gp, *_strides(gp), d_b, g.shape[0], g.shape[2], g.shape[3], weight.shape[0])
             if need_x:
-                wt = torch.empty((ci, co, k, k), dtype=torch.float32, device=dev)
-                _lib.call("sr_conv_flip_transpose_weights", dev, weight.detach().contiguous(), co, ci, k, wt)
-                if s == 1:
-                    src = gp
-                else:   # stride 2: the fp32 zero-stuffing kernel and the casts around it stay (a 16-bit one is not built)
-                    stuffed = empty_nhwc(b, co, h, w, dev)
-                    gp32 = gp.float()
-                    _lib.call("sr_zero_stuff2x_nhwc", dev, gp32, *_strides(gp32), stuffed, b, ho, wo, h, w, co)
-                    src = stuffed.to(dt16)
-                if _conv16_routes(src, wt, 1, None, None):
-                    d_x = _conv16(src, wt, None, 1, None, None, out_f32=ctx.in_dtypes[0] == torch.float32)
-                else:   # (MFMA16 = 1 and the rule declines the transposed shape, or the switch changed since the forward)
-                    d_x = _conv_raw(src, wt, None, 1)
+                d_x = _data_grad(gp, weight, x.shape, ctx.stride, ctx.pads, dt16, ctx.in_dtypes[0] == torch.float32)
         d_r = gp if (ctx.has_res and need_r) else None
         xdt, rdt = ctx.in_dtypes
         if d_x is not None and d_x.dtype != xdt:

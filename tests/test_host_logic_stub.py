@@ -21,11 +21,12 @@ B, K, C, H, W, D = 2, 3, 16, 8, 12, 4
 _BYREF = type(ctypes.byref(ctypes.c_int()))
 
 
-@pytest.fixture
-def stub(monkeypatch):
+def make_stub(monkeypatch):
     class Calls(list):
         prefer_wino = False
         prefer_wino4 = 0     # the F(4x4) kernel form sr_conv_prefers_wino4 answers
+        prefer16 = 0         # sr_conv16_prefers: 0 / 1, or the set of shapes (its arguments) it answers 1 for
+        prefer16_wgrad = 0   # sr_conv16_wgrad_prefers
     calls = Calls()
     calls.args = []          # (name, arguments) of every stubbed call
     calls.option_sets = []   # (id, value) of every sr_option_set, forwarded to the real library
@@ -64,6 +65,12 @@ def stub(monkeypatch):
                 return int(calls.prefer_wino)
             if self.name == "sr_conv_prefers_wino4":
                 return calls.prefer_wino4
+            if self.name == "sr_conv16_prefers":
+                return int(args in calls.prefer16) if isinstance(calls.prefer16, (set, frozenset)) else calls.prefer16
+            if self.name == "sr_conv16_wgrad_prefers":
+                return calls.prefer16_wgrad
+            if self.name.endswith("_supported"):
+                return 1
             if self.name in ("sr_pw_conv_plan", "sr_pw_conv_tiled_plan"):
                 # (tile variant, K split) through the two out-pointers; the tiled plan splits K only when it may
                 plan = (2, 1) if self.name == "sr_pw_conv_plan" else (1, 4) if args[3] else (3, 1)
@@ -97,6 +104,11 @@ def stub(monkeypatch):
     monkeypatch.setattr(torch.cuda, "current_stream", lambda d=None: Stream())
     monkeypatch.setattr(torch.cuda, "Event", Event)
     return calls
+
+
+@pytest.fixture
+def stub(monkeypatch):
+    return make_stub(monkeypatch)
 
 
 @pytest.mark.parametrize("cls,kw,fwd", [(cv.CostVolumeManager, {}, "sr_dot_volume_fwd"),
@@ -657,13 +669,16 @@ def _dispatch_trace(stub, monkeypatch, case, rc):
                 trace["records"] = [[n, f, list(shape), ex] for n, f, _, _, shape, ex in prof]
         except (ValueError, _lib.HipLibraryError) as e:
             trace["raises"] = f"{type(e).__name__}: {e}"
-        argtypes = lambda n: _lib.SIGNATURES[n][1]
         # (profiled: without the queries behind a record's name and executed FLOPs -- the records pin what they answered)
         trace["calls_profiled" if profiled else "calls"] = [
-            [n] + [("p" if v is not None else None) if t is ctypes.c_void_p else
-                   round(v.value if isinstance(v, ctypes.c_float) else v, 6) for v, t in zip(a, argtypes(n))]
-            for n, a in stub.args if not (profiled and n.endswith(("_kernel_name", "_plan")))]
+            _pinned_call(n, a) for n, a in stub.args if not (profiled and n.endswith(("_kernel_name", "_plan")))]
     return trace
+
+
+def _pinned_call(name, args):
+    """[entry point, every non-pointer argument, "p" / None for each pointer]"""
+    return [name] + [("p" if v is not None else None) if t is ctypes.c_void_p else
+                     round(v.value if isinstance(v, ctypes.c_float) else v, 6) for v, t in zip(args, _lib.SIGNATURES[name][1])]
 
 
 def _dispatch_traces(stub, monkeypatch):
@@ -694,6 +709,130 @@ def test_conv2d_dispatch_matches_the_golden(stub, monkeypatch):
     and executed FLOPs, shape) as recorded in tests/golden/conv2d_dispatch.json.gz."""
     got = _dispatch_traces(stub, monkeypatch)
     with gzip.open(_GOLDEN_DISPATCH, "rt") as f:
+        want = json.load(f)
+    assert sorted(got) == sorted(want)
+    for cid in want:
+        assert got[cid] == want[cid], cid
+
+
+# ---- the conv training layer's launch trace, pinned -----------------------------------------------------------------------
+# What autograd_ops._ConvBiasAct launches, forward and backward, over a grid of precisions (autocast dtype and the four 16-bit
+# switches), library answers, layer shapes, operands, needed gradients and FUSED_ACT_BIAS: every call to an entry point that
+# launches (pack calls included; pure queries are not part of it), in order, with the dtypes of the output and of what autograd
+# saved and the dtype, shape and strides of every returned gradient.  Recorded in tests/golden/conv_layer_trace.json.gz by
+# scripts/record_conv_layer_trace.py; a case that raises pins its exception.
+_GOLDEN_LAYER = os.path.join(os.path.dirname(os.path.abspath(__file__)), "golden", "conv_layer_trace.json.gz")
+_QUERIES = ("_supported", "_prefers", "_prefers_wino", "_bytes", "_floats")
+# amp: the autocast dtype (None: no autocast region); store / io / mfma / wgrad: STORE_HALF, HALF_IO, MFMA16, MFMA16_WGRAD;
+# p16: sr_conv16_prefers answers 0, 1, or "fwd" = 1 for the layer's own shape only (not for its transposed data gradient);
+# p16w / wino: sr_conv16_wgrad_prefers / sr_conv_prefers_wino; x16: x (and the residual) arrive in the autocast dtype, as from
+# a 16-bit layer before; sliced: x is a channel slice whose 16-bit rows are not 16-byte aligned; g32: the backward is handed a
+# dense fp32 gradient (directly: the engine would cast it to the output's dtype); need: the inputs that require a gradient
+# (x, weight, bias, residual); then: switches set between the forward and the backward.
+_LAYER_CASE = dict(amp=None, store=False, io=False, mfma=0, wgrad=0, p16=1, p16w=1, wino=False, k=3, s=1, pads=None, b=2, ci=8,
+                   co=16, bias=True, res=False, slope=0.1, x16=False, sliced=False, g32=False, need="xwbr", fused=True, then=None)
+_LAYER_SWITCHES = dict(store="STORE_HALF", io="HALF_IO", mfma="MFMA16", wgrad="MFMA16_WGRAD", fused="FUSED_ACT_BIAS")
+
+
+def _layer_cases():
+    bf16, fp16 = "bfloat16", "float16"
+    full = [dict()] + [dict(amp=bf16, io=io, mfma=m, wgrad=g) for io, m, g in
+                       ((False, 0, 0), (True, 0, 0), (True, 1, 0), (True, 2, 0), (True, 1, 1), (True, 1, 2), (True, 2, 1), (True, 2, 2))] + \
+        [dict(amp=fp16, io=io, mfma=m, wgrad=g) for io, m, g in ((False, 0, 0), (True, 0, 0), (True, 2, 0), (True, 2, 2))]
+    few = [full[0], full[1], full[2], full[4], full[5], full[8], full[12]]
+    shapes = [dict(k=1), dict(k=3), dict(k=3, wino=True), dict(k=1, s=2), dict(k=3, s=2), dict(k=3, pads=(1, 0, 1, 2)), dict(k=3, s=2, pads=(0, 0, 1, 1))]
+    for prec in full:       # precision x shape x STORE_HALF (16 x 16 maps: 4096 elements, what _stash narrows) x arriving dtype
+        for shape in shapes:
+            for store in (False, True):
+                for x16 in ((False, True) if prec.get("io") else (False,)):
+                    yield dict(prec, **shape, store=store, x16=x16)
+    variants = [dict(p16=0), dict(p16="fwd"), dict(p16w=0), dict(wino=True, res=True, bias=False),
+                dict(co=6), dict(co=6, fused=False), dict(b=0), dict(b=0, need="w"),
+                dict(bias=False), dict(res=True), dict(slope=None), dict(bias=False, res=True, slope=None), dict(bias=False, slope=None),
+                dict(sliced=True), dict(sliced=True, res=True), dict(g32=True), dict(g32=True, slope=None, bias=False),
+                dict(need="x"), dict(need="w"), dict(need="xwr", res=True), dict(need="wb"), dict(need="r", res=True),
+                dict(fused=False), dict(fused=False, slope=None), dict(fused=False, bias=False),
+                dict(then=dict(mfma=0)), dict(then=dict(wgrad=0)), dict(then=dict(mfma=2, wgrad=2)), dict(then=dict(fused=False))]
+    for prec in few:        # every other axis, one or two at a time, where it can change a branch
+        for shape in (shapes[0], shapes[1], shapes[4], shapes[5]):
+            for var in variants:
+                for x16 in ((False, True) if prec.get("io") else (False,)):
+                    if var.get("sliced") and not x16 and prec.get("io"):   # (an fp32 slice is repacked by the cast: aligned)
+                        continue
+                    yield dict(prec, **shape, **var, store=bool(prec.get("mfma")), x16=x16)
+
+
+def _layer_trace(stub, monkeypatch, case):
+    from simplerecon_amd import autograd_ops
+    c = dict(_LAYER_CASE, **case)
+    amp = getattr(torch, c["amp"]) if c["amp"] else None
+    monkeypatch.setattr(torch, "is_autocast_enabled", lambda *a: amp is not None)
+    monkeypatch.setattr(torch, "get_autocast_dtype", lambda *a: amp or torch.float16)
+    for key, name in _LAYER_SWITCHES.items():
+        monkeypatch.setattr(autograd_ops, name, c[key])
+    k, s, b, ci, co, h, w = c["k"], c["s"], c["b"], c["ci"], c["co"], 16, 16
+    layer = (b, h, w, ci, co, k, s)
+    stub.prefer16, stub.prefer16_wgrad, stub.prefer_wino = {layer} if c["p16"] == "fwd" else c["p16"], c["p16w"], c["wino"]
+    pt, pl, pb, pr = c["pads"] or (k // 2,) * 4
+    ho, wo = (h + pt + pb - k) // s + 1, (w + pl + pr - k) // s + 1
+    dt = amp if c["x16"] else torch.float32
+    x = torch.zeros(b, h, w, ci + 3, dtype=dt)[..., 1:1 + ci].permute(0, 3, 1, 2) if c["sliced"] else \
+        torch.zeros(b, ci, h, w, dtype=dt).contiguous(memory_format=torch.channels_last)
+    ins = dict(x=x.detach(), w=torch.zeros(co, ci, k, k), b=torch.zeros(co) if c["bias"] else None,
+               r=torch.zeros(b, co, ho, wo, dtype=dt).contiguous(memory_format=torch.channels_last) if c["res"] else None)
+    for name, t in ins.items():
+        if t is not None:
+            t.requires_grad_(name in c["need"])
+    trace = {}
+    pinned = lambda: [_pinned_call(n, a) for n, a in stub.args if not n.endswith(_QUERIES)]
+    describe = lambda t: None if t is None else [str(t.dtype), list(t.shape), list(t.stride())]
+    del stub[:], stub.args[:]
+    try:
+        out = autograd_ops._ConvBiasAct.apply(ins["x"], ins["w"], ins["b"], ins["r"], s, c["slope"], c["pads"])
+        trace["forward"] = pinned()
+        trace["out"] = describe(out)
+        trace["saved"] = [None if t is None else str(t.dtype) for t in out.grad_fn.saved_tensors]
+        for key, value in (c["then"] or {}).items():
+            monkeypatch.setattr(autograd_ops, _LAYER_SWITCHES[key], value)
+        del stub[:], stub.args[:]
+        if c["g32"]:
+            g = torch.zeros(out.shape).contiguous(memory_format=torch.channels_last)
+            grads = dict(zip("xwbr", autograd_ops._ConvBiasAct.backward(out.grad_fn, g)))
+        else:
+            wanted = [n for n, t in ins.items() if t is not None and t.requires_grad]
+            grads = dict(zip(wanted, torch.autograd.grad(out.sum(), [ins[n] for n in wanted], allow_unused=True)))
+        trace["backward"] = pinned()
+        trace["grads"] = {n: describe(grads.get(n)) for n in "xwbr"}
+    except (ValueError, TypeError, RuntimeError, _lib.HipLibraryError) as e:
+        trace["raises"] = f"{type(e).__name__}: {e}"
+    return trace
+
+
+def _layer_traces(stub, monkeypatch):
+    from simplerecon_amd import autograd_ops
+
+    def nhwc_any(t, name):   # autograd_ops._nhwc_any without its CUDA-device check
+        return t if autograd_ops._is_nhwc_view(t) else t.contiguous(memory_format=torch.channels_last)
+    monkeypatch.setattr(autograd_ops, "_nhwc_any", nhwc_any)
+    # (the layer's wrappers leave an autocast-off region: that writes back the patched state it read on the way in)
+    real = torch.is_autocast_enabled("cuda"), torch.get_autocast_dtype("cuda")
+    traces = {}
+    try:
+        for case in _layer_cases():
+            cid = ",".join(f"{k}={v}" for k, v in case.items() if v != _LAYER_CASE[k]) or "default"
+            assert cid not in traces, cid
+            traces[cid] = _layer_trace(stub, monkeypatch, case)
+    finally:
+        torch.set_autocast_enabled("cuda", real[0])
+        torch.set_autocast_dtype("cuda", real[1])
+    return json.loads(json.dumps(traces))
+
+
+def test_conv_layer_launch_trace_matches_the_golden(stub, monkeypatch):
+    """_ConvBiasAct launches the same kernels with the same arguments, saves the same dtypes and returns gradients of the same
+    dtype, shape and strides as recorded in tests/golden/conv_layer_trace.json.gz."""
+    got = _layer_traces(stub, monkeypatch)
+    with gzip.open(_GOLDEN_LAYER, "rt") as f:
         want = json.load(f)
     assert sorted(got) == sorted(want)
     for cid in want:
