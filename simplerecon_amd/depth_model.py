@@ -24,7 +24,7 @@ from .cost_volume import CostVolumeManager, FeatureVolumeManager
 from .layers import TensorFormatter
 from . import autograd_ops, ops
 from .image_encoder import EfficientNetV2SFeatures
-from .networks import CVEncoder, DepthDecoderPP, ResnetMatchingEncoder
+from .networks import CVEncoder, DepthDecoderPP, LazyLevels, ResnetMatchingEncoder
 
 
 @dataclass
@@ -72,33 +72,20 @@ class PendingPyramid:
         return self.feats
 
     def levels_from(self, first):
-        """Levels first.. as a sequence whose items join only as much of the encoder as produced them (r06): at batch 1
+        """Levels first.. as a LazyLevels whose items join only as much of the encoder as produced them (r06): at batch 1
         the encoder's ~200 small launches outlast matching encoder + sweep, and the first CVEncoder levels need only the
-        shallow pyramid levels -- they run while stages 5 / 6 of the encoder are still in flight."""
-        return _PendingLevels(self, first)
-
-
-class _PendingLevels:
-    def __init__(self, pending, first):
-        self.pending, self.first = pending, first
-
-    def __len__(self):
-        return len(self.pending.feats) - self.first
-
-    def peek(self):
-        """The tensors without any stream join (shapes / requires_grad checks only -- not for launching work on them)."""
-        return self.pending.feats[self.first:]
-
-    def __getitem__(self, i):
-        p = self.pending
-        if isinstance(i, slice) or i < 0:
-            raise TypeError("pending pyramid levels are taken one at a time, by non-negative index")
-        lvl = self.first + i
-        if p.events is None:
-            p.wait()
-        else:
-            torch.cuda.current_stream(p.feats[lvl].device).wait_event(p.events[lvl])
-        return p.feats[lvl]
+        shallow pyramid levels -- they run while stages 5 / 6 of the encoder are still in flight.  Without per-level events
+        an item is the full join."""
+        def level(lvl):
+            def join():
+                if self.events is None:
+                    self.wait()
+                else:
+                    torch.cuda.current_stream(self.feats[lvl].device).wait_event(self.events[lvl])
+                return self.feats[lvl]
+            join.tensor = self.feats[lvl]
+            return join
+        return LazyLevels(level(lvl) for lvl in range(first, len(self.feats)))
 
 
 def tensor_B_to_bM(t, batch_size, num_views):
@@ -304,25 +291,21 @@ class DepthModel(nn.Module):
             max_depth=max_depth, return_mask=return_mask, **({"reserve_cus": reserve} if reserve else {}))
         if flip:
             cost_volume = torch.flip(cost_volume, (-1,))
-        if isinstance(cur_feats, PendingPyramid) and isinstance(self.cost_volume_net, CVEncoder) \
-                and isinstance(self.depth_decoder, DepthDecoderPP):
-            # CVEncoder level i joins the encoder's side stream only as far as pyramid level matching_scale + i, and its LAST level
-            # is handed to the decoder as a closure: the decoder first launches the branches of its first column that do not read
-            # it (the full-resolution convolutions among them), then calls it.  The full join (which a HIP-graph capture and the
-            # allocator both need) comes last, when the deepest level has been waited for anyway.
-            pending = cur_feats
-            cost_volume_features, last_level = self.cost_volume_net(cost_volume, pending.levels_from(o.matching_scale),
-                                                                    defer_last=True)
-            shallow = pending.levels_from(0)
-            feats = [shallow[k] for k in range(o.matching_scale)] + cost_volume_features
-            depth_outputs = self.depth_decoder(feats, last_input=last_level)
+        # A pending pyramid goes to the project's own CVEncoder / DepthDecoderPP as LazyLevels: CVEncoder level i joins the encoder's
+        # side stream only as far as pyramid level matching_scale + i, and leaves its LAST level unresolved: the decoder first
+        # launches the branches of its first column that do not read it (the full-resolution convolutions among them), then
+        # resolves it.  The full join (which a HIP-graph capture and the allocator both need) comes last, when the deepest level
+        # has been waited for anyway.  Plugged-in modules get a resolved list.
+        pending = cur_feats if isinstance(cur_feats, PendingPyramid) else None
+        lazy = pending is not None and isinstance(self.cost_volume_net, CVEncoder) \
+            and isinstance(self.depth_decoder, DepthDecoderPP)
+        if pending is not None:
+            cur_feats = pending.levels_from(0) if lazy else pending.wait()
+        cost_volume_features = self.cost_volume_net(cost_volume, cur_feats[o.matching_scale:],
+                                                    **({"defer_last": True} if lazy else {}))
+        depth_outputs = self.depth_decoder(list(cur_feats[:o.matching_scale]) + cost_volume_features)
+        if lazy:
             pending.wait()
-        else:
-            if isinstance(cur_feats, PendingPyramid):
-                cur_feats = cur_feats.wait()
-            cost_volume_features = self.cost_volume_net(cost_volume, cur_feats[o.matching_scale:])
-            feats = list(cur_feats[:o.matching_scale]) + cost_volume_features
-            depth_outputs = self.depth_decoder(feats)
         for k in list(depth_outputs.keys()):
             log_depth = depth_outputs[k].float()
             if flip:

@@ -50,6 +50,46 @@ class MLP(nn.Module):
         return x
 
 
+class LazyLevels:
+    """A sequence of feature levels, each a tensor or a zero-argument callable that yields it -- a stream join (DepthModel's
+    pending image-prior pyramid) or launches held back (CVEncoder's deferred last level).  `levels[i]` resolves a callable on
+    first use and keeps the tensor; slices and sums are LazyLevels over the SAME items and resolve nothing, so a level is
+    resolved once whoever asks first.  Indices are a list's, negative ones included.  A callable may carry the tensor it will
+    yield as its `tensor` attribute, for peek()."""
+
+    def __init__(self, items=(), cells=None):
+        self._cells = [[x] for x in items] if cells is None else cells   # one shared cell per level
+
+    @classmethod
+    def of(cls, levels):
+        return levels if isinstance(levels, cls) else cls(levels)
+
+    def __len__(self):
+        return len(self._cells)
+
+    def __getitem__(self, i):
+        if isinstance(i, slice):
+            return LazyLevels(cells=self._cells[i])
+        cell = self._cells[i]
+        if callable(cell[0]):
+            cell[0] = cell[0]()
+        return cell[0]
+
+    def __add__(self, other):
+        return LazyLevels(cells=self._cells + LazyLevels.of(other)._cells)
+
+    def __radd__(self, other):
+        return LazyLevels.of(other) + self
+
+    def unresolved(self, i):
+        return callable(self._cells[i][0])
+
+    def peek(self):
+        """The levels as far as their tensors are known (None otherwise), resolving nothing: for shapes, channel counts and
+        requires_grad -- an unresolved level's tensor is not yet safe to launch work on."""
+        return [getattr(x, "tensor", None) if callable(x) else x for x, in self._cells]
+
+
 class CVEncoder(nn.Module):
     """Cost-volume + image-prior multi-scale encoder (reference networks.py:99-127)."""
 
@@ -80,17 +120,16 @@ class CVEncoder(nn.Module):
         return outputs
 
     def forward(self, x, img_feats, defer_last=False):
-        """defer_last=True (inference only): returns (outputs of levels 0 .. n-2, finish) where `finish()` -> the last level's
-        output.  ds_conv of the last level is already launched; `finish` takes the deepest image-prior level (a stream join when
-        the pyramid is still pending) and runs the two blocks that need it.  DepthModel hands `finish` to the decoder, which
-        first launches everything that does not depend on it."""
+        """Returns the `num_blocks` levels as a LazyLevels.  defer_last=True (inference only) leaves the last one unresolved:
+        its ds_conv is already launched; resolving it takes the deepest image-prior level and runs the two blocks that need it.
+        DepthDecoderPP first launches everything that does not depend on it."""
         from . import autograd_ops, ops
-        # `img_feats` may be DepthModel's pending pyramid (depth_model._PendingLevels): item i then joins the image-prior encoder's
-        # side stream just far enough for level i -- taken AFTER ds_conv_i has been launched, which does not need it
-        peek = img_feats.peek() if hasattr(img_feats, "peek") else list(img_feats)
-        if autograd_ops.grad_wanted(x, list(peek), self):
-            outs = self._forward_train(x, [img_feats[i] for i in range(len(peek))])
-            return (outs, None) if defer_last else outs
+        # `img_feats` may be DepthModel's pending pyramid: taking level i then joins the image-prior encoder's side stream just
+        # far enough for it -- AFTER ds_conv_i has been launched, which does not need it
+        img_feats = LazyLevels.of(img_feats)
+        peek = img_feats.peek()
+        if autograd_ops.grad_wanted(x, peek, self):
+            return LazyLevels(self._forward_train(x, list(img_feats)))
         outputs = []
         for i in range(self.num_blocks):
             ds = self.convs[f"ds_conv_{i}"]
@@ -103,11 +142,9 @@ class CVEncoder(nn.Module):
             def finish(i=i, buf=buf, c_out=c_out):
                 ops.copy_into(buf[:, c_out:], img_feats[i])
                 return self.convs[f"conv_{i}"][1](self.convs[f"conv_{i}"][0](buf))
-            if defer_last and i == self.num_blocks - 1:
-                return outputs, finish
-            x = finish()
+            x = finish if defer_last and i == self.num_blocks - 1 else finish()
             outputs.append(x)
-        return (outputs, None) if defer_last else outputs
+        return LazyLevels(outputs)
 
 
 _SIDE_STREAMS = {}  # device -> (stream, stream) for DepthDecoderPP's branch parallelism
@@ -149,12 +186,18 @@ class DepthDecoderPP(nn.Module):
                 )
 
     # The three inputs of a node (right / diagonal / up branch) are independent BasicBlocks writing disjoint channel
-    # slices of the node's concat buffer.  At small batch a single conv launch leaves CUs idle (150-600 work items for
-    # 512 slots), so for batches <= `branch_stream_max_batch` the diagonal and up branches run on two side HIP
-    # streams and join before `in_conv`.  At batch 8 the 240x320 launches fill the chip and the fork / join only costs,
-    # but the nodes from 120x160 down (<= 1200 of the convs' 8x16-pixel regions for 512 workgroup slots, their diagonal
-    # / up branches a quarter of that) leave part of it idle: those fork at any batch (`branch_stream_max_regions`,
+    # slices of the node's concat buffer; `_launch_branches` launches any of them, and its order is the schedule:
+    #   forked    diagonal on side stream 1, up on side stream 2, then right on the main stream; `forward` joins the side
+    #             streams that were used before `in_conv`
+    #   in order  right, diagonal, up on the current stream
+    # A node forks (`_node_buffer`) at small batch, where a single conv launch leaves CUs idle (150-600 work items for
+    # 512 slots): batches <= `branch_stream_max_batch`.  At batch 8 the 240x320 launches fill the chip and the fork / join
+    # only costs, but the nodes from 120x160 down (<= 1200 of the convs' 8x16-pixel regions for 512 workgroup slots, their
+    # diagonal / up branches a quarter of that) leave part of it idle: those fork at any batch (`branch_stream_max_regions`,
     # 0 = off; measured r02 at batch 8: 32.3 -> 32.0 ms per step with 1300, nothing with 400, nothing more with 5000).
+    # When the deepest input is still unresolved, the first column's nodes that do not read it are launched in two calls:
+    # right / diagonal before it is resolved (forked or in order), the up branch afterwards in order -- by then nothing is
+    # left for the main stream to run beside it, so a third stream's fork / join would only cost.
     branch_stream_max_batch = 2
     branch_stream_max_regions = int(os.environ.get("SR_DECODER_FORK_REGIONS", "1300"))
 
@@ -185,85 +228,65 @@ class DepthDecoderPP(nn.Module):
             prev_outputs = outputs[::-1]
         return {k: depth_outputs[k] for k in sorted(depth_outputs, reverse=True)}
 
-    def forward(self, input_features, last_input=None):
-        """`last_input` (inference only): a callable returning the deepest input feature, when `input_features` holds all but that
-        one (CVEncoder.forward(defer_last=True)).  The first column then launches the right / diagonal branches of the nodes that do
-        not read it BEFORE calling it -- the call may join the image-prior encoder's stream, and those branches (the full-resolution
-        convolutions among them) run while the encoder finishes.  Same launches, same inputs: the result does not change."""
+    def _node_buffer(self, i, j, x, streams):
+        """(concat buffer of node (i, j), whose right input is `x`; the streams its branches fork over, or None: in order)."""
+        from . import ops
+        b, _, h, w = x.shape
+        buf = ops.empty_nhwc(b, int(self.num_ch_dec[i]) * (3 if i + j != 4 else 2), h, w, x.device)
+        regions = b * ((h + 7) // 8) * ((w + 15) // 16)
+        fork = streams is not None and (b <= self.branch_stream_max_batch or regions <= self.branch_stream_max_regions)
+        return buf, streams if fork else None
+
+    def _launch_branches(self, i, j, buf, right=None, diag=None, up=None, fork=None):
+        """Launches the branches of node (i, j) whose inputs are given, each into its channel slice of `buf`.  `fork` = (main,
+        side 1, side 2): diagonal and up go out first, on their side streams behind the main stream's work so far, and are
+        in flight beside the right branch; None: right, diagonal, up on the current stream.  Returns the side streams used."""
+        from . import ops
+        c = int(self.num_ch_dec[i])
+        upsampled = [(name, x, k) for k, name, x in ((1, f"diag_conv_{i + 1}{j - 1}", diag), (2, f"up_conv_{i + 1}{j}", up))
+                     if x is not None]
+        for name, x, k in upsampled if fork else ():   # branch k on side stream k
+            fork[k].wait_stream(fork[0])
+            with torch.cuda.stream(fork[k]):
+                ops.upsample2x(self.convs[name](x), out=buf[:, k * c:(k + 1) * c])
+        if right is not None:
+            self.convs[f"right_conv_{i}{j - 1}"](right, out=buf[:, :c])
+        for name, x, k in () if fork else upsampled:
+            ops.upsample2x(self.convs[name](x), out=buf[:, k * c:(k + 1) * c])
+        return [fork[k] for _, _, k in upsampled] if fork else []
+
+    def forward(self, input_features):
+        """`input_features` may be a LazyLevels.  With a gradient wanted, everything is resolved for `_forward_train`.  Otherwise,
+        when the deepest level is still unresolved (CVEncoder.forward(defer_last=True)), the first column launches the right /
+        diagonal branches of the nodes that do not read it BEFORE resolving it -- that may join the image-prior encoder's stream,
+        and those branches (the full-resolution convolutions among them) run while the encoder finishes.  Same launches, same
+        inputs: the result does not change."""
         from . import autograd_ops, ops
-        if last_input is not None and autograd_ops.grad_wanted(list(input_features), self):
-            input_features, last_input = list(input_features) + [last_input()], None
-        if last_input is None and autograd_ops.grad_wanted(list(input_features), self):
-            return self._forward_train(input_features)
-        prev_outputs = list(input_features)
+        feats = LazyLevels.of(input_features)
+        if autograd_ops.grad_wanted(feats.peek(), self):
+            return self._forward_train(list(feats))
+        prev_outputs = list(feats[:-1])
         outputs = []
         depth_outputs = {}
         dev = prev_outputs[0].device
-        small_batch = dev.type == "cuda" and prev_outputs[0].shape[0] <= self.branch_stream_max_batch
-        if dev.type == "cuda":
-            main = torch.cuda.current_stream(dev)
-            s1, s2 = self._side_streams(dev)
-        early = {}   # node i of column 1 -> (buf, fork) whose right / diagonal branches are already launched
-        if last_input is not None:
-            for i in range(2, -1, -1):
-                right = self.convs[f"right_conv_{i}0"]
-                c = right.conv2.out_channels
-                x_i = prev_outputs[i]
-                buf = ops.empty_nhwc(x_i.shape[0], c * 3, x_i.shape[2], x_i.shape[3], x_i.device)
-                regions = x_i.shape[0] * ((x_i.shape[2] + 7) // 8) * ((x_i.shape[3] + 15) // 16)
-                fork = small_batch or (dev.type == "cuda" and regions <= self.branch_stream_max_regions)
-                diag = self.convs[f"diag_conv_{i + 1}0"]
-                if fork:
-                    s1.wait_stream(main)
-                    with torch.cuda.stream(s1):
-                        ops.upsample2x(diag(prev_outputs[i + 1]), out=buf[:, c:2 * c])
-                    right(x_i, out=buf[:, :c])
-                else:
-                    right(x_i, out=buf[:, :c])
-                    ops.upsample2x(diag(prev_outputs[i + 1]), out=buf[:, c:2 * c])
-                early[i] = (buf, fork)
-            prev_outputs.append(last_input())
+        streams = (torch.cuda.current_stream(dev), *self._side_streams(dev)) if dev.type == "cuda" else None
+        early = {}   # node i of column 1 -> (buf, side streams used) whose right / diagonal branches are already launched
+        if feats.unresolved(-1):
+            for i in range(len(prev_outputs) - 2, -1, -1):
+                buf, fork = self._node_buffer(i, 1, prev_outputs[i], streams)
+                early[i] = buf, self._launch_branches(i, 1, buf, prev_outputs[i], prev_outputs[i + 1], fork=fork)
+        prev_outputs.append(feats[-1])
         for j in range(1, 5):
-            max_i = 4 - j
-            for i in range(max_i, -1, -1):
-                right = self.convs[f"right_conv_{i}{j - 1}"]
-                diag = self.convs[f"diag_conv_{i + 1}{j - 1}"]
-                c = right.conv2.out_channels
-                x_i = prev_outputs[i]
-                n_parts = 3 if i + j != 4 else 2
-                if j == 1 and i in early:
-                    # right / diagonal branches are in flight (or done): nothing is left for this stream to run beside the up
-                    # branch, so it runs here (no fork / join of a third stream), then the join of the diagonal branch
-                    buf, fork = early.pop(i)
-                    up = self.convs[f"up_conv_{i + 1}{j}"]
-                    ops.upsample2x(up(outputs[-1]), out=buf[:, 2 * c:3 * c])
-                    if fork:
-                        main.wait_stream(s1)
-                    in_conv = self.convs[f"in_conv_{i}{j}"]
-                    output = in_conv[1](in_conv[0](buf))
-                    outputs.append(output)
-                    continue
-                buf = ops.empty_nhwc(x_i.shape[0], c * n_parts, x_i.shape[2], x_i.shape[3], x_i.device)
-                regions = x_i.shape[0] * ((x_i.shape[2] + 7) // 8) * ((x_i.shape[3] + 15) // 16)
-                fork = small_batch or (dev.type == "cuda" and regions <= self.branch_stream_max_regions)
-                if fork:
-                    s1.wait_stream(main)
-                    with torch.cuda.stream(s1):
-                        ops.upsample2x(diag(prev_outputs[i + 1]), out=buf[:, c:2 * c])
-                    if i + j != 4:
-                        s2.wait_stream(main)
-                        with torch.cuda.stream(s2):
-                            ops.upsample2x(self.convs[f"up_conv_{i + 1}{j}"](outputs[-1]), out=buf[:, 2 * c:3 * c])
-                    right(x_i, out=buf[:, :c])
-                    main.wait_stream(s1)
-                    if i + j != 4:
-                        main.wait_stream(s2)
+            for i in range(4 - j, -1, -1):
+                up = outputs[-1] if i + j != 4 else None
+                if i in early:
+                    buf, used = early.pop(i)
+                    self._launch_branches(i, j, buf, up=up)
                 else:
-                    right(x_i, out=buf[:, :c])
-                    ops.upsample2x(diag(prev_outputs[i + 1]), out=buf[:, c:2 * c])
-                    if i + j != 4:
-                        up = self.convs[f"up_conv_{i + 1}{j}"]
-                        ops.upsample2x(up(outputs[-1]), out=buf[:, 2 * c:3 * c])
+                    buf, fork = self._node_buffer(i, j, prev_outputs[i], streams)
+                    used = self._launch_branches(i, j, buf, prev_outputs[i], prev_outputs[i + 1], up, fork)
+                for side in used:
+                    streams[0].wait_stream(side)
                 in_conv = self.convs[f"in_conv_{i}{j}"]
                 output = in_conv[1](in_conv[0](buf))
                 outputs.append(output)

@@ -244,6 +244,47 @@ def test_sweep_reserve_rule():
     assert model._sweep_reserve(pending, one) == 0
 
 
+def test_lazy_levels():
+    """networks.LazyLevels, the one lazy sequence of the inference schedule: a callable item is resolved on first use and
+    kept; slices and sums share the items and resolve nothing, nor do peek() and unresolved(); indices are a list's."""
+    from simplerecon_amd import depth_model as dm
+    from simplerecon_amd.networks import LazyLevels
+    t = [torch.full((1,), float(i)) for i in range(4)]
+    calls = []
+
+    def later(i, known=True):
+        def resolve():
+            calls.append(i)
+            return t[i]
+        if known:
+            resolve.tensor = t[i]
+        return resolve
+    levels = LazyLevels([t[0], later(1), later(2), later(3, known=False)])
+    assert len(levels) == 4 and LazyLevels.of(levels) is levels and len(LazyLevels.of(t)) == 4
+    peek = levels.peek()
+    assert all(a is b for a, b in zip(peek, t[:3])) and peek[3] is None
+    tail, both = levels[1:], [t[0]] + levels[2:] + [t[1]]
+    assert isinstance(tail, LazyLevels) and isinstance(both, LazyLevels) and (len(tail), len(both)) == (3, 4)
+    assert [levels.unresolved(i) for i in range(4)] == [False, True, True, True] and tail.unresolved(-1) and calls == []
+    assert tail[1] is t[2] and calls == [2]              # resolved through the slice ...
+    assert levels[2] is t[2] and both[1] is t[2] and calls == [2]   # ... once, for every view of the same items
+    assert not levels.unresolved(2) and levels.unresolved(1) and levels.peek()[2] is t[2]
+    assert levels[-1] is t[3] and levels[-4] is t[0] and calls == [2, 3]
+    assert [x is y for x, y in zip(levels, t)] == [True] * 4 and calls == [2, 3, 1]   # iterating resolves the rest, in order
+    for bad in (4, -5):
+        with pytest.raises(IndexError):
+            levels[bad]
+        with pytest.raises(IndexError):
+            levels.unresolved(bad)
+    with pytest.raises(TypeError):
+        levels["0"]
+    # a pending pyramid's levels are such a sequence: reference-style slicing works and joins nothing
+    feats = [torch.empty(0)] * 5
+    rest = dm.PendingPyramid(None, feats).levels_from(1)[1:]
+    assert isinstance(rest, LazyLevels) and len(rest) == 3 and all(rest.unresolved(i) for i in range(3))
+    assert all(p is f for p, f in zip(rest.peek(), feats))
+
+
 def test_autocast_region_upcasts_half_features(stub):
     """Reference training runs under 16-bit autocast (options.py:100-101): inside an autocast region half-precision
     matching features are upcast to fp32 for the HIP kernels and the gradients come back in the caller's dtype."""
