@@ -1480,6 +1480,61 @@ int sr_adamw_step(const void* p_ptrs, const void* g_ptrs, const void* m_ptrs, co
                   int num_chunks, const double* groups_host, int num_groups, const float* grad_scale,
                   const float* found_inf, void* stream);
 
+/* sr_adamw_step_clipped: sr_adamw_step with one more optional device scalar, grad_coef (fp32, 4-byte aligned, or NULL):
+ * after `g = grad / grad_scale` the kernel computes `g = g * *grad_coef`, rounded separately, in registers.  One kernel
+ * body serves both entry points: sr_adamw_step forwards with grad_coef = NULL, and a coefficient of exactly 1.0f changes
+ * no bit of any result.
+ *
+ * sr_grad_stats: gradient norms, the non-finite flag, torch's clip coefficient and (optionally) the loss scaler's update,
+ * in two launches over the tables of sr_adamw_step (g_ptrs, numel, chunk_start, num_tensors, num_chunks).  Gradients are
+ * only read.
+ *   Launch 1, one 256-lane workgroup per chunk: every element is converted to DOUBLE, squared and added; a fixed-order
+ *   wave and LDS reduction writes one double per chunk into the workspace (0 for a tensor whose address is 0).  16-byte
+ *   loads for 16-byte aligned tensors, single floats for the numel % 4 tail and for every other tensor.
+ *   Launch 2, one workgroup: per tensor the sum of its partials in chunk order, then the sum over the tensors in index
+ *   order; no atomics, so two runs give the same bytes.  With s = *grad_scale (or *scaler_scale, or 1 without either)
+ *   it writes, all fp32:
+ *     norms[t]                        sqrt(sum_t) / s, computed in double and rounded once: the norm of the UNSCALED gradient
+ *     stats[SR_GRAD_STATS_NORM]       the same over all tensors
+ *     stats[SR_GRAD_STATS_FOUND_INF]  1.0 when the total sum is not finite, else 0.0
+ *     stats[SR_GRAD_STATS_COEF]       max_norm > 0: q = max_norm / (norm + 1e-6f) in fp32, each operation rounded, then
+ *                                     q > 1 ? 1 : q (torch.nn.utils.clip_grad_norm_; a NaN stays); otherwise 1.0
+ *     stats[SR_GRAD_STATS_SCALE]      s, the scale of THIS step: what sr_adamw_step_clipped divides by when the scaler's
+ *                                     own slot is updated in the same launch
+ *   The flag is equivalent to "some element is not finite": the square of a finite fp32 value is below 2^256 and a sum
+ *   of fewer than 2^31 of them is finite in double, while inf and NaN carry through the square and every addition of
+ *   non-negative terms.  Double also keeps gradients of 1e30 or 1e-30, whose squares leave the fp32 range, and makes the
+ *   sum independent of the order to 2^-26 relatively, far below fp32 resolution.
+ *   scaler_scale (fp32) / scaler_tracker (int32), both or neither, and not together with grad_scale: torch's
+ *   _amp_update_scale_ at the end of launch 2.  Flag set: scale = float(scale * backoff_factor), tracker = 0.  Otherwise
+ *   tracker += 1, and when it reaches growth_interval: scale = float(scale * growth_factor) if that is finite, tracker = 0.
+ * workspace: sr_grad_stats_workspace_bytes(num_chunks, num_tensors) bytes, 8-byte aligned; every byte a launch reads was
+ * written by launch 1 of the same call.
+ *
+ * sr_grad_scale_inplace: g[i] = g[i] * *coef for every element of every tensor with a gradient, one launch over the same
+ * chunk table (the in-place half of torch's clip_grad_norm_, which always multiplies).
+ *
+ * SR_ERR_INVALID_ARGUMENT: a NULL or misaligned table, output or scalar, num_tensors < 1, num_chunks < 0, a NaN max_norm,
+ * one scaler pointer without the other or together with grad_scale, a factor that is not positive, growth_interval < 1.
+ * SR_ERR_UNSUPPORTED: num_tensors above SR_ADAMW_MAX_TENSORS.  SR_ERR_WORKSPACE_TOO_SMALL.  No call allocates or
+ * synchronises with the host. */
+#define SR_GRAD_STATS_NORM 0
+#define SR_GRAD_STATS_FOUND_INF 1
+#define SR_GRAD_STATS_COEF 2
+#define SR_GRAD_STATS_SCALE 3
+#define SR_GRAD_STATS_SLOTS 4
+int sr_adamw_step_clipped(const void* p_ptrs, const void* g_ptrs, const void* m_ptrs, const void* v_ptrs,
+                          const int64_t* numel, const int32_t* chunk_start, const int32_t* group, float* steps,
+                          float* scalars, int num_tensors, int num_chunks, const double* groups_host, int num_groups,
+                          const float* grad_scale, const float* found_inf, const float* grad_coef, void* stream);
+size_t sr_grad_stats_workspace_bytes(int num_chunks, int num_tensors);
+int sr_grad_stats(const void* g_ptrs, const int64_t* numel, const int32_t* chunk_start, int num_tensors, int num_chunks,
+                  const float* grad_scale, float max_norm, float* norms, float* stats, float* scaler_scale,
+                  int32_t* scaler_tracker, double growth_factor, double backoff_factor, int growth_interval,
+                  void* workspace, size_t workspace_bytes, void* stream);
+int sr_grad_scale_inplace(const void* g_ptrs, const int64_t* numel, const int32_t* chunk_start, int num_tensors,
+                          int num_chunks, const float* coef, void* stream);
+
 #ifdef __cplusplus
 }
 #endif

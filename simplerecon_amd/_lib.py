@@ -223,6 +223,10 @@ SIGNATURES = {
     "sr_viz_colormap": (_i, [_p, _p, _i, _i, _i64, _p, _p, _i64, _p, _i64, _f, _f, _f, _f, _f, _p, _p, _p]),
     "sr_viz_unit": (_i, [_p, _i, _i64, _i, _p, _p, _p]),
     "sr_adamw_step": (_i, [_p, _p, _p, _p, _p, _p, _p, _p, _p, _i, _i, _p, _i, _p, _p, _p]),
+    "sr_adamw_step_clipped": (_i, [_p, _p, _p, _p, _p, _p, _p, _p, _p, _i, _i, _p, _i, _p, _p, _p, _p]),
+    "sr_grad_stats_workspace_bytes": (_sz, [_i, _i]),
+    "sr_grad_stats": (_i, [_p, _p, _p, _i, _i, _p, _f, _p, _p, _p, _p, C.c_double, C.c_double, _i, _p, _sz, _p]),
+    "sr_grad_scale_inplace": (_i, [_p, _p, _p, _i, _i, _p, _p]),
 }
 
 

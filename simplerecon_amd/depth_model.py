@@ -47,6 +47,7 @@ class Options:
     lr: float = 1e-4                      # options.py:82-104: AdamW, stepped schedule (configure_optimizers)
     wd: float = 1e-4
     lr_steps: tuple = (70000, 80000)
+    clip_grad_norm: float = 0.0           # not a reference option: Lightning's gradient_clip_val, which the reference leaves at 0
 
 
 def default_options(**kw):
@@ -405,7 +406,9 @@ class DepthModel(nn.Module):
         from . import optim, training
         opts = self.run_opts
         lr_steps = tuple(getattr(opts, "lr_steps", training.DEFAULT_LR_STEPS))
-        optimizer = optim.AdamW(self.parameters(), lr=getattr(opts, "lr", 1e-4), weight_decay=getattr(opts, "wd", 1e-4))
+        clip = float(getattr(opts, "clip_grad_norm", 0.0) or 0.0)    # global L2 norm inside the step when positive
+        optimizer = optim.AdamW(self.parameters(), lr=getattr(opts, "lr", 1e-4), weight_decay=getattr(opts, "wd", 1e-4),
+                                max_grad_norm=clip if clip > 0.0 else None)
         lr_scheduler = torch.optim.lr_scheduler.LambdaLR(optimizer, lambda step: training.lr_factor(step, lr_steps))
         return {"optimizer": optimizer, "lr_scheduler": {"scheduler": lr_scheduler, "interval": "step"}}
 

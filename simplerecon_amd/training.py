@@ -7,8 +7,11 @@ Lightning, logging or checkpoint I/O.
     for batch in loader:
         loss = training.train_step(model, batch, opt, sched)        # a 0-dim device tensor: no host synchronisation
 
-Not provided: gradient clipping and norms, a loss scaler of our own (torch.amp.GradScaler is used as it is), HIP-graph
-capture of the step."""
+Gradient clipping is the optimiser's (Options.clip_grad_norm -> optim.AdamW(max_grad_norm=...)); after a step
+`optimizer.grad_norm` holds the global gradient norm on the device, for an on_step callback to read.  The scaler is a
+torch.amp.GradScaler or an optim.LossScaler (inf check, unscale and scale update inside the optimiser's four launches).
+
+Not provided: HIP-graph capture of the step."""
 import contextlib
 
 import torch
@@ -31,8 +34,8 @@ def train_step(model, batch, optimizer, scheduler=None, scaler=None, autocast_dt
 
     autocast_dtype: torch.float16 / torch.bfloat16 runs forward and backward inside torch.autocast; mfma16 (1 or 2, with an
     autocast_dtype) adds experimental.autocast_mfma16(mode=mfma16) around both, as the data gradient reads the switch.
-    scaler: a torch.amp.GradScaler (fp16 needs one): the loss is scaled, the step goes through scaler.step, which hands
-    optim.AdamW the scale and the found-inf flag on the device, then scaler.update()."""
+    scaler: a torch.amp.GradScaler or an optim.LossScaler (fp16 needs one): the loss is scaled, the step goes through
+    scaler.step, which hands optim.AdamW the scale and the found-inf flag on the device, then scaler.update()."""
     if mfma16 and autocast_dtype is None:
         raise ValueError("mfma16 needs an autocast_dtype (the 16-bit MFMA convolutions run under torch.autocast)")
     optimizer.zero_grad()
