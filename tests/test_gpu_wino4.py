@@ -77,6 +77,7 @@ def test_wino4_matches_fp64_and_the_other_kernels(shape):
     ed = (yd.double() - ref).abs().max().item() / scale
     print(f"{shape}: rel-to-range error F(4x4) {e4:.2e}  F(2x2) {e2:.2e}  direct {ed:.2e}")
     assert e4 < 2e-5, f"F(4x4) error {e4} (F(2x2) {e2}, direct {ed})"
+    assert e2 < 2e-5 and ed < 2e-5, f"the kernels F(4x4) is measured against: F(2x2) error {e2}, direct {ed}"
     assert torch.isfinite(y4).all()
     assert torch.equal(y4, y4b) and torch.equal(y4, y4c), "the kernel forms run the same operations in the same order"
 
@@ -108,6 +109,7 @@ def test_wino4_numerics_on_offset_and_heavy_tailed_inputs(family, shape):
     print(f"{family} {shape}: range-rel F(4x4) {e['w4'][0]:.2e} F(2x2) {e['w2'][0]:.2e} direct {e['direct'][0]:.2e}; "
           f"rms-rel {e['w4'][1]:.2e} / {e['w2'][1]:.2e} / {e['direct'][1]:.2e}")
     assert same, "the kernel forms run the same operations in the same order"
+    assert e["w2"][0] < 2e-5, f"F(2x2), the yardstick of the rms bound below: range-relative error {e['w2'][0]} on `{family}` inputs"
     assert e["w4"][0] < 2e-5, f"F(4x4) range-relative error {e['w4'][0]} on `{family}` inputs (F(2x2) {e['w2'][0]}, direct {e['direct'][0]})"
     assert e["w4"][1] < 40 * max(e["w2"][1], 1e-8), f"F(4x4) rms error {e['w4'][1]} vs F(2x2) {e['w2'][1]}"
 
