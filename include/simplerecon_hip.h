@@ -257,6 +257,19 @@ int sr_mlp_volume_fwd(const float* cur, const float* src, const float* K_src, co
                       int64_t cv_sb, int64_t cv_sd, int64_t cv_sp, float* out_lowest, uint8_t* out_mask,
                       int reserve_cus, void* workspace, size_t workspace_bytes, void* stream);
 
+/* sr_mlp_volume_fwd for features that are channels-last already, read where they lie: cur [B, h*w, 16] and
+ * src [B*K, h*w, 16], dense fp32 with 16-byte-aligned base addresses (SR_ERR_INVALID_ARGUMENT otherwise) -- the two slices
+ * of the matching encoder's one output buffer.  No copy of either operand is made; geometry records, weight packing,
+ * workspace size, every other argument and every bit of the results are those of sr_mlp_volume_fwd on the same features in
+ * [B,16,h,w] / [B,K,16,h,w] order.  SR_ERR_UNSUPPORTED under SR_MLP_SPLIT (that kernel reads cur planar). */
+int sr_mlp_volume_fwd_nhwc(const float* cur, const float* src, const float* K_src, const float* T_src_cur,
+                           const float* T_cur_src, const float* invK_cur, const float* planes, int64_t ps_b,
+                           int64_t ps_d, int64_t ps_y, int64_t ps_x, const float* W1, const float* b1,
+                           const float* W2, const float* b2, const float* W3, const float* b3, int hidden,
+                           float leaky_slope, int B, int K, int C, int h, int w, int D, float* out_cv,
+                           int64_t cv_sb, int64_t cv_sd, int64_t cv_sp, float* out_lowest, uint8_t* out_mask,
+                           int reserve_cus, void* workspace, size_t workspace_bytes, void* stream);
+
 /* ------------------------------------------------------------- 2-D conv stack -------
  *
  * Channels-last activations: element (b, y, x, c) of a tensor lives at

@@ -73,6 +73,8 @@ SIGNATURES = {
     "sr_mlp_volume_tile_shape": (_i, [_i, _i, C.POINTER(C.c_int), C.POINTER(C.c_int)]),
     "sr_mlp_volume_fwd": (_i, [_p, _p, _p, _p, _p, _p, _p, _i64, _i64, _i64, _i64, _p, _p, _p, _p, _p, _p, _i,
                                _f, _i, _i, _i, _i, _i, _i, _p, _i64, _i64, _i64, _p, _p, _i, _p, _sz, _p]),
+    "sr_mlp_volume_fwd_nhwc": (_i, [_p, _p, _p, _p, _p, _p, _p, _i64, _i64, _i64, _i64, _p, _p, _p, _p, _p, _p, _i,
+                                    _f, _i, _i, _i, _i, _i, _i, _p, _i64, _i64, _i64, _p, _p, _i, _p, _sz, _p]),
     "sr_conv_packed_weight_floats": (_sz, [_i, _i, _i]),
     "sr_conv_pack_weights": (_i, [_p, _i, _i, _i, _p, _p]),
     "sr_conv2d_nhwc_fwd": (_i, [_p, _i64, _i, _p, _p, _p, _i64, _i, _p, _i64, _i, _i, _i, _i, _i, _i, _i, _i, _f, _p]),

@@ -328,6 +328,23 @@ def mlp_input_channels(matching_dim_size, num_source_views):
     return c * (1 + k) + (1 + k) + 3 * (1 + k) + k + k + k + 3 * k
 
 
+def dense_channels_last_pair(cur_feats, src_feats):
+    """True when cur_feats [B,16,h,w] and src_feats [B,K,16,h,w] are fp32 views whose memory is [B][h*w][16] and
+    [B*K][h*w][16] -- channel stride 1, pixel stride 16, image stride h*w*16, 16-byte-aligned first element -- what
+    sr_mlp_volume_fwd_nhwc reads in place.  (The stride of a dimension of size 1 addresses nothing and is not looked at.)"""
+    if cur_feats.dim() != 4 or src_feats.dim() != 5 or cur_feats.dtype != torch.float32 or src_feats.dtype != torch.float32:
+        return False
+    b, k, c, h, w = src_feats.shape
+    if c != 16 or tuple(cur_feats.shape) != (b, c, h, w):
+        return False
+    n = h * w * c
+    want_cur, want_src = (n, 1, w * c, c), (k * n, n, 1, w * c, c)
+    return all(size == 1 or stride == want
+               for t, wants in ((cur_feats, want_cur), (src_feats, want_src))
+               for size, stride, want in zip(t.shape, t.stride(), wants)) and \
+        cur_feats.data_ptr() % 16 == 0 and src_feats.data_ptr() % 16 == 0
+
+
 def mlp_tile_shape(h, w):
     """(th, tw) of the 64 pixels one wave of the metadata-MLP sweep owns on an h x w map under the current SR_MLP_TILE, as
     the library answers it (sr_mlp_volume_tile_shape, include/simplerecon_hip.h); (1, 64) is the flattened strip."""
@@ -404,24 +421,31 @@ class FeatureVolumeManager(CostVolumeManager):
             raise ValueError(f"MLP expects {lin[0].in_features} input channels but {k} views x {c} channels "
                              f"give {mlp_input_channels(c, k)}")
         planes = self._planes(b, min_depth, max_depth, depth_planes_bdhw)
-        cur, src = cur_feats.contiguous(), src_feats.contiguous()
         Ks, T, Tp, invK = (src_Ks.contiguous(), src_extrinsics.contiguous(), src_poses.contiguous(),
                            cur_invK.contiguous())
         weights = (lin[0].weight, lin[0].bias, lin[1].weight, lin[1].bias, lin[2].weight, lin[2].bias)
         for i, t in enumerate(weights):
             _lib.require_device_f32(f"mlp parameter {i}", t)
         wants_grad = self.differentiable and torch.is_grad_enabled() and \
-            any(t.requires_grad for t in (cur, src) + weights)
+            any(t.requires_grad for t in (cur_feats, src_feats) + weights)
         if wants_grad:
             _lib.refuse_autograd(planes)
-            vol, lowest, mask = _MlpVolumeFunction.apply(self, bool(return_mask), cur, src, Ks, T, Tp, invK, planes,
+            vol, lowest, mask = _MlpVolumeFunction.apply(self, bool(return_mask), cur_feats.contiguous(),
+                                                         src_feats.contiguous(), Ks, T, Tp, invK, planes,
                                                          *[t.contiguous() for t in weights])
         else:
+            # The matching encoder hands over two slices of its one channels-last buffer: the sweep reads them where they
+            # lie.  Anything else is copied into [B,16,h,w] / [B,K,16,h,w] order, which the library packs back.
+            in_place = cur_feats.is_cuda and src_feats.is_cuda and dense_channels_last_pair(cur_feats, src_feats)
+            cur, src = (cur_feats, src_feats) if in_place else (cur_feats.contiguous(), src_feats.contiguous())
             vol, lowest, mask = self._launch_sweep(cur, src, Ks, T, Tp, invK, planes,
-                                                   [t.detach().contiguous() for t in weights], return_mask, reserve_cus)
+                                                   [t.detach().contiguous() for t in weights], return_mask, reserve_cus,
+                                                   in_place)
         return vol, lowest, planes, (mask.bool() if mask is not None else None)
 
-    def _launch_sweep(self, cur, src, Ks, T, Tp, invK, planes, params, return_mask, reserve_cus=0):
+    def _launch_sweep(self, cur, src, Ks, T, Tp, invK, planes, params, return_mask, reserve_cus=0, in_place=False):
+        """`in_place`: cur and src are dense channels-last views (dense_channels_last_pair) and go to
+        sr_mlp_volume_fwd_nhwc as they are; otherwise they are contiguous and go to sr_mlp_volume_fwd."""
         b, k, c, h, w = src.shape
         dev = src.device
         lib = _lib.lib()
@@ -437,14 +461,17 @@ class FeatureVolumeManager(CostVolumeManager):
         cin, d = c * (k + 1) + 10 * k + 4, self.num_depth_bins
         record = lambda: ("sr_mlp_volume_fwd", 2.0 * (cin * hidden + hidden * hidden + hidden) * b * d * h * w, (), None)
         with _lib.SPLIT_GUARD:   # (SR_MLP_SPLIT is read by the packing and by the sweep inside this one call)
+            if in_place and _lib.get_option("SR_MLP_SPLIT") != 0:   # the split-precision kernel reads cur planar
+                cur, src, in_place = cur.contiguous(), src.contiguous(), False
+            entry = "sr_mlp_volume_fwd_nhwc" if in_place else "sr_mlp_volume_fwd"
             rc = ops._timed(
-                dev, record, lib.sr_mlp_volume_fwd,
+                dev, record, getattr(lib, entry),
                 _lib.ptr(cur), _lib.ptr(src), _lib.ptr(Ks), _lib.ptr(T), _lib.ptr(Tp), _lib.ptr(invK),
                 _lib.ptr(planes), *planes.stride(), *[_lib.ptr(t) for t in params], hidden,
                 0.01,  # nn.LeakyReLU default slope (reference networks.py:139)
                 b, k, c, h, w, d, _lib.ptr(vol), sb, sd, sp, _lib.ptr(lowest),
                 _lib.ptr(mask), int(reserve_cus), _lib.ptr(ws), ws.numel(), _lib.stream_ptr(dev))
-        _lib.check(rc, "sr_mlp_volume_fwd")
+        _lib.check(rc, entry)
         return vol, lowest, mask
 
     def to_fast(self) -> "FastFeatureVolumeManager":

@@ -22,8 +22,8 @@
 #include "sr_view.h"
 
 #define SR_HID 128          // hidden width of the matching MLP (reference cost_volume.py:402)
-// Layer-1 inputs are split into a depth-VARIANT part (per view: 16 warped channels, mask, z', dot, ray
-// angle, source ray(3) and one spare slot that carries the plane depth d for view 0) and a depth-INVARIANT
+// Layer-1 inputs are split into a depth-VARIANT part (per view: 16 warped channels, mask, z', ray angle,
+// source ray(3), dot and one spare slot that carries the plane depth d for view 0: sr_mlp_var_col) and a depth-INVARIANT
 // part (reference features 16, reference ray 3, the constant 1 that carries the bias, 3 pose measures per
 // view).  The invariant part is multiplied ONCE per (64-pixel tile, chunk of planes) and re-used as the
 // accumulator initialiser of every plane of the chunk (-17 % layer-1 MFMA work).
@@ -40,6 +40,37 @@ static inline int sr_mlp_steps1(int K) { return sr_mlp_steps_var(K) + sr_mlp_ste
 static inline size_t sr_mlp_packed_floats(int K) { return (size_t)(sr_mlp_steps1(K) + SR_MLP_STEPS2) * 256 + 128 + 4; }
 
 // ------------------------------------------------------------------ weight packing ----
+// The one map from a layer-1 input slot of the sweep to its column of W1 [hidden, Cin] (reference channel offsets:
+// cost_volume.py:709-723); both packers below and nothing else place W1 columns.  -1: no column (zero), -2: the bias.
+// Slots of a view: 0..15 warped channels | 16 mask, 17 z' | 18 ray angle, 19 ray_0 | 20 ray_1, 21 ray_2 | 22 dot * mask,
+// 23 spare (the plane depth d for view 0, nothing for k > 0).  One pair = one k-step (8..11), and the pair (22, 23) comes
+// last: both are exact zeros for a dead view k > 0, so that view ends after step 10 (SR_VIEW_BODY).
+#define SR_MLP_COLUMN_OFFSETS(K, C)                                                                    \
+  const int o_cur = (K) * (C), o_mask = o_cur + (C), o_z = o_mask + (K), o_d = o_z + (K), o_dot = o_d + 1; \
+  const int o_ang = o_dot + (K), o_cray = o_ang + (K), o_sray = o_cray + 3, o_pd = o_sray + 3 * (K);  \
+  const int o_rm = o_pd + (K), o_tm = o_rm + (K);
+__device__ __forceinline__ int sr_mlp_var_col(int K, int C, int k, int s) {   // slot s of view k (depth-variant part)
+  SR_MLP_COLUMN_OFFSETS(K, C)
+  (void)o_cur; (void)o_cray; (void)o_pd; (void)o_rm; (void)o_tm;
+  if (s < 16) return k * C + s;
+  if (s == 16) return o_mask + k;
+  if (s == 17) return o_z + k;
+  if (s == 18) return o_ang + k;
+  if (s < 22) return o_sray + 3 * k + (s - 19);
+  if (s == 22) return o_dot + k;
+  return (k == 0) ? o_d : -1;
+}
+__device__ __forceinline__ int sr_mlp_inv_col(int K, int C, int u) {          // slot u of the depth-invariant part
+  SR_MLP_COLUMN_OFFSETS(K, C)
+  (void)o_mask; (void)o_z; (void)o_d; (void)o_dot; (void)o_ang; (void)o_sray;
+  if (u < 16) return o_cur + u;
+  if (u < 19) return o_cray + (u - 16);
+  if (u == 19) return -2;
+  if (u >= SR_INV_FIXED + 3 * K) return -1;
+  const int k = (u - SR_INV_FIXED) / 3, i = (u - SR_INV_FIXED) - 3 * k;
+  return (i == 0 ? o_pd : (i == 1 ? o_rm : o_tm)) + k;
+}
+
 // W?p[t][lane][mt] = W[row = 32*mt + (lane&31)][column of k-slot (t, half = lane>>5)]
 __global__ void sr_mlp_pack_kernel(const float* __restrict__ W1, const float* __restrict__ b1,
                                    const float* __restrict__ W2, const float* __restrict__ b2,
@@ -48,36 +79,19 @@ __global__ void sr_mlp_pack_kernel(const float* __restrict__ W1, const float* __
   const int steps_var = (SR_VIEW_SLOTS / 2) * K;
   const int steps1 = steps_var + (SR_INV_FIXED + 3 * K + 1) / 2;
   const int Cin = C * (K + 1) + 10 * K + 4;
-  // reference channel offsets (cost_volume.py:709-723)
-  const int o_cur = K * C, o_mask = o_cur + C, o_z = o_mask + K, o_d = o_z + K, o_dot = o_d + 1;
-  const int o_ang = o_dot + K, o_cray = o_ang + K, o_sray = o_cray + 3, o_pd = o_sray + 3 * K;
-  const int o_rm = o_pd + K, o_tm = o_rm + K;
   const int total = (steps1 + SR_MLP_STEPS2) * 256 + 128 + 1;
   for (int e = blockIdx.x * blockDim.x + threadIdx.x; e < total; e += gridDim.x * blockDim.x) {
     float v = 0.0f;
     if (e < steps1 * 256) {
       const int t = e >> 8, lane = (e >> 2) & 63, mt = e & 3;
       const int row = 32 * mt + (lane & 31);
-      int col = -1;  // -1: zero, -2: bias
+      int col;
       if (t < steps_var) {
         const int slot = 2 * t + (lane >> 5);
-        const int k = slot / SR_VIEW_SLOTS, s = slot - k * SR_VIEW_SLOTS;
-        if (s < 16) col = k * C + s;
-        else if (s == 16) col = o_mask + k;
-        else if (s == 17) col = o_z + k;
-        else if (s == 18) col = o_dot + k;
-        else if (s == 19) col = o_ang + k;
-        else if (s < 23) col = o_sray + 3 * k + (s - 20);
-        else col = (k == 0) ? o_d : -1;
+        const int k = slot / SR_VIEW_SLOTS;
+        col = sr_mlp_var_col(K, C, k, slot - k * SR_VIEW_SLOTS);
       } else {
-        const int u = 2 * (t - steps_var) + (lane >> 5);
-        if (u < 16) col = o_cur + u;
-        else if (u < 19) col = o_cray + (u - 16);
-        else if (u == 19) col = -2;
-        else if (u < SR_INV_FIXED + 3 * K) {
-          const int k = (u - SR_INV_FIXED) / 3, i = (u - SR_INV_FIXED) - 3 * k;
-          col = (i == 0 ? o_pd : (i == 1 ? o_rm : o_tm)) + k;
-        }
+        col = sr_mlp_inv_col(K, C, 2 * (t - steps_var) + (lane >> 5));
       }
       v = (col >= 0) ? W1[(size_t)row * Cin + col] : (col == -2 ? b1[row] : 0.0f);
     } else if (e < (steps1 + SR_MLP_STEPS2) * 256) {
@@ -107,7 +121,7 @@ __global__ void sr_mlp_pack_kernel(const float* __restrict__ W1, const float* __
 // ------------------------------------------------------------------ the sweep ---------
 
 struct SrMlpParams {
-  const float* cur;       // [B,16,h,w]
+  const float* cur;       // [B,16,h,w], or [B, h*w, 16] when cur_nhwc
   const float* src_nhwc;  // [B*K, h*w, 16]
   const float* invK;      // [B,16]
   const float* geom;      // [B*K, SR_GEOM_STRIDE]
@@ -119,6 +133,7 @@ struct SrMlpParams {
   int tiles_x;            // th x tw tiles per tile row, ceil(w / tw); 0: the flattened strip (sr_mlp_lane_pixel)
   int th_log2, tw_log2;   // th * tw = 64
   int chunk, chunks;      // planes per work unit, ceil(D / chunk)
+  int cur_nhwc;           // cur is channels-last like src (sr_mlp_volume_fwd_nhwc): a lane's 16 channels are one 64-byte run
   int vec_store;          // channels-last volume (plane stride 1): a lane keeps the costs of its unit's planes and
                           // stores them as 16-byte pieces at the end of the unit (instead of one 4-byte store per plane
                           // into 64 different 256-byte rows: r02 PMC counted 6.7x the volume's bytes in WRITE_SIZE)
@@ -264,8 +279,17 @@ __global__ __launch_bounds__(256, 1) void sr_mlp_volume_kernel(SrMlpParams p) {
     const float* src_b = p.src_nhwc + (size_t)b * p.K * N * C;
 
     float cur[C];
+    if (p.cur_nhwc) {   // (wave-uniform) the same 16 values either way
+      const float4* c4 = reinterpret_cast<const float4*>(p.cur + ((size_t)b * N + pc) * C);
 #pragma unroll
-    for (int c = 0; c < C; ++c) cur[c] = p.cur[((size_t)b * C + c) * N + pc];
+      for (int i = 0; i < C / 4; ++i) {
+        const float4 v = c4[i];
+        cur[4 * i] = v.x; cur[4 * i + 1] = v.y; cur[4 * i + 2] = v.z; cur[4 * i + 3] = v.w;
+      }
+    } else {
+#pragma unroll
+      for (int c = 0; c < C; ++c) cur[c] = p.cur[((size_t)b * C + c) * N + pc];
+    }
 
     float r0, r1, r2;
     {
@@ -346,15 +370,15 @@ __global__ __launch_bounds__(256, 1) void sr_mlp_volume_kernel(SrMlpParams p) {
     };
     // pieces of the per-view feature assembly (o = fn or f); the ray pieces need no taps
     float rv0, rv1, rv2, rsd, rdot;
-#define SR_RAY_A_T(o, t0, t1, t2, kview)                                                      \
+#define SR_RAY_A_T(t0, t1, t2)                                                                \
     {                                                                                         \
       _Pragma("clang fp contract(off)")                                                       \
       rv0 = X0 - (t0); rv1 = X1 - (t1); rv2 = X2 - (t2);                                       \
       rsd = fmaxf(sqrtf((rv0 * rv0 + rv1 * rv1) + rv2 * rv2), 1e-12f);                         \
-      (o)[23] = ((kview) == 0) ? d : 0.0f; /* plane depth rides in view 0's spare slot */      \
     }
-#define SR_RAY_A(o, g, kview) SR_RAY_A_T(o, (g)[12], (g)[13], (g)[14], kview)
-#define SR_RAY_A0(o, kview) SR_RAY_A_T(o, gt0, gt1, gt2, kview)  /* camera centre read by project_view */
+#define SR_RAY_A(o, g, kview)  /* the split kernel: every view carries its spare slot */      \
+    SR_RAY_A_T((g)[12], (g)[13], (g)[14]) (o)[23] = ((kview) == 0) ? d : 0.0f;
+#define SR_RAY_A0 SR_RAY_A_T(gt0, gt1, gt2)  /* camera centre read by project_view */
   // (r03) the source ray F.normalize(X - t_k) (cost_volume.py:654-669) and the ray angle F.cosine_similarity(...)
   // (:683-688) divide three components by one norm each: ONE IEEE reciprocal + three multiplies per normalisation
   // instead of three IEEE divisions (10 VALU instructions apiece beside the MFMAs).  x * (1/n) differs from x / n by at
@@ -363,13 +387,13 @@ __global__ __launch_bounds__(256, 1) void sr_mlp_volume_kernel(SrMlpParams p) {
     {                                                                                         \
       _Pragma("clang fp contract(off)")                                                       \
       const float rinv = 1.0f / rsd;                                                          \
-      (o)[20] = rv0 * rinv; (o)[21] = rv1 * rinv; (o)[22] = rv2 * rinv;                        \
+      (o)[19] = rv0 * rinv; (o)[20] = rv1 * rinv; (o)[21] = rv2 * rinv;                        \
     }
 #define SR_RAY_C(o)                                                                           \
     {                                                                                         \
       _Pragma("clang fp contract(off)")                                                       \
-      const float n2 = fmaxf(sqrtf(((o)[20] * (o)[20] + (o)[21] * (o)[21]) + (o)[22] * (o)[22]), 1e-5f); \
-      (o)[19] = ((crn0 * (o)[20] + crn1 * (o)[21]) + crn2 * (o)[22]) * (1.0f / n2);            \
+      const float n2 = fmaxf(sqrtf(((o)[19] * (o)[19] + (o)[20] * (o)[20]) + (o)[21] * (o)[21]), 1e-5f); \
+      (o)[18] = ((crn0 * (o)[19] + crn1 * (o)[20]) + crn2 * (o)[21]) * (1.0f / n2);            \
     }
 #define SR_INTERP2(o, i, lo)  /* channels 4i+2lo, 4i+2lo+1 as one packed fp32 pair (v_pk_fma_f32) */       \
     {                                                                                         \
@@ -394,7 +418,7 @@ __global__ __launch_bounds__(256, 1) void sr_mlp_volume_kernel(SrMlpParams p) {
       any_bounds |= sr_in_bounds(smp, p.h, p.w);                                              \
       (o)[16] = front ? 1.0f : 0.0f; /* mask (cost_volume.py:611-612) */                      \
       (o)[17] = smp.zp;              /* z'_k (cost_volume.py:603-609) */                      \
-      (o)[18] = front ? rdot : 0.0f; /* dot * mask (cost_volume.py:691-695) */                \
+      (o)[22] = front ? rdot : 0.0f; /* dot * mask (cost_volume.py:691-695) */                \
     }
 #define SR_DOT_DEAD(o)  /* SR_DOT of a dead view: channels 0..15 are never read, dot * mask is 0 */ \
     {                                                                                         \
@@ -403,7 +427,7 @@ __global__ __launch_bounds__(256, 1) void sr_mlp_volume_kernel(SrMlpParams p) {
       any_bounds |= sr_in_bounds(smp, p.h, p.w);                                              \
       (o)[16] = front ? 1.0f : 0.0f;                                                          \
       (o)[17] = smp.zp;                                                                       \
-      (o)[18] = 0.0f;                                                                         \
+      (o)[22] = 0.0f;                                                                         \
     }
 #define SR_SB __builtin_amdgcn_sched_barrier(0);
 
@@ -430,12 +454,12 @@ __global__ __launch_bounds__(256, 1) void sr_mlp_volume_kernel(SrMlpParams p) {
       bool dc = project_view(0), dn;  // is the view being multiplied / being assembled dead?
       if (!dc) {  // view 0, not overlapped
         load_taps(0);
-        SR_RAY_A0(f, 0) SR_RAY_B(f) SR_RAY_C(f)
+        SR_RAY_A0 SR_RAY_B(f) SR_RAY_C(f)
         SR_INTERP2(f, 0, 0) SR_INTERP2(f, 0, 1) SR_INTERP2(f, 1, 0) SR_INTERP2(f, 1, 1)
         SR_INTERP2(f, 2, 0) SR_INTERP2(f, 2, 1) SR_INTERP2(f, 3, 0) SR_INTERP2(f, 3, 1)
         SR_DOT(f)
       } else {
-        SR_RAY_A0(f, 0) SR_RAY_B(f) SR_RAY_C(f)
+        SR_RAY_A0 SR_RAY_B(f) SR_RAY_C(f)
         SR_DOT_DEAD(f)
         f[0] = f[1] = 0.0f;  // named (not used) by the select in front of the first step
       }
@@ -445,8 +469,10 @@ __global__ __launch_bounds__(256, 1) void sr_mlp_volume_kernel(SrMlpParams p) {
       // scalar branches per view (so every tap load is consumed inside the body that issued it and no s_waitcnt has to
       // be pessimistic behind a join):
       //   view k live: steps 0..11; the taps of view k+1 are first touched at step 7 (>= 3.5k cycles after issue)
-      //   view k dead: steps 8..11 only (slots 16..23: mask, z', rays, angle, plane depth); the taps of view k+1 are
-      //                first touched at step 10
+      //   view k dead: steps 8..10 only (slots 16..21: mask, z', ray angle, rays); step 11 would multiply dot * mask and
+      //                the spare slot, exact zeros both (SR_DOT_DEAD; no W1 column and no value for k > 0: sr_mlp_var_col,
+      //                SR_RAY_A_T) -- except for view 0, whose spare slot carries the plane depth: it keeps step 11.  The
+      //                taps of view k+1 are first touched at step 10, two k-steps after their issue
       //   view k+1 dead: no tap loads, no interpolation, no dot product
       // The executed k-steps keep their ascending (view, step) order, so every accumulator sees the same sequence of
       // non-zero additions as without the skip.  The last iteration has no view k+1: it re-derives the metadata of
@@ -456,6 +482,9 @@ __global__ __launch_bounds__(256, 1) void sr_mlp_volume_kernel(SrMlpParams p) {
         wN = wk[((t) + 1 < VS ? (t) + 1 : (t)) * 64];       \
         sr_l1_step(acc, wA, f[2 * (t)], f[2 * (t) + 1]);     \
         wA = wN;
+#define SR_STEP11(FIRST)  /* the spare slot: the plane depth for view 0, nothing (0) for every other view */ \
+        sr_l1_step(acc, wA, f[22], (FIRST) ? d : 0.0f);
+#define SR_STEP_END(t) sr_l1_step(acc, wA, f[2 * (t)], f[2 * (t) + 1]);  /* the body's last step: no next weights */
 #define SR_IF_LIVE(ND, x) if (!(ND)) { x }
 #define SR_VIEW_BODY(FIRST, CD, ND)                                                    \
         {                                                                              \
@@ -464,8 +493,8 @@ __global__ __launch_bounds__(256, 1) void sr_mlp_volume_kernel(SrMlpParams p) {
           float4 wA = wk[((CD) ? 8 : 0) * 64 + ((FIRST) ? 64 : 0)], wN;                \
           SR_SB                                                                        \
           if (!(CD)) {                                                                 \
-            if (!(FIRST)) { SR_STEP(0) SR_RAY_A0(fn, kn) SR_SB }                     \
-            SR_STEP(1) if (FIRST) { SR_RAY_A0(fn, kn) } SR_RAY_B(fn) SR_SB           \
+            if (!(FIRST)) { SR_STEP(0) SR_RAY_A0 SR_SB }                     \
+            SR_STEP(1) if (FIRST) { SR_RAY_A0 } SR_RAY_B(fn) SR_SB           \
             SR_STEP(2) SR_RAY_C(fn) SR_SB                                              \
             SR_STEP(3) SR_SB                                                           \
             SR_STEP(4) SR_SB                                                           \
@@ -475,16 +504,21 @@ __global__ __launch_bounds__(256, 1) void sr_mlp_volume_kernel(SrMlpParams p) {
             SR_STEP(8) SR_IF_LIVE(ND, SR_INTERP2(fn, 1, 0) SR_INTERP2(fn, 1, 1)) SR_SB \
             SR_STEP(9) SR_IF_LIVE(ND, SR_INTERP2(fn, 2, 0) SR_INTERP2(fn, 2, 1)) SR_SB \
             SR_STEP(10) SR_IF_LIVE(ND, SR_INTERP2(fn, 3, 0)) SR_SB                     \
-            SR_STEP(11) if (ND) { SR_DOT_DEAD(fn) } else { SR_INTERP2(fn, 3, 1) SR_DOT(fn) } SR_SB \
-          } else {                                                                     \
-            if (!(FIRST)) { SR_STEP(8) SR_RAY_A0(fn, kn) SR_SB }                     \
-            SR_STEP(9) if (FIRST) { SR_RAY_A0(fn, kn) } SR_RAY_B(fn) SR_RAY_C(fn) SR_SB \
+            SR_STEP11(FIRST) if (ND) { SR_DOT_DEAD(fn) } else { SR_INTERP2(fn, 3, 1) SR_DOT(fn) } SR_SB \
+          } else if (FIRST) {  /* dead view 0: step 8 ran in front of the bodies, step 11 carries the plane depth */ \
+            SR_STEP(9) SR_RAY_A0 SR_RAY_B(fn) SR_RAY_C(fn) SR_SB               \
             SR_STEP(10) SR_IF_LIVE(ND, SR_INTERP2(fn, 0, 0) SR_INTERP2(fn, 0, 1)       \
                                        SR_INTERP2(fn, 1, 0) SR_INTERP2(fn, 1, 1)) SR_SB \
-            SR_STEP(11) if (ND) { SR_DOT_DEAD(fn) } else {                             \
+            SR_STEP11(FIRST) if (ND) { SR_DOT_DEAD(fn) } else {                             \
+              SR_INTERP2(fn, 2, 0) SR_INTERP2(fn, 2, 1) SR_INTERP2(fn, 3, 0) SR_INTERP2(fn, 3, 1) SR_DOT(fn) } SR_SB \
+          } else {             /* dead view k > 0: three steps */                      \
+            SR_STEP(8) SR_RAY_A0 SR_SB                                         \
+            SR_STEP(9) SR_RAY_B(fn) SR_RAY_C(fn) SR_SB                                 \
+            SR_STEP_END(10) if (ND) { SR_DOT_DEAD(fn) } else {                         \
+              SR_INTERP2(fn, 0, 0) SR_INTERP2(fn, 0, 1) SR_INTERP2(fn, 1, 0) SR_INTERP2(fn, 1, 1) SR_SB \
               SR_INTERP2(fn, 2, 0) SR_INTERP2(fn, 2, 1) SR_INTERP2(fn, 3, 0) SR_INTERP2(fn, 3, 1) SR_DOT(fn) } SR_SB \
           }                                                                            \
-          _Pragma("unroll") for (int t = (ND) ? 16 : 0; t < SR_VIEW_SLOTS; ++t) f[t] = fn[t]; \
+          _Pragma("unroll") for (int t = (ND) ? 16 : 0; t < SR_VIEW_SLOTS - 1; ++t) f[t] = fn[t]; \
         }
       // The four bodies are four if-without-else in a row on four flags the compiler cannot relate to each other
       // (sr_opaque): hipcc flattens an if / else between live accumulators into a predicated chain whose joins carry
@@ -661,19 +695,7 @@ __global__ void sr_mlp_pack_split_kernel(const float* __restrict__ W1, const flo
   const int steps_inv = (SR_INV_FIXED + 3 * K + 1) / 2;
   const int steps1 = steps_var + steps_inv;
   const int Cin = C * (K + 1) + 10 * K + 4;
-  const int o_cur = K * C, o_mask = o_cur + C, o_z = o_mask + K, o_d = o_z + K, o_dot = o_d + 1;
-  const int o_ang = o_dot + K, o_cray = o_ang + K, o_sray = o_cray + 3, o_pd = o_sray + 3 * K;
-  const int o_rm = o_pd + K, o_tm = o_rm + K;
   unsigned* pk = reinterpret_cast<unsigned*>(packed);
-  auto var_col = [&](int k, int s) {   // column of W1 for slot s of view k (-1: none)
-    if (s < 16) return k * C + s;
-    if (s == 16) return o_mask + k;
-    if (s == 17) return o_z + k;
-    if (s == 18) return o_dot + k;
-    if (s == 19) return o_ang + k;
-    if (s < 23) return o_sray + 3 * k + (s - 20);
-    return (k == 0) ? o_d : -1;
-  };
   auto put = [&](size_t word, int piece, float wa, float wb) {
     unsigned hi, lo;
     S::split(wa, wb, hi, lo);
@@ -687,21 +709,13 @@ __global__ void sr_mlp_pack_split_kernel(const float* __restrict__ W1, const flo
       if (q < 2048) { mt = q >> 9; piece = (q >> 8) & 1; lane = (q >> 2) & 63; dw = q & 3; slot0 = 8 * (lane >> 5) + 2 * dw; }
       else { const int q2 = q - 2048; mt = q2 >> 8; piece = (q2 >> 7) & 1; lane = (q2 >> 2) & 31; dw = q2 & 3; slot0 = 16 + 2 * dw; }
       const int row = 32 * mt + (lane & 31);
-      const int ca = var_col(k, slot0), cb = var_col(k, slot0 + 1);
+      const int ca = sr_mlp_var_col(K, C, k, slot0), cb = sr_mlp_var_col(K, C, k, slot0 + 1);
       put(e, piece, ca >= 0 ? W1[(size_t)row * Cin + ca] : 0.0f, cb >= 0 ? W1[(size_t)row * Cin + cb] : 0.0f);
     } else if (e < steps1 * 256) {   // depth-invariant part: fp32, the layout of sr_mlp_pack_kernel
       const int e1 = e - steps_var * 256;
       const int t = e1 >> 8, lane = (e1 >> 2) & 63, mt = e1 & 3;
       const int row = 32 * mt + (lane & 31);
-      const int u = 2 * t + (lane >> 5);
-      int col = -1;
-      if (u < 16) col = o_cur + u;
-      else if (u < 19) col = o_cray + (u - 16);
-      else if (u == 19) col = -2;
-      else if (u < SR_INV_FIXED + 3 * K) {
-        const int k = (u - SR_INV_FIXED) / 3, i = (u - SR_INV_FIXED) - 3 * k;
-        col = (i == 0 ? o_pd : (i == 1 ? o_rm : o_tm)) + k;
-      }
+      const int col = sr_mlp_inv_col(K, C, 2 * t + (lane >> 5));
       packed[e] = (col >= 0) ? W1[(size_t)row * Cin + col] : (col == -2 ? b1[row] : 0.0f);
     } else if (e < steps1 * 256 + SR_SPL_W2_WORDS) {
       const int q = e - steps1 * 256;
@@ -1073,7 +1087,10 @@ static float* sr_ws_packed(void* workspace, int B, int K, int C, int h, int w) {
 // parked for the whole sweep (batch 1, graph replay: 5.72 -> 5.48 ms per frame although the sweep itself takes 14 % longer).
 // At batch 8 it costs what it gains (25.4-25.6 vs 25.2-25.5 ms; 27.2 vs 26.5 on the keyframe stream), at 960x736 / 96
 // planes it loses 2.4 ms of 46: the caller's decision, by batch size.  A reserve that would leave fewer than 8 CUs is ignored.
-static int sr_mlp_volume_sweep_reserved(const float* cur, const float* invK_cur, const float* planes, int64_t ps_b,
+// src_nhwc = null: cur is planar [B,16,h,w] and the source features are the workspace copy of sr_volume_prepare; else both are
+// the caller's channels-last buffers, cur [B, h*w, 16] and src_nhwc [B*K, h*w, 16], read where they lie.
+static int sr_mlp_volume_sweep_reserved(const float* cur, const float* src_nhwc, const float* invK_cur,
+                                        const float* planes, int64_t ps_b,
                                         int64_t ps_d, int64_t ps_y, int64_t ps_x, float leaky_slope, int B, int K,
                                         int C, int h, int w, int D, float* out_cv, int64_t cv_sb, int64_t cv_sd,
                                         int64_t cv_sp, float* out_lowest, uint8_t* out_mask, int reserve_cus,
@@ -1088,7 +1105,8 @@ static int sr_mlp_volume_sweep_reserved(const float* cur, const float* invK_cur,
   const int N = h * w;
 
   SrMlpParams p;
-  p.cur = cur; p.src_nhwc = sr_ws_src_nhwc(workspace, B, K); p.invK = invK_cur; p.geom = sr_ws_geom(workspace);
+  p.cur = cur; p.src_nhwc = src_nhwc ? src_nhwc : sr_ws_src_nhwc(workspace, B, K); p.cur_nhwc = src_nhwc != nullptr;
+  p.invK = invK_cur; p.geom = sr_ws_geom(workspace);
   p.packed = sr_ws_packed(workspace, B, K, C, h, w);
   p.planes = {planes, ps_b, ps_d, ps_y, ps_x};
   p.out = {out_cv, cv_sb, cv_sd, cv_sp, out_lowest, out_mask};
@@ -1126,7 +1144,8 @@ static int sr_mlp_volume_sweep_reserved(const float* cur, const float* invK_cur,
   const size_t lds_max = 160 * 1024;
   const int split = sr_mlp_split_mode();
   if (split < 0) return SR_ERR_INVALID_ARGUMENT;
-  if (split) {   // fenced experiment: both weight blocks must fit the LDS (K <= 7)
+  if (split) {   // fenced experiment: both weight blocks must fit the LDS (K <= 7); reads cur planar only
+    if (p.cur_nhwc) return SR_ERR_UNSUPPORTED;
     const size_t bytes = ((size_t)SR_SPL_TAB + SR_SPL_W2_WORDS + (size_t)K * SR_SPL_VIEW_WORDS) * 4;
     if (bytes > lds_max) return SR_ERR_UNSUPPORTED;
     const void* fn = split == 1 ? (const void*)sr_mlp_volume_split_kernel<1> : (const void*)sr_mlp_volume_split_kernel<2>;
@@ -1159,8 +1178,8 @@ extern "C" int sr_mlp_volume_sweep(const float* cur, const float* invK_cur, cons
                                    int C, int h, int w, int D, float* out_cv, int64_t cv_sb, int64_t cv_sd,
                                    int64_t cv_sp, float* out_lowest, uint8_t* out_mask, void* workspace,
                                    size_t workspace_bytes, void* stream_) {
-  return sr_mlp_volume_sweep_reserved(cur, invK_cur, planes, ps_b, ps_d, ps_y, ps_x, leaky_slope, B, K, C, h, w, D, out_cv,
-                                      cv_sb, cv_sd, cv_sp, out_lowest, out_mask, 0, workspace, workspace_bytes, stream_);
+  return sr_mlp_volume_sweep_reserved(cur, nullptr, invK_cur, planes, ps_b, ps_d, ps_y, ps_x, leaky_slope, B, K, C, h, w, D,
+                                      out_cv, cv_sb, cv_sd, cv_sp, out_lowest, out_mask, 0, workspace, workspace_bytes, stream_);
 }
 
 int sr_launch_argmax_planes(const float* cv, int64_t sb, int64_t sd, int64_t sp, SrPlanes planes, int B, int h, int w,
@@ -1201,7 +1220,34 @@ extern "C" int sr_mlp_volume_fwd(const float* cur, const float* src, const float
   if (rc) return rc;
   rc = sr_mlp_pack_weights(W1, b1, W2, b2, W3, b3, hidden, B, K, C, h, w, workspace, workspace_bytes, stream_);
   if (rc) return rc;
-  return sr_mlp_volume_sweep_reserved(cur, invK_cur, planes, ps_b, ps_d, ps_y, ps_x, leaky_slope, B, K, C, h, w, D, out_cv,
-                                      cv_sb, cv_sd, cv_sp, out_lowest, out_mask, reserve_cus, workspace, workspace_bytes,
-                                      stream_);
+  return sr_mlp_volume_sweep_reserved(cur, nullptr, invK_cur, planes, ps_b, ps_d, ps_y, ps_x, leaky_slope, B, K, C, h, w, D,
+                                      out_cv, cv_sb, cv_sd, cv_sp, out_lowest, out_mask, reserve_cus, workspace,
+                                      workspace_bytes, stream_);
+}
+
+// sr_mlp_volume_fwd on features that already are channels-last (the matching encoder's output buffer): no transposing copy
+// of either operand, the sweep reads cur [B, h*w, 16] and src [B*K, h*w, 16] where the caller keeps them.
+extern "C" int sr_mlp_volume_fwd_nhwc(const float* cur, const float* src, const float* K_src, const float* T_src_cur,
+                                      const float* T_cur_src, const float* invK_cur, const float* planes, int64_t ps_b,
+                                      int64_t ps_d, int64_t ps_y, int64_t ps_x, const float* W1, const float* b1,
+                                      const float* W2, const float* b2, const float* W3, const float* b3, int hidden,
+                                      float leaky_slope, int B, int K, int C, int h, int w, int D, float* out_cv,
+                                      int64_t cv_sb, int64_t cv_sd, int64_t cv_sp, float* out_lowest, uint8_t* out_mask,
+                                      int reserve_cus, void* workspace, size_t workspace_bytes, void* stream_) {
+  if (B < 0 || K <= 0 || C <= 0 || h <= 0 || w <= 0 || D <= 0 || reserve_cus < 0) return SR_ERR_INVALID_ARGUMENT;
+  if (B == 0) return SR_OK;
+  if (!cur || !src || !K_src || !T_src_cur || !T_cur_src || !workspace) return SR_ERR_INVALID_ARGUMENT;
+  if (((size_t)cur | (size_t)src) & 15) return SR_ERR_INVALID_ARGUMENT;   // a pixel is read as four 16-byte pieces
+  if (hidden != SR_HID || C != 16) return SR_ERR_UNSUPPORTED;
+  const int split = sr_mlp_split_mode();
+  if (split < 0) return SR_ERR_INVALID_ARGUMENT;
+  if (split) return SR_ERR_UNSUPPORTED;   // the split-precision kernel reads cur planar: sr_mlp_volume_fwd serves it
+  if (workspace_bytes < sr_mlp_volume_workspace_bytes(B, K, C, h, w, hidden)) return SR_ERR_WORKSPACE_TOO_SMALL;
+  int rc = sr_launch_geom(K_src, T_src_cur, T_cur_src, sr_ws_geom(workspace), B * K, (hipStream_t)stream_);
+  if (rc) return rc;
+  rc = sr_mlp_pack_weights(W1, b1, W2, b2, W3, b3, hidden, B, K, C, h, w, workspace, workspace_bytes, stream_);
+  if (rc) return rc;
+  return sr_mlp_volume_sweep_reserved(cur, src, invK_cur, planes, ps_b, ps_d, ps_y, ps_x, leaky_slope, B, K, C, h, w, D,
+                                      out_cv, cv_sb, cv_sd, cv_sp, out_lowest, out_mask, reserve_cus, workspace,
+                                      workspace_bytes, stream_);
 }
