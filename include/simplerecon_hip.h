@@ -1548,6 +1548,34 @@ int sr_grad_stats(const void* g_ptrs, const int64_t* numel, const int32_t* chunk
 int sr_grad_scale_inplace(const void* g_ptrs, const int64_t* numel, const int32_t* chunk_start, int num_tensors,
                           int num_chunks, const float* coef, void* stream);
 
+/* ---- offline and dense tuple generation (sr_tuples.hip; reference data_scripts/generate_test_tuples.py:65-157, 268-382,
+ * tools/keyframe_buffer.py:245-381) -----------------------------------------------------------------------------------
+ * sr_pose_inverse_f64: inverses[i] = poses[i]^-1 for n row-major 4x4 fp64 matrices, a general inverse by cofactors (no
+ * rigid-motion shortcut; a singular matrix gives inf / NaN).
+ *
+ * sr_tuple_walk_f64: one walk per entry of reference_indices [n_walks] (int32 frame numbers into poses [n_poses,4,4] and
+ * their inverses), one wave each.  The walk is primed with its reference frame r and offers, in this order, r+1, r-1,
+ * r+2, r-2, ... (both_directions != 0; a direction that has run out still takes its turn) or r-1, r-2, ... (0) to a FIFO
+ * of buffer_size poses: a candidate c is admitted when sqrt(t^2 + R^2) of inv(pose c) @ pose b reaches
+ * keyframe_pose_distance for every buffered b (R = sqrt(2 (1 - min(3, trace) / 3)), t = |translation|); admitted into a full
+ * buffer it pushes the oldest entry out, the primed frame first.  The walk ends when both directions have run out or after a
+ * candidate's test has left acceptance_cap admissions behind it.  Then the oldest entry is dropped, the next one becomes
+ * the reference pose of the penalties (R - optimal_r)^2 + w (t - optimal_t)^2, w = 5 below optimal_t and 1 from it on,
+ * of inv(reference) @ pose b over all entries left, itself included, and the min(n_measurement_frames, entries left - 1)
+ * smallest are the sources.  indices [n_walks, 1 + n_measurement_frames] int32: r, then the sources by ascending penalty
+ * (ties: older entry first), then -1; counts [n_walks]: the number of sources.  A reference index outside [0, n_poses) gives
+ * a row of -1 and count 0.  Every byte of both outputs is written; fp64 throughout; no atomics, no workspace, no
+ * synchronisation: the same call gives the same bytes.
+ * Poses must be finite with a bottom row of exactly 0 0 0 1 (the kernel reads rows 0..2 only); the caller checks.
+ * SR_ERR_UNSUPPORTED: buffer_size > 64 (one slot per lane), n_measurement_frames > 63.  SR_ERR_INVALID_ARGUMENT: negative
+ * sizes, buffer_size < 1, n_poses > 2^28, a NULL pointer (poses may be NULL when n_poses == 0), fp64 pointers not 8-byte or
+ * int32 pointers not 4-byte aligned. */
+int sr_pose_inverse_f64(const double* poses, double* inverses, int n, void* stream);
+int sr_tuple_walk_f64(const double* poses, const double* inverses, int n_poses, const int32_t* reference_indices,
+                      int n_walks, int both_directions, int buffer_size, int acceptance_cap,
+                      double keyframe_pose_distance, double optimal_t, double optimal_r, int n_measurement_frames,
+                      int32_t* indices, int32_t* counts, void* stream);
+
 #ifdef __cplusplus
 }
 #endif

@@ -229,6 +229,8 @@ SIGNATURES = {
     "sr_grad_stats_workspace_bytes": (_sz, [_i, _i]),
     "sr_grad_stats": (_i, [_p, _p, _p, _i, _i, _p, _f, _p, _p, _p, _p, C.c_double, C.c_double, _i, _p, _sz, _p]),
     "sr_grad_scale_inplace": (_i, [_p, _p, _p, _i, _i, _p, _p]),
+    "sr_pose_inverse_f64": (_i, [_p, _p, _i, _p]),
+    "sr_tuple_walk_f64": (_i, [_p, _p, _i, _p, _i, _i, _i, _i, C.c_double, C.c_double, C.c_double, _i, _p, _p, _p]),
 }
 
 
