@@ -155,6 +155,16 @@ __device__ __forceinline__ bool sr_in_bounds(const SrSample& s, int h, int w) {
   return (s.pix_x > 2.0f) & (s.pix_x < (float)(w - 2)) & (s.pix_y > 2.0f) & (s.pix_y < (float)(h - 2));
 }
 
+// Back-projected ray of pixel (x, y) through the 4x4 inverse intrinsics iK: r = iK[:3,:3] (x + 0.5, y + 0.5, 1)
+// (geometry_utils.py:34-44); the point at plane depth d is d * r (geometry_utils.py:56-57).
+__device__ __forceinline__ void sr_pixel_ray(const float* iK, int x, int y, float& r0, float& r1, float& r2) {
+#pragma clang fp contract(off)
+  const float px = (float)x + 0.5f, py = (float)y + 0.5f;
+  r0 = iK[0] * px + iK[1] * py + iK[2];
+  r1 = iK[4] * px + iK[5] * py + iK[6];
+  r2 = iK[8] * px + iK[9] * py + iK[10];
+}
+
 // Activation code carried by the `leaky_slope` argument of the convolution entry points (simplerecon_hip.h): a value
 // >= 0 is the LeakyReLU slope (0 = ReLU), SR_ACT_NONE (any value in (-1.5, 0)) the identity, SR_ACT_SILU x * sigmoid(x).
 #ifdef __HIPCC__
@@ -221,6 +231,77 @@ struct SrDotParams {
   int B, K, h, w, D;
   float inv_w, inv_h;
 };
+
+// ---- stages shared by the L1-gather sweeps sr_dot_volume_kernel<C> and sr_dot_volume_kernel16q (sr_dot_volume.hip) ----
+// What a lane of those kernels works on: a wavefront owns 64 consecutive pixels and the planes [j0, j1) of its plane group.
+// Plane groups (grp of S, read by the kernel): waves of one workgroup (LDS argmax merge,
+// sr_dot_store_lowest), or -- when there are too few pixel tiles to balance 256 CUs -- separate single-wave workgroups
+// along grid z (lowest cost then comes from sr_argmax_planes).
+// XCD-aware tile order: workgroup id % 8 selects the XCD (observed dispatch order; speed only, never correctness), so give
+// each XCD a CONTIGUOUS band of pixel tiles -- its private L2 then holds one band (plus the disparity range) of every
+// source map instead of all of them.  Bijective for any grid size.
+struct SrDotLane {
+  int lane, grp, S, b, N, tile;
+  int pix, pc, y, x;   // this lane's pixel; pc = pix clamped into the image (what inactive lanes load from), (y, x) of pc
+  bool active;         // pix < N
+  int j0, j1;
+};
+__device__ __forceinline__ SrDotLane sr_dot_lane(const SrDotParams& p, int grp, int S) {
+  SrDotLane l;
+  l.lane = threadIdx.x & 63;
+  l.grp = grp;
+  l.S = S;
+  l.b = blockIdx.y;
+  l.N = p.h * p.w;
+  l.tile = blockIdx.x;
+  {
+    const int nwg = gridDim.x, q = nwg >> 3, r = nwg & 7, xcd = l.tile & 7, idx = l.tile >> 3;
+    l.tile = (xcd < r ? xcd * (q + 1) : r * (q + 1) + (xcd - r) * q) + idx;
+  }
+  l.pix = l.tile * 64 + l.lane;
+  l.active = l.pix < l.N;
+  l.pc = l.active ? l.pix : l.N - 1;
+  l.y = l.pc / p.w;
+  l.x = l.pc - l.y * p.w;
+  const int per = (p.D + l.S - 1) / l.S;
+  l.j0 = l.grp * per;
+  l.j1 = min(p.D, l.j0 + per);
+  return l;
+}
+// running argmax over a lane's planes: first max wins; NaN = max (torch.argmax)
+__device__ __forceinline__ void sr_argmax_step(float cost, float d, float& best, float& best_d, bool& have) {
+  if (!have || cost > best || (cost != cost && best == best)) { best = cost; best_d = d; have = true; }
+}
+// lowest-cost depth of a pixel from its plane groups' running argmaxes; smem: [S][64] best cost, [S][64] best depth,
+// [S][64] valid flag
+__device__ __forceinline__ void sr_dot_store_lowest(const SrDotParams& p, const SrDotLane& l, float* smem, float best,
+                                                    float best_d, bool have) {
+  if (p.out.lowest) {
+    if (gridDim.z > 1) {
+      // merged by the caller (separate launch)
+    } else if (l.S == 1) {
+      if (l.active) p.out.lowest[(size_t)l.b * l.N + l.pix] = best_d;
+    } else {
+      float* s_best = smem;
+      float* s_d = smem + l.S * 64;
+      float* s_have = smem + 2 * l.S * 64;
+      s_best[l.grp * 64 + l.lane] = best;
+      s_d[l.grp * 64 + l.lane] = best_d;
+      s_have[l.grp * 64 + l.lane] = have ? 1.0f : 0.0f;
+      __syncthreads();
+      if (l.grp == 0 && l.active) {
+        float bb = best, bd = best_d;  // group 0 always owns plane 0
+        for (int g = 1; g < l.S; ++g)
+          if (s_have[g * 64 + l.lane] != 0.0f &&
+              (s_best[g * 64 + l.lane] > bb || (s_best[g * 64 + l.lane] != s_best[g * 64 + l.lane] && bb == bb))) {
+            bb = s_best[g * 64 + l.lane];
+            bd = s_d[g * 64 + l.lane];
+          }
+        p.out.lowest[(size_t)l.b * l.N + l.pix] = bd;
+      }
+    }
+  }
+}
 
 // workspace carving: [geom records | channels-last source features | per-pixel argmax keys of the LDS-staged sweep]
 static inline float* sr_ws_geom(void* workspace) { return (float*)sr_align_up((size_t)workspace, 256); }

@@ -107,44 +107,19 @@ __device__ __forceinline__ float sr_tap_dot(const float* __restrict__ img, int t
 
 template <int C>
 __global__ __launch_bounds__(1024) void sr_dot_volume_kernel(SrDotParams p) {
-  extern __shared__ float smem[];  // [S][64] best cost, [S][64] best depth, [S][64] valid flag
-  const int lane = threadIdx.x & 63;
-  // plane groups: waves of one workgroup (LDS argmax merge below), or -- when there are too few pixel tiles to
-  // balance 256 CUs -- separate single-wave workgroups along grid z (lowest cost then comes from sr_argmax_planes)
-  const int grp = gridDim.z > 1 ? (int)blockIdx.z : (int)(threadIdx.x >> 6);
+  extern __shared__ float smem[];  // sr_dot_store_lowest
+  const int grp = gridDim.z > 1 ? (int)blockIdx.z : (int)(threadIdx.x >> 6);   // plane group grp of S: sr_dot_lane
   const int S = gridDim.z > 1 ? (int)gridDim.z : (int)(blockDim.x >> 6);
-  const int b = blockIdx.y;
-  const int N = p.h * p.w;
-  // XCD-aware tile order: workgroup id % 8 selects the XCD (observed dispatch order; speed only, never
-  // correctness), so give each XCD a CONTIGUOUS band of pixel tiles -- its private L2 then holds one band
-  // (plus the disparity range) of every source map instead of all of them.  Bijective for any grid size.
-  int tile = blockIdx.x;
-  {
-    const int nwg = gridDim.x, q = nwg >> 3, r = nwg & 7, xcd = tile & 7, idx = tile >> 3;
-    tile = (xcd < r ? xcd * (q + 1) : r * (q + 1) + (xcd - r) * q) + idx;
-  }
-  const int pix = tile * 64 + lane;
-  const bool active = pix < N;
-  const int pc = active ? pix : N - 1;
-  const int y = pc / p.w, x = pc - y * p.w;
-
-  const int per = (p.D + S - 1) / S;
-  const int j0 = grp * per;
-  const int j1 = min(p.D, j0 + per);
+  const SrDotLane l = sr_dot_lane(p, grp, S);
+  const int b = l.b, N = l.N, pix = l.pix, pc = l.pc, y = l.y, x = l.x;
+  const bool active = l.active;
 
   float cur[C];
 #pragma unroll
   for (int c = 0; c < C; ++c) cur[c] = p.cur[((size_t)b * C + c) * N + pc];
 
   float r0, r1, r2;
-  {
-#pragma clang fp contract(off)
-    const float* iK = p.invK + 16 * (size_t)b;
-    const float px = (float)x + 0.5f, py = (float)y + 0.5f;  // geometry_utils.py:34-44
-    r0 = iK[0] * px + iK[1] * py + iK[2];
-    r1 = iK[4] * px + iK[5] * py + iK[6];
-    r2 = iK[8] * px + iK[9] * py + iK[10];
-  }
+  sr_pixel_ray(p.invK + 16 * (size_t)b, x, y, r0, r1, r2);
 
   const float* geom_b = p.geom + (size_t)b * p.K * SR_GEOM_STRIDE;
   const float* src_b = p.src_nhwc + (size_t)b * p.K * N * C;
@@ -153,7 +128,7 @@ __global__ __launch_bounds__(1024) void sr_dot_volume_kernel(SrDotParams p) {
 
   float best = 0.0f, best_d = 0.0f;
   bool have = false;
-  for (int j = j0; j < j1; ++j) {
+  for (int j = l.j0; j < l.j1; ++j) {
     const float d = planes[j * p.planes.sd];
     float X0, X1, X2;
     {
@@ -179,36 +154,12 @@ __global__ __launch_bounds__(1024) void sr_dot_volume_kernel(SrDotParams p) {
       any_bounds |= sr_in_bounds(s, p.h, p.w);
     }
     if (active) out[j * p.out.sd] = cost;
-    if (!have || cost > best || (cost != cost && best == best)) { best = cost; best_d = d; have = true; }  // first max wins; NaN = max (torch.argmax)
+    sr_argmax_step(cost, d, best, best_d, have);
     if (j == p.D - 1 && p.out.mask && active)
       p.out.mask[(size_t)b * N + pix] = (uint8_t)(any_depth && any_bounds);
   }
 
-  if (p.out.lowest) {
-    if (gridDim.z > 1) {
-      // merged by the caller (separate launch)
-    } else if (S == 1) {
-      if (active) p.out.lowest[(size_t)b * N + pix] = best_d;
-    } else {
-      float* s_best = smem;
-      float* s_d = smem + S * 64;
-      float* s_have = smem + 2 * S * 64;
-      s_best[grp * 64 + lane] = best;
-      s_d[grp * 64 + lane] = best_d;
-      s_have[grp * 64 + lane] = have ? 1.0f : 0.0f;
-      __syncthreads();
-      if (grp == 0 && active) {
-        float bb = best, bd = best_d;  // group 0 always owns plane 0
-        for (int g = 1; g < S; ++g)
-          if (s_have[g * 64 + lane] != 0.0f &&
-              (s_best[g * 64 + lane] > bb || (s_best[g * 64 + lane] != s_best[g * 64 + lane] && bb == bb))) {
-            bb = s_best[g * 64 + lane];
-            bd = s_d[g * 64 + lane];
-          }
-        p.out.lowest[(size_t)b * N + pix] = bd;
-      }
-    }
-  }
+  sr_dot_store_lowest(p, l, smem, best, best_d, have);
 }
 
 // 16-channel variant (what SimpleRecon uses) with texel-coalesced taps.  In the generic kernel a lane owns a pixel and
@@ -229,25 +180,12 @@ __device__ __forceinline__ float sr_quad_sum(float v) {
 
 __global__ __launch_bounds__(1024) void sr_dot_volume_kernel16q(SrDotParams p) {
   constexpr int C = 16;
-  extern __shared__ float smem[];  // [S][64] best cost, [S][64] best depth, [S][64] valid flag
-  const int lane = threadIdx.x & 63;
-  // plane groups: waves of one workgroup (LDS argmax merge below), or -- when there are too few pixel tiles to
-  // balance 256 CUs -- separate single-wave workgroups along grid z (lowest cost then comes from sr_argmax_planes)
-  const int grp = gridDim.z > 1 ? (int)blockIdx.z : (int)(threadIdx.x >> 6);
+  extern __shared__ float smem[];  // sr_dot_store_lowest
+  const int grp = gridDim.z > 1 ? (int)blockIdx.z : (int)(threadIdx.x >> 6);   // plane group grp of S: sr_dot_lane
   const int S = gridDim.z > 1 ? (int)gridDim.z : (int)(blockDim.x >> 6);
-  const int b = blockIdx.y;
-  const int N = p.h * p.w;
-  int tile = blockIdx.x;  // XCD-aware tile order, see sr_dot_volume_kernel
-  {
-    const int nwg = gridDim.x, q = nwg >> 3, r = nwg & 7, xcd = tile & 7, idx = tile >> 3;
-    tile = (xcd < r ? xcd * (q + 1) : r * (q + 1) + (xcd - r) * q) + idx;
-  }
-  const int pix = tile * 64 + lane;
-  const bool active = pix < N;
-  const int pc = active ? pix : N - 1;
-  const int y = pc / p.w, x = pc - y * p.w;
-  const int per = (p.D + S - 1) / S;
-  const int j0 = grp * per, j1 = min(p.D, j0 + per);
+  const SrDotLane l = sr_dot_lane(p, grp, S);
+  const int lane = l.lane, b = l.b, N = l.N, tile = l.tile, pix = l.pix, pc = l.pc, y = l.y, x = l.x;
+  const bool active = l.active;
 
   // reference features of the pixel this lane serves in round r (pixel 16r + lane/4), channels 4*(lane%4)..+3
   const int quad = lane & 3, slot = lane >> 2;
@@ -260,14 +198,7 @@ __global__ __launch_bounds__(1024) void sr_dot_volume_kernel16q(SrDotParams p) {
   }
 
   float r0, r1, r2;
-  {
-#pragma clang fp contract(off)
-    const float* iK = p.invK + 16 * (size_t)b;
-    const float px = (float)x + 0.5f, py = (float)y + 0.5f;  // geometry_utils.py:34-44
-    r0 = iK[0] * px + iK[1] * py + iK[2];
-    r1 = iK[4] * px + iK[5] * py + iK[6];
-    r2 = iK[8] * px + iK[9] * py + iK[10];
-  }
+  sr_pixel_ray(p.invK + 16 * (size_t)b, x, y, r0, r1, r2);
   const float* geom_b = p.geom + (size_t)b * p.K * SR_GEOM_STRIDE;
   const float* src_b = p.src_nhwc + (size_t)b * p.K * N * C;
   const float* planes = p.planes.ptr + b * p.planes.sb + y * p.planes.sy + x * p.planes.sx;
@@ -276,7 +207,7 @@ __global__ __launch_bounds__(1024) void sr_dot_volume_kernel16q(SrDotParams p) {
 
   float best = 0.0f, best_d = 0.0f;
   bool have = false;
-  for (int j = j0; j < j1; ++j) {
+  for (int j = l.j0; j < l.j1; ++j) {
     const float d = planes[j * p.planes.sd];
     float X0, X1, X2;
     {
@@ -327,36 +258,12 @@ __global__ __launch_bounds__(1024) void sr_dot_volume_kernel16q(SrDotParams p) {
       cost = (lane >> 4) == r ? v : cost;
     }
     if (active) out[j * p.out.sd] = cost;
-    if (!have || cost > best || (cost != cost && best == best)) { best = cost; best_d = d; have = true; }  // first max wins; NaN = max (torch.argmax)
+    sr_argmax_step(cost, d, best, best_d, have);
     if (j == p.D - 1 && p.out.mask && active)
       p.out.mask[(size_t)b * N + pix] = (uint8_t)(any_depth && any_bounds);
   }
 
-  if (p.out.lowest) {
-    if (gridDim.z > 1) {
-      // merged by the caller (separate launch)
-    } else if (S == 1) {
-      if (active) p.out.lowest[(size_t)b * N + pix] = best_d;
-    } else {
-      float* s_best = smem;
-      float* s_d = smem + S * 64;
-      float* s_have = smem + 2 * S * 64;
-      s_best[grp * 64 + lane] = best;
-      s_d[grp * 64 + lane] = best_d;
-      s_have[grp * 64 + lane] = have ? 1.0f : 0.0f;
-      __syncthreads();
-      if (grp == 0 && active) {
-        float bb = best, bd = best_d;  // group 0 always owns plane 0
-        for (int g = 1; g < S; ++g)
-          if (s_have[g * 64 + lane] != 0.0f &&
-              (s_best[g * 64 + lane] > bb || (s_best[g * 64 + lane] != s_best[g * 64 + lane] && bb == bb))) {
-            bb = s_best[g * 64 + lane];
-            bd = s_d[g * 64 + lane];
-          }
-        p.out.lowest[(size_t)b * N + pix] = bd;
-      }
-    }
-  }
+  sr_dot_store_lowest(p, l, smem, best, best_d, have);
 }
 
 // ------------------------------------------------------------------------ C ABI -------

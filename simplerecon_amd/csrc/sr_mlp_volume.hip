@@ -208,6 +208,33 @@ __device__ __forceinline__ int sr_opaque(bool flag) {
 
 #define SR_LDS_W3_FLOATS 256  // w3tab (128) + b3 + pad, in front of W1 in LDS
 
+// ---- stages shared by sr_mlp_volume_kernel and sr_mlp_volume_split_kernel ----
+
+// current-frame ray F.normalize(X) (cost_volume.py:641-651, eps 1e-12): X = d * r, so the ray does not depend
+// on the plane beyond rounding; it is formed from plane 0 (depth d0) for every chunk (so results do not depend on how
+// planes are chunked into work units) and shared by all planes.  crn: cosine_similarity's first operand.
+__device__ __forceinline__ void sr_mlp_cur_ray(float d0, float r0, float r1, float r2, float& cr0, float& cr1, float& cr2,
+                                               float& crn0, float& crn1, float& crn2) {
+#pragma clang fp contract(off)
+  const float X0 = d0 * r0, X1 = d0 * r1, X2 = d0 * r2;
+  const float cden = fmaxf(sqrtf((X0 * X0 + X1 * X1) + X2 * X2), 1e-12f);
+  cr0 = X0 / cden; cr1 = X1 / cden; cr2 = X2 / cden;
+  const float n1 = fmaxf(sqrtf((cr0 * cr0 + cr1 * cr1) + cr2 * cr2), 1e-5f);
+  crn0 = cr0 / n1; crn1 = cr1 / n1; crn2 = cr2 / n1;
+}
+
+// the four bilinear taps of a sample, 16 channels each, from the channels-last image `img`
+__device__ __forceinline__ void sr_mlp_load_taps(const float* img, const SrSample& smp, float4 (&taps)[16]) {
+  const float4* t_nw = reinterpret_cast<const float4*>(img + (size_t)smp.o_nw * 16);
+  const float4* t_ne = reinterpret_cast<const float4*>(img + (size_t)smp.o_ne * 16);
+  const float4* t_sw = reinterpret_cast<const float4*>(img + (size_t)smp.o_sw * 16);
+  const float4* t_se = reinterpret_cast<const float4*>(img + (size_t)smp.o_se * 16);
+#pragma unroll
+  for (int i = 0; i < 4; ++i) {
+    taps[i] = t_nw[i]; taps[4 + i] = t_ne[i]; taps[8 + i] = t_sw[i]; taps[12 + i] = t_se[i];
+  }
+}
+
 template <bool W1_LDS, bool W2_LDS>
 __global__ __launch_bounds__(256, 1) void sr_mlp_volume_kernel(SrMlpParams p) {
   extern __shared__ __attribute__((aligned(16))) float lds[];
@@ -292,27 +319,9 @@ __global__ __launch_bounds__(256, 1) void sr_mlp_volume_kernel(SrMlpParams p) {
     }
 
     float r0, r1, r2;
-    {
-#pragma clang fp contract(off)
-      const float* iK = p.invK + 16 * (size_t)b;
-      const float px = (float)x + 0.5f, py = (float)y + 0.5f;
-      r0 = iK[0] * px + iK[1] * py + iK[2];
-      r1 = iK[4] * px + iK[5] * py + iK[6];
-      r2 = iK[8] * px + iK[9] * py + iK[10];
-    }
-    // current-frame ray F.normalize(X) (cost_volume.py:641-651, eps 1e-12): X = d * r, so the ray does not depend
-    // on the plane beyond rounding; it is formed from plane 0 for every chunk (so results do not depend on how
-    // planes are chunked into work units) and shared by all planes.
+    sr_pixel_ray(p.invK + 16 * (size_t)b, x, y, r0, r1, r2);
     float cr0, cr1, cr2, crn0, crn1, crn2;
-    {
-#pragma clang fp contract(off)
-      const float d0 = plane_ptr[0];
-      const float X0 = d0 * r0, X1 = d0 * r1, X2 = d0 * r2;
-      const float cden = fmaxf(sqrtf((X0 * X0 + X1 * X1) + X2 * X2), 1e-12f);
-      cr0 = X0 / cden; cr1 = X1 / cden; cr2 = X2 / cden;
-      const float n1 = fmaxf(sqrtf((cr0 * cr0 + cr1 * cr1) + cr2 * cr2), 1e-5f);
-      crn0 = cr0 / n1; crn1 = cr1 / n1; crn2 = cr2 / n1;  // cosine_similarity's first operand
-    }
+    sr_mlp_cur_ray(plane_ptr[0], r0, r1, r2, cr0, cr1, cr2, crn0, crn1, crn2);
 
     // ---- depth-invariant part of layer 1 (weights straight from L2, once per unit) ----
     f32x16 hc[2][4];
@@ -358,15 +367,7 @@ __global__ __launch_bounds__(256, 1) void sr_mlp_volume_kernel(SrMlpParams p) {
       return __builtin_amdgcn_ballot_w64(active & smp.any_tap) == 0;
     };
     auto load_taps = [&](int k) {
-      const float* img = src_b + (size_t)k * N * C;
-      const float4* t_nw = reinterpret_cast<const float4*>(img + (size_t)smp.o_nw * C);
-      const float4* t_ne = reinterpret_cast<const float4*>(img + (size_t)smp.o_ne * C);
-      const float4* t_sw = reinterpret_cast<const float4*>(img + (size_t)smp.o_sw * C);
-      const float4* t_se = reinterpret_cast<const float4*>(img + (size_t)smp.o_se * C);
-#pragma unroll
-      for (int i = 0; i < 4; ++i) {
-        taps[i] = t_nw[i]; taps[4 + i] = t_ne[i]; taps[8 + i] = t_sw[i]; taps[12 + i] = t_se[i];
-      }
+      sr_mlp_load_taps(src_b + (size_t)k * N * C, smp, taps);
     };
     // pieces of the per-view feature assembly (o = fn or f); the ray pieces need no taps
     float rv0, rv1, rv2, rsd, rdot;
@@ -835,24 +836,9 @@ __global__ __launch_bounds__(256, 1) void sr_mlp_volume_split_kernel(SrMlpParams
     for (int c = 0; c < C; ++c) cur[c] = p.cur[((size_t)b * C + c) * N + pc];
 
     float r0, r1, r2;
-    {
-#pragma clang fp contract(off)
-      const float* iK = p.invK + 16 * (size_t)b;
-      const float px = (float)x + 0.5f, py = (float)y + 0.5f;
-      r0 = iK[0] * px + iK[1] * py + iK[2];
-      r1 = iK[4] * px + iK[5] * py + iK[6];
-      r2 = iK[8] * px + iK[9] * py + iK[10];
-    }
+    sr_pixel_ray(p.invK + 16 * (size_t)b, x, y, r0, r1, r2);
     float cr0, cr1, cr2, crn0, crn1, crn2;
-    {
-#pragma clang fp contract(off)
-      const float d0 = plane_ptr[0];
-      const float X0 = d0 * r0, X1 = d0 * r1, X2 = d0 * r2;
-      const float cden = fmaxf(sqrtf((X0 * X0 + X1 * X1) + X2 * X2), 1e-12f);
-      cr0 = X0 / cden; cr1 = X1 / cden; cr2 = X2 / cden;
-      const float n1 = fmaxf(sqrtf((cr0 * cr0 + cr1 * cr1) + cr2 * cr2), 1e-5f);
-      crn0 = cr0 / n1; crn1 = cr1 / n1; crn2 = cr2 / n1;
-    }
+    sr_mlp_cur_ray(plane_ptr[0], r0, r1, r2, cr0, cr1, cr2, crn0, crn1, crn2);
 
     // depth-invariant part of layer 1: fp32 MFMA, once per unit (as in sr_mlp_volume_kernel)
     f32x16 hc[2][4];
@@ -886,15 +872,7 @@ __global__ __launch_bounds__(256, 1) void sr_mlp_volume_split_kernel(SrMlpParams
     bool any_depth, any_bounds;
     auto issue_view = [&](int k) {
       sr_project_sample(geom_b + k * SR_GEOM_STRIDE, X0, X1, X2, p.h, p.w, p.inv_w, p.inv_h, smp);
-      const float* img = src_b + (size_t)k * N * C;
-      const float4* t_nw = reinterpret_cast<const float4*>(img + (size_t)smp.o_nw * C);
-      const float4* t_ne = reinterpret_cast<const float4*>(img + (size_t)smp.o_ne * C);
-      const float4* t_sw = reinterpret_cast<const float4*>(img + (size_t)smp.o_sw * C);
-      const float4* t_se = reinterpret_cast<const float4*>(img + (size_t)smp.o_se * C);
-#pragma unroll
-      for (int i = 0; i < 4; ++i) {
-        taps[i] = t_nw[i]; taps[4 + i] = t_ne[i]; taps[8 + i] = t_sw[i]; taps[12 + i] = t_se[i];
-      }
+      sr_mlp_load_taps(src_b + (size_t)k * N * C, smp, taps);
     };
     float rv0, rv1, rv2, rsd, rdot;
 #define SR_SPLIT_VIEW                                                                     \
@@ -1204,6 +1182,41 @@ extern "C" int sr_mlp_pack_weights(const float* W1, const float* b1, const float
   return sr_hip_rc(hipGetLastError());
 }
 
+// One body behind sr_mlp_volume_fwd and sr_mlp_volume_fwd_nhwc.  nhwc = false: cur is planar [B,16,h,w] and src [B*K,16,h,w]
+// is transposed into the workspace (sr_volume_prepare).  nhwc = true: both already are channels-last (the matching
+// encoder's output buffer) -- no transposing copy of either operand, the sweep reads cur [B, h*w, 16] and src
+// [B*K, h*w, 16] where the caller keeps them.
+static int sr_mlp_volume_run(bool nhwc, const float* cur, const float* src, const float* K_src, const float* T_src_cur,
+                             const float* T_cur_src, const float* invK_cur, const float* planes, int64_t ps_b,
+                             int64_t ps_d, int64_t ps_y, int64_t ps_x, const float* W1, const float* b1,
+                             const float* W2, const float* b2, const float* W3, const float* b3, int hidden,
+                             float leaky_slope, int B, int K, int C, int h, int w, int D, float* out_cv,
+                             int64_t cv_sb, int64_t cv_sd, int64_t cv_sp, float* out_lowest, uint8_t* out_mask,
+                             int reserve_cus, void* workspace, size_t workspace_bytes, void* stream_) {
+  if (B < 0 || K <= 0 || C <= 0 || h <= 0 || w <= 0 || D <= 0 || reserve_cus < 0) return SR_ERR_INVALID_ARGUMENT;
+  if (B == 0) return SR_OK;
+  if (!T_cur_src) return SR_ERR_INVALID_ARGUMENT;
+  if (nhwc) {
+    if (!cur || !src || !K_src || !T_src_cur || !workspace) return SR_ERR_INVALID_ARGUMENT;
+    if (((size_t)cur | (size_t)src) & 15) return SR_ERR_INVALID_ARGUMENT;   // a pixel is read as four 16-byte pieces
+  }
+  if (hidden != SR_HID || C != 16) return SR_ERR_UNSUPPORTED;
+  if (nhwc) {
+    const int split = sr_mlp_split_mode();
+    if (split < 0) return SR_ERR_INVALID_ARGUMENT;
+    if (split) return SR_ERR_UNSUPPORTED;   // the split-precision kernel reads cur planar: sr_mlp_volume_fwd serves it
+  }
+  if (workspace_bytes < sr_mlp_volume_workspace_bytes(B, K, C, h, w, hidden)) return SR_ERR_WORKSPACE_TOO_SMALL;
+  int rc = nhwc ? sr_launch_geom(K_src, T_src_cur, T_cur_src, sr_ws_geom(workspace), B * K, (hipStream_t)stream_)
+                : sr_volume_prepare(src, K_src, T_src_cur, T_cur_src, B, K, C, h, w, workspace, workspace_bytes, stream_);
+  if (rc) return rc;
+  rc = sr_mlp_pack_weights(W1, b1, W2, b2, W3, b3, hidden, B, K, C, h, w, workspace, workspace_bytes, stream_);
+  if (rc) return rc;
+  return sr_mlp_volume_sweep_reserved(cur, nhwc ? src : nullptr, invK_cur, planes, ps_b, ps_d, ps_y, ps_x, leaky_slope, B, K,
+                                      C, h, w, D, out_cv, cv_sb, cv_sd, cv_sp, out_lowest, out_mask, reserve_cus, workspace,
+                                      workspace_bytes, stream_);
+}
+
 extern "C" int sr_mlp_volume_fwd(const float* cur, const float* src, const float* K_src, const float* T_src_cur,
                                  const float* T_cur_src, const float* invK_cur, const float* planes, int64_t ps_b,
                                  int64_t ps_d, int64_t ps_y, int64_t ps_x, const float* W1, const float* b1,
@@ -1211,22 +1224,11 @@ extern "C" int sr_mlp_volume_fwd(const float* cur, const float* src, const float
                                  float leaky_slope, int B, int K, int C, int h, int w, int D, float* out_cv,
                                  int64_t cv_sb, int64_t cv_sd, int64_t cv_sp, float* out_lowest, uint8_t* out_mask,
                                  int reserve_cus, void* workspace, size_t workspace_bytes, void* stream_) {
-  if (B < 0 || K <= 0 || C <= 0 || h <= 0 || w <= 0 || D <= 0 || reserve_cus < 0) return SR_ERR_INVALID_ARGUMENT;
-  if (B == 0) return SR_OK;
-  if (!T_cur_src) return SR_ERR_INVALID_ARGUMENT;
-  if (hidden != SR_HID || C != 16) return SR_ERR_UNSUPPORTED;
-  if (workspace_bytes < sr_mlp_volume_workspace_bytes(B, K, C, h, w, hidden)) return SR_ERR_WORKSPACE_TOO_SMALL;
-  int rc = sr_volume_prepare(src, K_src, T_src_cur, T_cur_src, B, K, C, h, w, workspace, workspace_bytes, stream_);
-  if (rc) return rc;
-  rc = sr_mlp_pack_weights(W1, b1, W2, b2, W3, b3, hidden, B, K, C, h, w, workspace, workspace_bytes, stream_);
-  if (rc) return rc;
-  return sr_mlp_volume_sweep_reserved(cur, nullptr, invK_cur, planes, ps_b, ps_d, ps_y, ps_x, leaky_slope, B, K, C, h, w, D,
-                                      out_cv, cv_sb, cv_sd, cv_sp, out_lowest, out_mask, reserve_cus, workspace,
-                                      workspace_bytes, stream_);
+  return sr_mlp_volume_run(false, cur, src, K_src, T_src_cur, T_cur_src, invK_cur, planes, ps_b, ps_d, ps_y, ps_x, W1, b1, W2, b2, W3, b3,
+                           hidden, leaky_slope, B, K, C, h, w, D, out_cv, cv_sb, cv_sd, cv_sp, out_lowest, out_mask, reserve_cus,
+                           workspace, workspace_bytes, stream_);
 }
 
-// sr_mlp_volume_fwd on features that already are channels-last (the matching encoder's output buffer): no transposing copy
-// of either operand, the sweep reads cur [B, h*w, 16] and src [B*K, h*w, 16] where the caller keeps them.
 extern "C" int sr_mlp_volume_fwd_nhwc(const float* cur, const float* src, const float* K_src, const float* T_src_cur,
                                       const float* T_cur_src, const float* invK_cur, const float* planes, int64_t ps_b,
                                       int64_t ps_d, int64_t ps_y, int64_t ps_x, const float* W1, const float* b1,
@@ -1234,20 +1236,7 @@ extern "C" int sr_mlp_volume_fwd_nhwc(const float* cur, const float* src, const 
                                       float leaky_slope, int B, int K, int C, int h, int w, int D, float* out_cv,
                                       int64_t cv_sb, int64_t cv_sd, int64_t cv_sp, float* out_lowest, uint8_t* out_mask,
                                       int reserve_cus, void* workspace, size_t workspace_bytes, void* stream_) {
-  if (B < 0 || K <= 0 || C <= 0 || h <= 0 || w <= 0 || D <= 0 || reserve_cus < 0) return SR_ERR_INVALID_ARGUMENT;
-  if (B == 0) return SR_OK;
-  if (!cur || !src || !K_src || !T_src_cur || !T_cur_src || !workspace) return SR_ERR_INVALID_ARGUMENT;
-  if (((size_t)cur | (size_t)src) & 15) return SR_ERR_INVALID_ARGUMENT;   // a pixel is read as four 16-byte pieces
-  if (hidden != SR_HID || C != 16) return SR_ERR_UNSUPPORTED;
-  const int split = sr_mlp_split_mode();
-  if (split < 0) return SR_ERR_INVALID_ARGUMENT;
-  if (split) return SR_ERR_UNSUPPORTED;   // the split-precision kernel reads cur planar: sr_mlp_volume_fwd serves it
-  if (workspace_bytes < sr_mlp_volume_workspace_bytes(B, K, C, h, w, hidden)) return SR_ERR_WORKSPACE_TOO_SMALL;
-  int rc = sr_launch_geom(K_src, T_src_cur, T_cur_src, sr_ws_geom(workspace), B * K, (hipStream_t)stream_);
-  if (rc) return rc;
-  rc = sr_mlp_pack_weights(W1, b1, W2, b2, W3, b3, hidden, B, K, C, h, w, workspace, workspace_bytes, stream_);
-  if (rc) return rc;
-  return sr_mlp_volume_sweep_reserved(cur, src, invK_cur, planes, ps_b, ps_d, ps_y, ps_x, leaky_slope, B, K, C, h, w, D,
-                                      out_cv, cv_sb, cv_sd, cv_sp, out_lowest, out_mask, reserve_cus, workspace,
-                                      workspace_bytes, stream_);
+  return sr_mlp_volume_run(true, cur, src, K_src, T_src_cur, T_cur_src, invK_cur, planes, ps_b, ps_d, ps_y, ps_x, W1, b1, W2, b2, W3, b3,
+                           hidden, leaky_slope, B, K, C, h, w, D, out_cv, cv_sb, cv_sd, cv_sp, out_lowest, out_mask, reserve_cus,
+                           workspace, workspace_bytes, stream_);
 }

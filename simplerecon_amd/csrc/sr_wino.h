@@ -84,8 +84,75 @@ __device__ __forceinline__ float4 wn_io_load(__amdgpu_buffer_rsrc_t r, unsigned 
   return make_float4(v.x, v.y, v.z, v.w);
 }
 
-// (`SR_WN_PIN`: an empty asm that makes a value opaque at that point, so that addresses derived from it are formed there
-// as register + immediate instead of being hoisted out of the loops, one register -- then one spill -- each)
+// `SR_WN_PIN`: an empty asm that makes a value opaque at that point, so that addresses derived from it are formed there
+// as register + immediate instead of being hoisted out of the loops, one register -- then one spill -- each.
+#define SR_WN_PIN(...) asm volatile("" : __VA_ARGS__)
+
+// ---- stages shared by sr_wino_kernel (sr_wino.hip) and its split-precision twin (sr_wino_split.hip) ----
+
+// Region coordinates of work item wk of a grid of `xcd_g` workgroups, NT N-tiles per workgroup.
+// XCD-aware work order.  Workgroup b runs on XCD b % 8 (round-robin dispatch) and each XCD has its own L2.  In round r
+// the grid works on items [r G, (r + 1) G): give XCD x the CONTIGUOUS eighth [r G + x G/8, r G + (x + 1) G/8) of them
+// (consecutive items are horizontally adjacent regions, G/8 of them about three region rows), so that the halo
+// pixels two neighbouring regions share are fetched into ONE L2 instead of two (r02 PMC: 1.40x the algorithmic
+// bytes).  The last, partial round keeps the plain order.
+struct WnRegion { int b, oy0, ox0, co0, ks; };
+template <int NT>
+__device__ __forceinline__ WnRegion wn_decode(const SrWinoParams& p, int wk, int xcd_g) {
+  if (p.xcd_order && (xcd_g & 7) == 0) {
+    const int r0 = wk / xcd_g * xcd_g;
+    if (r0 + xcd_g <= p.total) { const int bb = wk - r0; wk = r0 + (bb & 7) * (xcd_g >> 3) + (bb >> 3); }
+  }
+  WnRegion r;
+  r.ks = wk % p.ksplit; wk /= p.ksplit;
+  const int cb = wk % p.co_blocks; wk /= p.co_blocks;
+  const int rx = wk % p.regions_x; wk /= p.regions_x;
+  const int ry = wk % p.regions_y;
+  r.b = wk / p.regions_y;
+  r.oy0 = ry * (2 * WN_TR); r.ox0 = rx * (2 * WN_TC); r.co0 = cb * (32 * NT);
+  return r;
+}
+
+// LDS side of the staging: element e -> pixel e >> 2, quad e & 3.  The 48 thread slots beyond the 720 elements of a
+// patch write their (zero) registers into the pad quad of a pixel row instead of being branched around.
+// st_lds0: slots 0 / 1 (+ it * 64 pixels), st_lds2: slot 2.
+__device__ __forceinline__ void wn_stage_lds(int tid, int& st_lds0, int& st_lds2) {
+  static_assert(WN_STAGE_PER_THREAD == 3 && 2 * 256 < WN_STAGE_ELEMS, "only the third slot of a thread can be a spare");
+  st_lds0 = (tid >> 2) * WN_ROW + 4 * (tid & 3);
+  st_lds2 = tid + 512 < WN_STAGE_ELEMS ? st_lds0 + 128 * WN_ROW : (tid + 512 - WN_STAGE_ELEMS) * WN_ROW + 16;
+}
+__device__ __forceinline__ void wn_stage_store(const float4 (&stg)[WN_STAGE_PER_THREAD], float* raw, int st_lds0, int st_lds2) {
+  *reinterpret_cast<float4*>(&raw[st_lds0]) = stg[0];
+  *reinterpret_cast<float4*>(&raw[st_lds0 + 64 * WN_ROW]) = stg[1];
+  *reinterpret_cast<float4*>(&raw[st_lds2]) = stg[2];
+}
+
+// In-register input transform.  Wave w produces the frequency ROW ur = w of V = B^T d B (the rows it alone multiplies).
+// Row ur of B^T d needs two patch rows: (0,2) d0-d2, (1,2) d1+d2, (2,1) d2-d1, (1,3) d1-d3.  Lane (i, kk) does it for
+// tile i (the MFMA row it feeds) and the channel quads 2g + kk -- the A operands of its own MFMAs.
+// The two patch rows are ONE register each (a, b): every other term of a load address is an immediate (left to itself
+// the compiler hoists the 16 distinct addresses out of the work loop and spills them; see SR_WN_PIN).
+__device__ __forceinline__ void wn_transform_role(int wave, int i, int kk, float& t_sign, int& rv_a, int& rv_b) {
+  const int t_ra = wave == 0 ? 0 : (wave == 2 ? 2 : 1), t_rb = wave == 0 ? 2 : (wave == 1 ? 2 : (wave == 2 ? 1 : 3));
+  t_sign = wave == 1 ? 1.0f : -1.0f;
+  const int rv_base = ((2 * (i >> 3)) * WN_PW + 2 * (i & 7)) * WN_ROW + 4 * kk;   // patch offset of tile i, quad kk
+  rv_a = rv_base + t_ra * WN_PW * WN_ROW;
+  rv_b = rv_base + t_rb * WN_PW * WN_ROW;
+}
+__device__ __forceinline__ float4 wn_rv_fma(float t_sign, const float4 da, const float4 db) {
+  const wn_f2 sg = {t_sign, t_sign};
+  const wn_f2 lo = __builtin_elementwise_fma(sg, wn_f2{db.x, db.y}, wn_f2{da.x, da.y});
+  const wn_f2 hi = __builtin_elementwise_fma(sg, wn_f2{db.z, db.w}, wn_f2{da.z, da.w});
+  return make_float4(lo.x, lo.y, hi.x, hi.y);
+}
+__device__ __forceinline__ void wn_rv_ld(const float* raw, int rv_a, int rv_b, int g, int c, float4& da, float4& db) {
+  da = *reinterpret_cast<const float4*>(&raw[rv_a + 8 * g + c * WN_ROW]);
+  db = *reinterpret_cast<const float4*>(&raw[rv_b + 8 * g + c * WN_ROW]);
+}
+// wn_rv_row: the four frequencies uc = 0..3 of a row of B^T d from its four columns = the A operands of steps (g, uc).
+__device__ __forceinline__ void wn_rv_row(const float4 (&w)[4], float4 (&a)[4]) {
+  a[0] = f4sub(w[0], w[2]); a[1] = f4add(w[1], w[2]); a[2] = f4sub(w[2], w[1]); a[3] = f4sub(w[1], w[3]);
+}
 
 // ---- split-precision variant (sr_wino_split.hip; fenced experiment, SR_WINO_SPLIT=bf16|f16) ----
 int sr_wino_split_mode();   // 0 off, 1 bf16, 2 f16, -1 unknown value (read per call)

@@ -77,18 +77,9 @@ __global__ __launch_bounds__(256, NT == 1 ? SR_WINO_NT1_WAVES : SR_WINO_WAVES) v
   static_assert(8 % SR_WINO_NB == 0 && SR_WINO_PD < SR_WINO_NB, "the register rotation must line up across slabs");
   constexpr int NB = SR_WINO_NB, PD = SR_WINO_PD;  // weight prefetch: PD steps ahead through NB rotating register sets
 
-  // Transform role: wave w produces the frequency ROW ur = w of V = B^T d B (the rows it alone multiplies).  Row ur of
-  // B^T d needs two patch rows: (0,2) d0-d2, (1,2) d1+d2, (2,1) d2-d1, (1,3) d1-d3.  Lane (i, kk) does it for tile i (the
-  // MFMA row it feeds) and the channel quads 2g + kk -- the A operands of its own MFMAs.
-  const int t_ra = wave == 0 ? 0 : (wave == 2 ? 2 : 1), t_rb = wave == 0 ? 2 : (wave == 1 ? 2 : (wave == 2 ? 1 : 3));
-  const float t_sign = wave == 1 ? 1.0f : -1.0f;
-  const int rv_base = ((2 * (i >> 3)) * WN_PW + 2 * (i & 7)) * WN_ROW + 4 * kk;   // patch offset of tile i, quad kk
-  // the two patch rows this wave's transform reads, as ONE register each: every other term of an rv_ld address is an
-  // immediate (left to itself the compiler hoists the 16 distinct addresses out of the work loop and spills them)
-  int rv_a = rv_base + t_ra * WN_PW * WN_ROW, rv_b = rv_base + t_rb * WN_PW * WN_ROW;
-  // (`SR_WN_PIN`: an empty asm that makes the value opaque at this point, so that addresses derived from it are formed
-  // HERE as register + immediate instead of being hoisted out of the loops, one register -- then one spill -- each)
-#define SR_WN_PIN(...) asm volatile("" : __VA_ARGS__)
+  float t_sign;   // transform role of this wave: frequency row ur = wave of V = B^T d B
+  int rv_a, rv_b;
+  wn_transform_role(wave, i, kk, t_sign, rv_a, rv_b);
 
 #ifdef SR_WINO_TRACE
   int tr_region = -1;
@@ -99,27 +90,16 @@ __global__ __launch_bounds__(256, NT == 1 ? SR_WINO_NT1_WAVES : SR_WINO_WAVES) v
   }
 #endif
   // Region coordinates of a work item and the per-thread staging offsets of its 10x18 input patch.
-  struct Region { int b, oy0, ox0, co0, ks; };
+  // (The stages shared with sr_wino_split_kernel, sr_wino.h, are called through lambdas of this kernel: called directly the
+  // same functions give the same instructions in another order, and this kernel's code object is kept byte-identical.)
+  typedef WnRegion Region;
   // XCD-aware work order.  Workgroup b runs on XCD b % 8 (round-robin dispatch) and each XCD has its own L2.  In round r
   // the grid works on items [r G, (r + 1) G): give XCD x the CONTIGUOUS eighth [r G + x G/8, r G + (x + 1) G/8) of them
   // (consecutive items are horizontally adjacent regions, G/8 of them about three region rows), so that the halo
   // pixels two neighbouring regions share are fetched into ONE L2 instead of two (r02 PMC: 1.40x the algorithmic
   // bytes).  The last, partial round keeps the plain order.
   const int xcd_g = (int)gridDim.x;
-  auto decode = [&](int wk) {
-    if (p.xcd_order && (xcd_g & 7) == 0) {
-      const int r0 = wk / xcd_g * xcd_g;
-      if (r0 + xcd_g <= p.total) { const int bb = wk - r0; wk = r0 + (bb & 7) * (xcd_g >> 3) + (bb >> 3); }
-    }
-    Region r;
-    r.ks = wk % p.ksplit; wk /= p.ksplit;
-    const int cb = wk % p.co_blocks; wk /= p.co_blocks;
-    const int rx = wk % p.regions_x; wk /= p.regions_x;
-    const int ry = wk % p.regions_y;
-    r.b = wk / p.regions_y;
-    r.oy0 = ry * (2 * WN_TR); r.ox0 = rx * (2 * WN_TC); r.co0 = cb * (32 * NT);
-    return r;
-  };
+  auto decode = [&](int wk) { return wn_decode<NT>(p, wk, xcd_g); };
   // ---- staging: global -> registers -> LDS ----
   // Vector path (VEC4): lane offsets in BYTES relative to the image base, through the buffer descriptor `rs_in`.  For an
   // interior region (the whole 10x18 patch inside the image) they are the per-thread constants `rel` plus the scalar
@@ -199,17 +179,9 @@ __global__ __launch_bounds__(256, NT == 1 ? SR_WINO_NT1_WAVES : SR_WINO_WAVES) v
       }
     }
   };
-  // LDS side of the staging: element e -> pixel e >> 2, quad e & 3.  The 48 thread slots beyond the 720 elements of a
-  // patch write their (zero) registers into the pad quad of a pixel row instead of being branched around.
-  static_assert(WN_STAGE_PER_THREAD == 3 && 2 * 256 < WN_STAGE_ELEMS, "only the third slot of a thread can be a spare");
-  int st_lds0 = (tid >> 2) * WN_ROW + 4 * (tid & 3);   // slots 0 / 1: + it * 64 pixels
-  int st_lds2 = tid + 512 < WN_STAGE_ELEMS ? st_lds0 + 128 * WN_ROW : (tid + 512 - WN_STAGE_ELEMS) * WN_ROW + 16;
-  auto stage_store = [&](const float4 (&stg)[WN_STAGE_PER_THREAD], float* raw) {
-    *reinterpret_cast<float4*>(&raw[st_lds0]) = stg[0];
-    *reinterpret_cast<float4*>(&raw[st_lds0 + 64 * WN_ROW]) = stg[1];
-    *reinterpret_cast<float4*>(&raw[st_lds2]) = stg[2];
-  };
-  (void)rv_base;
+  int st_lds0, st_lds2;   // LDS side of the staging
+  wn_stage_lds(tid, st_lds0, st_lds2);
+  auto stage_store = [&](const float4 (&stg)[WN_STAGE_PER_THREAD], float* raw) { wn_stage_store(stg, raw, st_lds0, st_lds2); };
   // weight fragments: scalar record base (SGPR pair) + a 32-bit lane index -- the saddr form of global_load, no 64-bit
   // vector address arithmetic in the MFMA stream
   unsigned wu_lane = 0;   // BYTE offset of this lane's fragment inside a record (a 32-bit offset: what the saddr form takes)
@@ -220,27 +192,14 @@ __global__ __launch_bounds__(256, NT == 1 ? SR_WINO_NT1_WAVES : SR_WINO_WAVES) v
 #pragma unroll
     for (int n = 0; n < NT; ++n) dst[n] = *reinterpret_cast<const float4*>(wrec + (wu_lane + 512u * n));
   };
-  // rv_col(raw, g, c): row `ur = wave` of B^T d at patch column c, channel quad 2g + kk; rv_row: the four frequencies
-  // uc = 0..3 of that row from its four columns = the A operands of steps (g, uc).
-  auto rv_fma = [&](const float4 da, const float4 db) {
-    const wn_f2 sg = {t_sign, t_sign};
-    const wn_f2 lo = __builtin_elementwise_fma(sg, wn_f2{db.x, db.y}, wn_f2{da.x, da.y});
-    const wn_f2 hi = __builtin_elementwise_fma(sg, wn_f2{db.z, db.w}, wn_f2{da.z, da.w});
-    return make_float4(lo.x, lo.y, hi.x, hi.y);
-  };
-  auto rv_ld = [&](const float* raw, int g, int c, float4& da, float4& db) {
-    da = *reinterpret_cast<const float4*>(&raw[rv_a + 8 * g + c * WN_ROW]);
-    db = *reinterpret_cast<const float4*>(&raw[rv_b + 8 * g + c * WN_ROW]);
-  };
+  auto rv_fma = [&](const float4 da, const float4 db) { return wn_rv_fma(t_sign, da, db); };
+  auto rv_ld = [&](const float* raw, int g, int c, float4& da, float4& db) { wn_rv_ld(raw, rv_a, rv_b, g, c, da, db); };
   auto rv_col = [&](const float* raw, int g, int c) {
     float4 da, db;
     rv_ld(raw, g, c, da, db);
     return rv_fma(da, db);
   };
-  auto rv_row = [&](const float4 (&w)[4], float4 (&a)[4]) {
-    a[0] = f4sub(w[0], w[2]); a[1] = f4add(w[1], w[2]); a[2] = f4sub(w[2], w[1]); a[3] = f4sub(w[1], w[3]);
-  };
-
+  auto rv_row = [&](const float4 (&w)[4], float4 (&a)[4]) { wn_rv_row(w, a); };
   // Software pipeline: slab c of a region sits in raw buffer (c odd ? A : B); slab c+1 is fetched into registers at
   // the top of slab c and stored to the other buffer after step 3 (the last read of this wave's own transform of slab c
   // is in step 3, the other buffer's last readers finished a slab ago); the workgroup barrier sits after step 5, and

@@ -1,7 +1,9 @@
 // sr_wino_split.hip -- split-precision variant of the Winograd F(2x2, 3x3) convolution (gfx950).  A FENCED EXPERIMENT:
 // selected only by SR_WINO_SPLIT=bf16|f16 (read per call), never the default, never what bench.py's headline measures
-// (DESIGN.md 3.3e).  Same operator, tensors, launch plan, LDS staging, in-register input transform and epilogue as
-// sr_wino_kernel<NT, true, true> (sr_wino.hip; reference modules/layers.py:24-85); what changes is the multiply:
+// (DESIGN.md 3.3e).  The twin of sr_wino_kernel<NT, true, true> (sr_wino.hip): work-item decode, in-register input
+// transform and the LDS side of the staging are the shared stages of sr_wino.h.  Still copies of the twin's code, because
+// moving them into a shared function changed the fp32 kernel's machine code: the aiming and loads of the vector staging, the
+// vector epilogue (here with the 1 / USCALE fma), and the U = G g G^T element of the pack kernel.  What differs is the multiply:
 //   * every fp32 operand -- the transformed input V = B^T d B in the kernel, the transformed weight U = G g G^T at pack
 //     time -- is written as two 16-bit pieces, x = x_hi + x_lo (round-to-nearest each, the subtraction is exact);
 //   * a product is three products on the 16-bit matrix pipe, x_hi w_hi + x_hi w_lo + x_lo w_hi, exact in the fp32
@@ -90,7 +92,6 @@ __global__ void sr_wino_pack_split_kernel(const float* __restrict__ w, unsigned*
   }
 }
 
-#define WS_PIN(...) asm volatile("" : __VA_ARGS__)
 #ifndef SR_WS_NT1_WGS
 #define SR_WS_NT1_WGS 3   // workgroups per CU of the 32-channel instantiation: 3 fit its 46 KB of LDS and 168 registers (3 spills); the
 #endif                    // latency-bound split kernel gains 9 - 18 % on the 60x80 / 30x40 layers from the third (2: 45.9 / 55.1 us, 3: 42.0 / 45.1)
@@ -108,29 +109,14 @@ __global__ __launch_bounds__(256, NT == 1 ? SR_WS_NT1_WGS : 2) void sr_wino_spli
   const int chunks = (p.G >> 1) / p.ksplit;
   const int64_t rec = (int64_t)2 * p.Co_pad;
 
-  // transform role of wave w: frequency row ur = w of V = B^T d B (see sr_wino_kernel)
-  const int t_ra = wave == 0 ? 0 : (wave == 2 ? 2 : 1), t_rb = wave == 0 ? 2 : (wave == 1 ? 2 : (wave == 2 ? 1 : 3));
-  const float t_sign = wave == 1 ? 1.0f : -1.0f;
-  const int rv_base = ((2 * (i >> 3)) * WN_PW + 2 * (i & 7)) * WN_ROW + 4 * kk;
-  int rv_a = rv_base + t_ra * WN_PW * WN_ROW, rv_b = rv_base + t_rb * WN_PW * WN_ROW;
+  float t_sign;
+  int rv_a, rv_b;
+  wn_transform_role(wave, i, kk, t_sign, rv_a, rv_b);
 
-  struct Region { int b, oy0, ox0, co0, ks; };
+  typedef WnRegion Region;
   const int xcd_g = (int)gridDim.x;
-  auto decode = [&](int wk) {
-    if (p.xcd_order && (xcd_g & 7) == 0) {
-      const int r0 = wk / xcd_g * xcd_g;
-      if (r0 + xcd_g <= p.total) { const int bb = wk - r0; wk = r0 + (bb & 7) * (xcd_g >> 3) + (bb >> 3); }
-    }
-    Region r;
-    r.ks = wk % p.ksplit; wk /= p.ksplit;
-    const int cb = wk % p.co_blocks; wk /= p.co_blocks;
-    const int rx = wk % p.regions_x; wk /= p.regions_x;
-    const int ry = wk % p.regions_y;
-    r.b = wk / p.regions_y;
-    r.oy0 = ry * (2 * WN_TR); r.ox0 = rx * (2 * WN_TC); r.co0 = cb * (32 * NT);
-    return r;
-  };
-  // ---- staging: global -> registers -> LDS (the vector path of sr_wino_kernel) ----
+  auto decode = [&](int wk) { return wn_decode<NT>(p, wk, xcd_g); };
+  // ---- staging: global -> registers -> LDS (copy of the vector path of sr_wino_kernel's aim / stage_load) ----
   int offs[WN_STAGE_PER_THREAD];
   unsigned s_org = 0;
   __amdgpu_buffer_rsrc_t rs_in = sr_rsrc(p.in, 0);
@@ -175,14 +161,9 @@ __global__ __launch_bounds__(256, NT == 1 ? SR_WS_NT1_WGS : 2) void sr_wino_spli
         stg[it] = wn_io_load<0>(rs_in, (unsigned)offs[it], so);
     }
   };
-  static_assert(WN_STAGE_PER_THREAD == 3 && 2 * 256 < WN_STAGE_ELEMS, "only the third slot of a thread can be a spare");
-  int st_lds0 = (tid >> 2) * WN_ROW + 4 * (tid & 3);
-  int st_lds2 = tid + 512 < WN_STAGE_ELEMS ? st_lds0 + 128 * WN_ROW : (tid + 512 - WN_STAGE_ELEMS) * WN_ROW + 16;
-  auto stage_store = [&](const float4 (&stg)[WN_STAGE_PER_THREAD], float* raw) {
-    *reinterpret_cast<float4*>(&raw[st_lds0]) = stg[0];
-    *reinterpret_cast<float4*>(&raw[st_lds0 + 64 * WN_ROW]) = stg[1];
-    *reinterpret_cast<float4*>(&raw[st_lds2]) = stg[2];
-  };
+  int st_lds0, st_lds2;
+  wn_stage_lds(tid, st_lds0, st_lds2);
+  auto stage_store = [&](const float4 (&stg)[WN_STAGE_PER_THREAD], float* raw) { wn_stage_store(stg, raw, st_lds0, st_lds2); };
   // weight fragments: step s = (uc = s >> 1, piece = s & 1) -> record (xi = 4 wave + uc, 2 ch + piece)
   unsigned wu_lane = 0;
   auto load_b = [&](int ch, int s, sr_u4 (&dst)[NT]) {
@@ -191,20 +172,12 @@ __global__ __launch_bounds__(256, NT == 1 ? SR_WS_NT1_WGS : 2) void sr_wino_spli
 #pragma unroll
     for (int n = 0; n < NT; ++n) dst[n] = *reinterpret_cast<const sr_u4*>(wrec + (wu_lane + 512u * n));
   };
-  auto rv_fma = [&](const float4 da, const float4 db) {
-    const wn_f2 sg = {t_sign, t_sign};
-    const wn_f2 lo = __builtin_elementwise_fma(sg, wn_f2{db.x, db.y}, wn_f2{da.x, da.y});
-    const wn_f2 hi = __builtin_elementwise_fma(sg, wn_f2{db.z, db.w}, wn_f2{da.z, da.w});
-    return make_float4(lo.x, lo.y, hi.x, hi.y);
-  };
   auto rv_col = [&](const float* raw, int g, int c) {
-    const float4 da = *reinterpret_cast<const float4*>(&raw[rv_a + 8 * g + c * WN_ROW]);
-    const float4 db = *reinterpret_cast<const float4*>(&raw[rv_b + 8 * g + c * WN_ROW]);
-    return rv_fma(da, db);
+    float4 da, db;
+    wn_rv_ld(raw, rv_a, rv_b, g, c, da, db);
+    return wn_rv_fma(t_sign, da, db);
   };
-  auto rv_row = [&](const float4 (&w)[4], float4 (&a)[4]) {
-    a[0] = f4sub(w[0], w[2]); a[1] = f4add(w[1], w[2]); a[2] = f4sub(w[2], w[1]); a[3] = f4sub(w[1], w[3]);
-  };
+  auto rv_row = [&](const float4 (&w)[4], float4 (&a)[4]) { wn_rv_row(w, a); };
 
   float4 stg[WN_STAGE_PER_THREAD];
   const bool chain = !(chunks & 1);
@@ -218,7 +191,7 @@ __global__ __launch_bounds__(256, NT == 1 ? SR_WS_NT1_WGS : 2) void sr_wino_spli
     wu_lane = (unsigned)(kk * p.Co_pad + co0 + i) * 16u;
     const bool has_next = chain && (work + (int)gridDim.x < p.total);
     if (!staged) {
-      WS_PIN("+v"(st_lds0), "+v"(st_lds2));
+      SR_WN_PIN("+v"(st_lds0), "+v"(st_lds2));
       aim(reg);
       stage_load(sl0 * 16, stg);
       stage_store(stg, rawB);
@@ -241,7 +214,7 @@ __global__ __launch_bounds__(256, NT == 1 ? SR_WS_NT1_WGS : 2) void sr_wino_spli
       }
       const float* raw = (ch & 1) ? rawA : rawB;
       float* raw_next = (ch & 1) ? rawB : rawA;
-      WS_PIN("+v"(rv_a), "+v"(rv_b), "+v"(st_lds0), "+v"(st_lds2), "+v"(wu_lane));
+      SR_WN_PIN("+v"(rv_a), "+v"(rv_b), "+v"(st_lds0), "+v"(st_lds2), "+v"(wu_lane));
       // the pieces of frequencies 0 and 1 fly while the slab is transformed
 #pragma unroll
       for (int s = 0; s < 4; ++s) load_b(sl0 + ch, s, b_f[s]);
@@ -286,7 +259,7 @@ __global__ __launch_bounds__(256, NT == 1 ? SR_WS_NT1_WGS : 2) void sr_wino_spli
     slab(std::true_type{}, 0);
     for (int ch = 1; ch < chunks; ++ch) slab(std::false_type{}, ch);
 
-    // ---- epilogue: Y = A^T M A, + bias + residual, LeakyReLU, store (the vector epilogue of sr_wino_kernel) ----
+    // ---- epilogue: Y = A^T M A, + bias + residual, LeakyReLU, store (copy of sr_wino_kernel's vector epilogue) ----
     const bool partial = p.ksplit > 1;
     const float* __restrict__ resp = (p.res && !partial)
         ? reinterpret_cast<const float*>(reinterpret_cast<const char*>(p.res) + (int64_t)b * p.res_sb * ES) : nullptr;
@@ -324,7 +297,7 @@ __global__ __launch_bounds__(256, NT == 1 ? SR_WS_NT1_WGS : 2) void sr_wino_spli
       asm volatile("" : "+s"(neg1s));
       const wn_f2 neg1 = {neg1s, neg1s};
       unsigned rsp4 = (unsigned)p.res_sp * ES, osp4 = out_sp * ES;
-      WS_PIN("+s"(rsp4), "+s"(osp4));
+      SR_WN_PIN("+s"(rsp4), "+s"(osp4));
       const bool fast_leaky = slope >= 0.0f && slope <= 1.0f;
       const wn_f2 slope2 = {slope, slope};
       auto epilogue = [&](auto full_tag, auto res_tag) {
