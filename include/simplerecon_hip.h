@@ -388,14 +388,24 @@ int sr_conv3x3_wino_splitk_nhwc_fwd(const float* in, int64_t in_batch_stride, in
                                     int Cout, float leaky_slope, void* workspace, size_t workspace_bytes,
                                     void* stream);
 
-/* Name of the kernel instantiation sr_conv3x3_wino_nhwc_fwd launches for these arguments (the output-channel block
- * is chosen per launch); aligned_in / aligned_out = input / output+residual+bias rows are 16-byte aligned with
- * channel counts that are multiples of 4.  For profilers. */
-const char* sr_wino_kernel_name(int B, int H, int W, int Cin, int Cout, int aligned_in, int aligned_out);
+/* The F(2x2) launch plan of a shape: output-channel block `nt` (32 nt channels per work item) and split-K factor `ks`
+ * (either pointer may be NULL); `allow_split` = the launcher may split K (a usable workspace and the vector epilogue).  For
+ * tests and sweeps: a launch reports what it ran through sr_last_launch. */
+int sr_wino_conv_plan(int B, int H, int W, int Cin, int Cout, int allow_split, int* nt, int* ks);
 
-/* Name of the kernel instantiation sr_conv2d_nhwc_fwd launches for these arguments (tile shape is
- * chosen per launch); `aligned16` = input pointer / strides are 16-byte aligned.  For profilers. */
-const char* sr_conv_kernel_name(int B, int H, int W, int Cin, int Cout, int ksize, int stride, int aligned16);
+/* ---- what a launch ran ----
+ * The convolution launchers -- sr_conv2d_*_nhwc_fwd, sr_conv3x3_wino_*nhwc_fwd, sr_conv3x3_wino4_*nhwc_fwd, sr_pw_conv_*nhwc_fwd,
+ * sr_pw_conv_tiled_nhwc_fwd, sr_stem7x7_fwd, sr_conv1x1_stats_nhwc_fwd, sr_conv3x3_c16_nhwc_fwd -- note, at the branch that
+ * issues their main kernel, which instantiation that was and the padded problem it works through (a split-K finish or a pack
+ * kernel beside it is not noted).  sr_last_launch() reports the calling thread's note: the kernel's name as a profiler shows
+ * it, with the template arguments that were chosen per launch (`sr_wino_kernel<2, true, true>`, `sr_conv_kernel<3, 2, 1, 1, 8,
+ * true>`, `sr_wino4pp_kernel`; the tiled pointwise kernel by its workgroup tile and K split: `sr_pw_tiled_kernel<64x128, ks 2,
+ * false>`), and the FLOPs the kernel issues on that padded problem (2 per multiply-add; negative where none are counted: the
+ * direct convolution kernels).  The note is valid ON THE CALLING THREAD UNTIL ITS NEXT LAUNCHER CALL, and only after a launcher
+ * that returned SR_OK; reading it clears it, so SR_ERR_INVALID_ARGUMENT means no launcher has noted anything since the last
+ * read (or a NULL / empty buffer).  `name` is cut to name_capacity - 1 characters; 64 hold every name.  Costs the launchers a
+ * few thread-local integer stores; nothing is formatted before this call. */
+int sr_last_launch(char* name, int name_capacity, double* executed_flops);
 
 /* F.interpolate(scale_factor=2, mode="bilinear", align_corners=False) -- `upsample` of the
  * reference (utils/generic_utils.py:96-105) -- on channels-last data, [B,H,W,C] -> [B,2H,2W,C]. */

@@ -10,7 +10,7 @@ import torch
 
 _HERE = os.path.dirname(os.path.abspath(__file__))
 LIB_PATH = os.environ.get("SR_HIP_LIBRARY") or os.path.join(_HERE, "libsimplerecon_hip.so")   # override: ablation / trace builds
-ABI_VERSION = 3
+ABI_VERSION = 4
 
 _lib = None
 
@@ -138,7 +138,8 @@ SIGNATURES = {
     "sr_wino_splitk_workspace_bytes": (_sz, [_i, _i, _i, _i, _i]),
     "sr_conv3x3_wino_splitk_nhwc_fwd": (_i, [_p, _i64, _i, _p, _p, _p, _i64, _i, _p, _i64, _i, _i, _i, _i, _i, _i, _f,
                                              _p, _sz, _p]),
-    "sr_wino_kernel_name": (C.c_char_p, [_i, _i, _i, _i, _i, _i, _i]),
+    "sr_wino_conv_plan": (_i, [_i, _i, _i, _i, _i, _i, _p, _p]),
+    "sr_last_launch": (_i, [_p, _i, _p]),
     "sr_conv3x3_wino_nhwc_fwd": (_i, [_p, _i64, _i, _p, _p, _p, _i64, _i, _p, _i64, _i, _i, _i, _i, _i, _i, _f, _p]),
     "sr_wino4_packed_weight_floats": (_sz, [_i, _i]),
     "sr_wino4_pack_weights": (_i, [_p, _i, _i, _p, _p]),
@@ -146,7 +147,6 @@ SIGNATURES = {
     "sr_conv3x3_wino4_nhwc_fwd": (_i, [_p, _i64, _i, _p, _p, _p, _i64, _i, _p, _i64, _i, _i, _i, _i, _i, _i, _f, _p]),
     "sr_conv3x3_wino4_variant_nhwc_fwd": (_i, [_p, _i64, _i, _p, _p, _p, _i64, _i, _p, _i64, _i, _i, _i, _i, _i, _i, _f, _i,
                                                _p]),
-    "sr_conv_kernel_name": (C.c_char_p, [_i, _i, _i, _i, _i, _i, _i, _i]),
     "sr_upsample2x_nhwc_fwd": (_i, [_p, _i64, _i, _p, _i64, _i, _i, _i, _i, _i, _p]),
     "sr_exp_fwd": (_i, [_p, _p, _i64, _p]),
     "sr_stem_packed_weight_floats": (_sz, [_i]),
@@ -432,7 +432,7 @@ def call(name, device, *args, allow=()):
     """lib().<name>(*args, stream) with `device` current and torch's current stream on it as the trailing `void* stream`:
     ints, floats and None (NULL) go in as they are (`argtypes` converts them), anything else is a tensor and goes in as its
     device address.  A non-zero code raises HipLibraryError naming `name`, unless it is in `allow`: then it is returned.  For
-    entry points that launch; pure queries (workspace sizes, plans, kernel names) are plain lib() calls.  ops._launch and
+    entry points that launch; pure queries (workspace sizes, plans) are plain lib() calls.  ops._launch and
     what goes through ops._timed (the PROFILE bracket) call the library directly: batch-1 inference is host-bound on its
     ~250 conv launches per frame, and this frame costs half a microsecond per call."""
     ctx = on_device(device)
@@ -443,6 +443,14 @@ def call(name, device, *args, allow=()):
     if rc != 0 and rc not in allow:
         check(rc, name)
     return rc
+
+
+def last_launch():
+    """(kernel name, executed FLOPs or None) of the launcher call this thread just made, as the launcher itself noted them
+    (sr_last_launch: right after a launch that returned 0, once -- reading clears the note).  For ops.PROFILE records only."""
+    name, executed = C.create_string_buffer(64), C.c_double()
+    check(lib().sr_last_launch(C.byref(name), len(name), C.byref(executed)), "sr_last_launch")
+    return name.value.decode(), (executed.value if executed.value >= 0 else None)
 
 
 def refuse_autograd(*tensors):

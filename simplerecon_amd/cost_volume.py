@@ -459,18 +459,18 @@ class FeatureVolumeManager(CostVolumeManager):
         sb, sd, sp = self._volume_strides(vol)
         from . import ops   # (ops._timed: bench.py's in-step kernel table)
         cin, d = c * (k + 1) + 10 * k + 4, self.num_depth_bins
-        record = lambda: ("sr_mlp_volume_fwd", 2.0 * (cin * hidden + hidden * hidden + hidden) * b * d * h * w, (), None)
+        flops = 2.0 * (cin * hidden + hidden * hidden + hidden) * b * d * h * w
         with _lib.SPLIT_GUARD:   # (SR_MLP_SPLIT is read by the packing and by the sweep inside this one call)
             if in_place and _lib.get_option("SR_MLP_SPLIT") != 0:   # the split-precision kernel reads cur planar
                 cur, src, in_place = cur.contiguous(), src.contiguous(), False
             entry = "sr_mlp_volume_fwd_nhwc" if in_place else "sr_mlp_volume_fwd"
             rc = ops._timed(
-                dev, record, getattr(lib, entry),
+                dev, flops, (), getattr(lib, entry),
                 _lib.ptr(cur), _lib.ptr(src), _lib.ptr(Ks), _lib.ptr(T), _lib.ptr(Tp), _lib.ptr(invK),
                 _lib.ptr(planes), *planes.stride(), *[_lib.ptr(t) for t in params], hidden,
                 0.01,  # nn.LeakyReLU default slope (reference networks.py:139)
                 b, k, c, h, w, d, _lib.ptr(vol), sb, sd, sp, _lib.ptr(lowest),
-                _lib.ptr(mask), int(reserve_cus), _lib.ptr(ws), ws.numel(), _lib.stream_ptr(dev))
+                _lib.ptr(mask), int(reserve_cus), _lib.ptr(ws), ws.numel(), _lib.stream_ptr(dev), name="sr_mlp_volume_fwd")
         _lib.check(rc, entry)
         return vol, lowest, mask
 

@@ -25,6 +25,15 @@ int sr_device_cus();
 // runtime is asked once and again only for a larger size; a refusal is not remembered.  Returns the runtime's error.
 hipError_t sr_allow_lds(const void* kernel, size_t bytes);
 
+// What the calling thread's last launcher call ran (sr_options.hip): the launch site notes the kernel family, the integers
+// that selected the template arguments (a..f, in the kernel's order: see sr_last_launch) and the padded problem the kernel
+// works through -- m x n x k multiplies, m = 0 where no such count is kept.  Plain thread-local stores; sr_last_launch turns
+// them into the record's kernel name and executed FLOPs.  A launcher with several kernels notes its main one.
+enum SrKernel { SR_K_NONE = 0, SR_K_CONV, SR_K_WINO, SR_K_WINO_SPLIT, SR_K_WINO4, SR_K_PW, SR_K_PW_TILED, SR_K_STEM, SR_K_C1S,
+                SR_K_T16 };
+struct SrLaunchNote { int kernel, a, b, c, d, e, f; int64_t m, n, k; };
+void sr_note_launch(const SrLaunchNote& note);
+
 // Second stages of the deterministic backward sums (sr_conv_bwd.hip), shared with their 16-bit forms (sr_conv16_wgrad.hip):
 // d_weight[co][ci][tap] = the `per` partial [tap][64 co][64 ci] slabs of each (co, ci) block added in index order, and
 // d_bias[c] = the [blocks][C] partial sums added in block order.  Each returns the launch's error code.

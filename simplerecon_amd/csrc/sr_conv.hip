@@ -537,6 +537,7 @@ static int sr_conv_launch(SrConvParams& p, int B, int nt, hipStream_t stream) {
   if (blocks > p.total_tiles) blocks = p.total_tiles;
   dim3 grid(blocks), block(256);
   const bool v4 = p.vec4 && (p.Cin % 4 == 0);
+  sr_note_launch({SR_K_CONV, KS, S, MT, nt == 2 ? 2 : 1, CM, v4, 0, 0, 0});   // (no count of the multiplies it issues is kept)
   if (nt == 2 && v4) hipLaunchKernelGGL((sr_conv_kernel<KS, S, MT, 2, CM, true>), grid, block, 0, stream, p);
   else if (nt == 2) hipLaunchKernelGGL((sr_conv_kernel<KS, S, MT, 2, CM, false>), grid, block, 0, stream, p);
   else if (v4) hipLaunchKernelGGL((sr_conv_kernel<KS, S, MT, 1, CM, true>), grid, block, 0, stream, p);
@@ -723,22 +724,6 @@ extern "C" int sr_conv2d_splitk_nhwc_fwd(const float* in, int64_t in_batch_strid
   return sr_conv2d_dispatch(in, in_batch_stride, in_pix_stride, packed_weight, bias, residual, res_batch_stride,
                             res_pix_stride, out, out_batch_stride, out_pix_stride, B, H, W, Cin, Cout, ksize, stride,
                             leaky_slope, 0, stream_, nullptr, workspace, workspace_bytes);
-}
-
-// Symbol of the kernel instantiation sr_conv2d_nhwc_fwd picks for these arguments (for profilers / bench).
-extern "C" const char* sr_conv_kernel_name(int B, int H, int W, int Cin, int Cout, int ksize, int stride,
-                                           int aligned16) {
-  static thread_local char buf[96];
-  SrConvParams p;
-  const int pad = ksize / 2;
-  p.Ho = (H + 2 * pad - ksize) / stride + 1;
-  p.Wo = (W + 2 * pad - ksize) / stride + 1;
-  p.Co_pad = ((Cout + 31) / 32) * 32;
-  const SrConvCfg cfg = sr_conv_cfg(p, B, stride, ksize);
-  const int mt = cfg.shape == 0 ? 2 : 1, cm = cfg.shape == 2 ? 8 : 32, nt = cfg.nt;
-  snprintf(buf, sizeof(buf), "sr_conv_kernel<%d, %d, %d, %d, %d, %s>", ksize, stride, mt, nt, cm,
-           (aligned16 && Cin % 4 == 0) ? "true" : "false");
-  return buf;
 }
 
 extern "C" int sr_upsample2x_nhwc_fwd(const float* in, int64_t in_batch_stride, int in_pix_stride, float* out,

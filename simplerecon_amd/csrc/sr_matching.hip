@@ -848,6 +848,8 @@ extern "C" int sr_conv3x3_c16_nhwc_fwd(const float* in, int64_t in_batch_stride,
   int blocks = 3 * sr_cus();
   if (blocks > p.total) blocks = p.total;
   const bool norm = in_stats != nullptr, act = in_leaky_slope >= 0.f;
+  // tiles of 8 x 16 pixels (the staged halo less its border) by 16 output channels, 9 taps of Cin
+  sr_note_launch({SR_K_T16, 0, 0, 0, 0, 0, 0, (int64_t)p.total * ((SR_T16_HH - 2) * (SR_T16_HW - 2)), 16, (int64_t)Cin * 9});
   if (norm && act) hipLaunchKernelGGL((sr_t16_kernel<true, true>), dim3(blocks), dim3(256), 0, (hipStream_t)stream_, p);
   else if (norm) hipLaunchKernelGGL((sr_t16_kernel<true, false>), dim3(blocks), dim3(256), 0, (hipStream_t)stream_, p);
   else if (act) hipLaunchKernelGGL((sr_t16_kernel<false, true>), dim3(blocks), dim3(256), 0, (hipStream_t)stream_, p);
@@ -882,6 +884,8 @@ extern "C" int sr_stem7x7_fwd(const float* in, int64_t in_batch_stride, int64_t 
   p.total = p.tiles_x * p.tiles_y * B;
   int blocks = 2 * sr_cus();
   if (blocks > p.total) blocks = p.total;
+  // tiles of SR_STEM_T x SR_STEM_T output pixels by 64 channels, the 147 taps in SR_STEM_STEPS k-steps of two
+  sr_note_launch({SR_K_STEM, 0, 0, 0, 0, 0, 0, (int64_t)p.total * (SR_STEM_T * SR_STEM_T), 64, 2 * SR_STEM_STEPS});
   hipLaunchKernelGGL(sr_stem_kernel, dim3(blocks), dim3(256), 0, (hipStream_t)stream_, p);
   return sr_hip_rc(hipGetLastError());
 }
@@ -1003,6 +1007,7 @@ extern "C" int sr_conv1x1_stats_nhwc_fwd(const float* in, int64_t in_batch_strid
   int blocks = 3 * sr_cus();
   if (blocks > p.total) blocks = p.total;
   hipStream_t stream = (hipStream_t)stream_;
+  sr_note_launch({SR_K_C1S, 0, 0, 0, 0, 0, 0, (int64_t)p.total * SR_C1S_PIX, Cout, Cin});   // tiles of SR_C1S_PIX pixels
   hipLaunchKernelGGL(sr_conv1x1_stats_kernel, dim3(blocks), dim3(256), 0, stream, p);
   SrInormParams q;
   q.in = nullptr; q.in_sb = 0; q.in_sp = 0; q.out = nullptr; q.out_sb = 0; q.out_sp = 0;

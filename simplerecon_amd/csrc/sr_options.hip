@@ -11,6 +11,7 @@
 #include <map>
 #include <mutex>
 #include <utility>
+#include <stdio.h>
 #include <stdlib.h>
 #include <string.h>
 
@@ -104,6 +105,35 @@ int sr_device_cus() {
     cus[dev].store(v, std::memory_order_relaxed);
   }
   return v;
+}
+
+// The kernel the calling thread's last launcher call issued, as its launch site noted it (sr_common.h).  Nothing is formatted
+// and no floating point is touched until somebody asks: sr_last_launch below, only under a profiling bracket.
+static thread_local SrLaunchNote t_note = {SR_K_NONE, 0, 0, 0, 0, 0, 0, 0, 0, 0};
+
+void sr_note_launch(const SrLaunchNote& note) { t_note = note; }
+
+extern "C" int sr_last_launch(char* name, int name_capacity, double* executed_flops) {
+  const SrLaunchNote n = t_note;
+  t_note.kernel = SR_K_NONE;
+  if (n.kernel == SR_K_NONE || !name || name_capacity <= 0 || !executed_flops) return SR_ERR_INVALID_ARGUMENT;
+  const char* const tf[2] = {"false", "true"};
+  // the template arguments chosen per launch, in the kernel's order (trailing ones that a launcher fixes, such as the I/O format,
+  // are left out); the tiled pointwise kernel by its workgroup tile and K split, not by the <WM, WN, NTW> the tile follows from
+  switch (n.kernel) {
+    case SR_K_CONV: snprintf(name, name_capacity, "sr_conv_kernel<%d, %d, %d, %d, %d, %s>", n.a, n.b, n.c, n.d, n.e, tf[n.f != 0]); break;
+    case SR_K_WINO: snprintf(name, name_capacity, "sr_wino_kernel<%d, %s, %s>", n.a, tf[n.b != 0], tf[n.c != 0]); break;
+    case SR_K_WINO_SPLIT: snprintf(name, name_capacity, "sr_wino_split_kernel<%d, %d>", n.a, n.b); break;
+    case SR_K_WINO4: snprintf(name, name_capacity, "%s", n.a == 3 ? "sr_wino4ws_kernel" : n.a == 2 ? "sr_wino4pp_kernel" : "sr_wino4_kernel"); break;
+    case SR_K_PW: snprintf(name, name_capacity, "sr_pw_kernel<%d, %d, %s>", n.a, n.b, tf[n.c != 0]); break;
+    case SR_K_PW_TILED: snprintf(name, name_capacity, "sr_pw_tiled_kernel<%dx%d, ks %d, %s>", n.a, n.b, n.c, tf[n.d != 0]); break;
+    case SR_K_STEM: snprintf(name, name_capacity, "sr_stem_kernel"); break;
+    case SR_K_C1S: snprintf(name, name_capacity, "sr_conv1x1_stats_kernel"); break;
+    case SR_K_T16: snprintf(name, name_capacity, "sr_t16_kernel"); break;
+    default: return SR_ERR_INVALID_ARGUMENT;
+  }
+  *executed_flops = n.m > 0 ? 2.0 * (double)n.m * (double)n.n * (double)n.k : -1.0;
+  return SR_OK;
 }
 
 // hipFuncAttributeMaxDynamicSharedMemorySize once per (kernel, device) instead of once per launch: the largest

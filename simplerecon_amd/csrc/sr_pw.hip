@@ -226,6 +226,9 @@ int pw_launch(const SrPwParams& p, hipStream_t stream, int io) {
   const int mt_per_wg = 4 / KS;
   const long wgs = ((long)p.total_mt + mt_per_wg - 1) / mt_per_wg * p.n_blocks;
   const size_t lds = KS > 1 ? (size_t)mt_per_wg * (KS - 1) * NT * 16 * 64 * sizeof(float) : 0;
+  // 32-row M tiles by blocks of NT 32-channel tiles, K in groups of 8
+  sr_note_launch({SR_K_PW, NT, KS, !io && p.gate, 0, 0, 0, (int64_t)p.total_mt * 32, (int64_t)p.n_blocks * NT * 32,
+                  (int64_t)p.G8 * 8});
   if (io == 1) hipLaunchKernelGGL((sr_pw_kernel<NT, KS, false, 1>), dim3((unsigned)wgs), dim3(256), lds, stream, p);
   else if (io == 2) hipLaunchKernelGGL((sr_pw_kernel<NT, KS, false, 2>), dim3((unsigned)wgs), dim3(256), lds, stream, p);
   else if (p.gate) hipLaunchKernelGGL((sr_pw_kernel<NT, KS, true>), dim3((unsigned)wgs), dim3(256), lds, stream, p);

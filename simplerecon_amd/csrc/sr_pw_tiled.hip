@@ -202,6 +202,8 @@ int pt_launch(const SrPtParams& p, int tiles_m, hipStream_t stream) {
   const dim3 grid((unsigned)(tiles_m * p.tiles_n), (unsigned)p.ksplit);
   auto kernel = p.gate ? sr_pw_tiled_kernel<WM, WN, NTW, true> : sr_pw_tiled_kernel<WM, WN, NTW, false>;
   if (hipError_t e = sr_allow_lds((const void*)kernel, lds)) return sr_hip_rc(e);
+  sr_note_launch({SR_K_PW_TILED, BM, BN, p.ksplit, p.gate != nullptr, 0, 0, (int64_t)tiles_m * BM, (int64_t)p.tiles_n * BN,
+                  (int64_t)p.slabs * PT_KS});
   hipLaunchKernelGGL(kernel, grid, dim3(256), lds, stream, p);
   return sr_hip_rc(hipGetLastError());
 }

@@ -53,6 +53,12 @@ struct SrWinoParams {
 #endif
 };
 
+// Launch note (sr_common.h) of an F(2x2) kernel with leading template arguments <nt, b[, c]>: p.total work items, each WN_TR x
+// WN_TC tiles of 16 frequencies by 32 nt output channels over its K part's 16-channel slabs.
+static inline SrLaunchNote sr_wino_note(int kernel, int nt, int b, int c, const SrWinoParams& p) {
+  return {kernel, nt, b, c, 0, 0, 0, (int64_t)p.total * (WN_TR * WN_TC * 16), 32 * nt, (p.G / 2) * 16 / p.ksplit};
+}
+
 #ifdef SR_WINO_TRACE
 #define SR_TR_REGIONS 12
 #define SR_TR_EVENTS 16

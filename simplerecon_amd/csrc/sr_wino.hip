@@ -626,14 +626,13 @@ extern "C" size_t sr_wino_splitk_workspace_bytes(int B, int H, int W, int Cin, i
   return ks > 1 ? (size_t)ks * B * H * W * Cout * sizeof(float) : 0;
 }
 
-// Symbol of the kernel instantiation sr_conv3x3_wino_nhwc_fwd launches (for profilers / bench): `aligned_in` = input
-// rows 16-byte aligned and Cin % 4 == 0, `aligned_out` = output / residual / bias rows 16-byte aligned and Cout % 4 == 0.
-extern "C" const char* sr_wino_kernel_name(int B, int H, int W, int Cin, int Cout, int aligned_in, int aligned_out) {
-  static thread_local char buf[64];
-  const int vin = aligned_in != 0, vout = vin && aligned_out;
-  snprintf(buf, sizeof(buf), "sr_wino_kernel<%d, %s, %s>", sr_wino_plan(B, H, W, Cin, Cout, vout != 0).nt,
-           vin ? "true" : "false", vout ? "true" : "false");
-  return buf;
+// The launch plan of a shape (tests, sweeps): `allow_split` = the launcher may split K (a usable workspace, vector epilogue).
+extern "C" int sr_wino_conv_plan(int B, int H, int W, int Cin, int Cout, int allow_split, int* nt, int* ks) {
+  if (B <= 0 || H <= 0 || W <= 0 || Cin <= 0 || Cout <= 0) return SR_ERR_INVALID_ARGUMENT;
+  const SrWinoPlan pl = sr_wino_plan(B, H, W, Cin, Cout, allow_split != 0);
+  if (nt) *nt = pl.nt;
+  if (ks) *ks = pl.ks;
+  return SR_OK;
 }
 
 static int sr_wino_run(const float* in, int64_t in_batch_stride, int in_pix_stride, const float* packed_u,
@@ -699,11 +698,13 @@ static int sr_wino_run(const float* in, int64_t in_batch_stride, int in_pix_stri
 #define SR_WINO_LAUNCH_IO(NTV, IOV)                                                                              \
   {                                                                                                               \
     if (hipError_t e = sr_allow_lds((const void*)sr_wino_kernel<NTV, true, true, IOV>, lds)) return sr_hip_rc(e); \
+    sr_note_launch(sr_wino_note(SR_K_WINO, NTV, true, true, p));                                                  \
     hipLaunchKernelGGL((sr_wino_kernel<NTV, true, true, IOV>), dim3(blocks), dim3(256), lds, stream, p);          \
   }
 #define SR_WINO_LAUNCH(NTV, V4, VO)                                                                               \
   {                                                                                                               \
     if (hipError_t e = sr_allow_lds((const void*)sr_wino_kernel<NTV, V4, VO>, lds)) return sr_hip_rc(e);          \
+    sr_note_launch(sr_wino_note(SR_K_WINO, NTV, V4, VO, p));                                                      \
     hipLaunchKernelGGL((sr_wino_kernel<NTV, V4, VO>), dim3(blocks), dim3(256), lds, stream, p);                   \
   }
   if (split) { const int rc = sr_wino_split_launch(p, nt, blocks, split, stream); if (rc) return rc; }

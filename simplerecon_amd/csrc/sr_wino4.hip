@@ -1100,6 +1100,8 @@ static int w4_run(const float* in, int64_t in_batch_stride, int in_pix_stride, c
   if (total >= lim) return SR_ERR_UNSUPPORTED;
   p.total = (int)total;
   p.slope = leaky_slope;
+  // a work item: the 16 4x4 tiles of a 16 x 16 region at 36 frequencies by 64 output channels, over p.S 16-channel slabs
+  SrLaunchNote note = {SR_K_WINO4, /* form, set below */ 0, 0, 0, 0, 0, 0, (int64_t)p.total * (16 * 36), 64, (int64_t)p.S * 16};
   if (variant == 3) {   // wave-specialised: 4 MFMA waves + 4 transform waves, one workgroup per CU
     int blocks = sr_device_cus();
     if (blocks > p.total) blocks = p.total;
@@ -1110,6 +1112,7 @@ static int w4_run(const float* in, int64_t in_batch_stride, int in_pix_stride, c
 #ifdef SR_W4_TRACE
     w4_trace_begin(p, (hipStream_t)stream_);
 #endif
+    note.a = 3; sr_note_launch(note);
     hipLaunchKernelGGL(kernel, dim3(blocks), dim3(512), W4_WS_LDS_BYTES, (hipStream_t)stream_, p);
 #ifdef SR_W4_TRACE
     w4_trace_end(blocks, (hipStream_t)stream_);
@@ -1120,6 +1123,7 @@ static int w4_run(const float* in, int64_t in_batch_stride, int in_pix_stride, c
     int blocks = 2 * sr_device_cus();
     if (blocks > p.total) blocks = p.total;
     if (int rc = w4_allow_lds((const void*)sr_wino4_kernel, W4_LDS_BYTES)) return rc;
+    note.a = 1; sr_note_launch(note);
     hipLaunchKernelGGL(sr_wino4_kernel, dim3(blocks), dim3(256), W4_LDS_BYTES, (hipStream_t)stream_, p);
     return sr_hip_rc(hipGetLastError());
   }
@@ -1129,6 +1133,7 @@ static int w4_run(const float* in, int64_t in_batch_stride, int in_pix_stride, c
   w4_trace_begin(p, (hipStream_t)stream_);
 #endif
   if (int rc = w4_allow_lds((const void*)sr_wino4pp_kernel, 2 * W4_LDS_BYTES)) return rc;
+  note.a = 2; sr_note_launch(note);
   hipLaunchKernelGGL(sr_wino4pp_kernel, dim3(blocks), dim3(512), 2 * W4_LDS_BYTES, (hipStream_t)stream_, p);
 #ifdef SR_W4_TRACE
   w4_trace_end(blocks, (hipStream_t)stream_);

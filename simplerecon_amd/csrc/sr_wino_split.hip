@@ -403,6 +403,7 @@ int sr_wino_split_launch(const SrWinoParams& p, int nt, int blocks, int mode, hi
 #define WS_LAUNCH(NTV, FMTV)                                                                                      \
   {                                                                                                               \
     if (hipError_t e = sr_allow_lds((const void*)sr_wino_split_kernel<NTV, FMTV>, lds)) return sr_hip_rc(e);      \
+    sr_note_launch(sr_wino_note(SR_K_WINO_SPLIT, NTV, FMTV, 0, p));                                               \
     hipLaunchKernelGGL((sr_wino_split_kernel<NTV, FMTV>), dim3(blocks), dim3(256), lds, stream, p);               \
   }
   if (mode == 1 && nt == 2) WS_LAUNCH(2, 1)

@@ -4,7 +4,6 @@ and thin wrappers that hand raw pointers/strides to the C ABI (include/simplerec
 A "channels-last view" is a logically [B,C,H,W] torch tensor whose memory is [B,H,W,Ctot] with
 this tensor occupying channels [c0, c0+C) of each pixel -- either a dense channels_last tensor or
 a channel slice `buf[:, c0:c1]` of one.  Kernels take (pointer, batch stride, pixel stride)."""
-import ctypes as C
 import contextlib
 import os
 import weakref
@@ -15,7 +14,8 @@ from torch import nn
 from . import _lib
 
 # When set to a list, every timed launch (_timed) appends (kernel symbol, algorithmic FLOPs, start event, end event, shape,
-# executed FLOPs): bench.py uses it to time the dominant kernel with HIP events on the launch stream.
+# executed FLOPs): bench.py uses it to time the dominant kernel with HIP events on the launch stream.  The symbol and the
+# executed FLOPs are reported by the launcher that issued the kernel (sr_last_launch), not worked out again here.
 PROFILE = None
 
 # Packed weights (and the other tensors derived from a module's parameters), per module: {cache tag: [state key, payload,
@@ -410,10 +410,11 @@ def _aligned16(t, sb, sp):
     return t is None or (t.data_ptr() % 16 == 0 and sp % 4 == 0 and sb % 4 == 0)
 
 
-def _timed(device, record, fn, *args):
+def _timed(device, flops, shape, fn, *args, name=None):
     """fn(*args) on `device` -> the library's rc.  With PROFILE on, two timing events bracket the launch and a launch that
-    succeeded appends (kernel name, algorithmic FLOPs, start event, end event, shape, executed FLOPs); record() -> (kernel
-    name, algorithmic FLOPs, shape, executed FLOPs or None) is only asked then."""
+    succeeded appends (kernel name, algorithmic FLOPs, start event, end event, shape, executed FLOPs): `flops` and `shape`
+    are facts of the call, the kernel's name and the FLOPs it executed are what the launcher noted (_lib.last_launch).  The
+    MLP sweep alone passes `name` -- its entry point, sr_mlp_volume_fwd, which the benchmark keys on -- and is not asked."""
     prof = PROFILE
     with _lib.on_device(device):
         if prof is None:
@@ -423,23 +424,20 @@ def _timed(device, record, fn, *args):
         rc = fn(*args)
         ev1.record()
         if rc == 0:
-            name, flops, shape, executed = record()
+            name, executed = (name, None) if name is not None else _lib.last_launch()
             prof.append((name, flops, ev0, ev1, shape, executed))
     return rc
 
 
-def _launch(x, shape, entry, fallback, describe, fn, *args):
+def _launch(x, shape, entry, fallback, fn, *args):
     """A conv launch through _timed; raises for any error but SR_ERR_UNSUPPORTED with a `fallback` behind it (`entry`: the
-    call's name in the message).  describe() -> (kernel name, executed FLOPs or None) completes the PROFILE record."""
+    call's name in the message)."""
     if PROFILE is None:   # (skips _timed's call frame: a quarter microsecond per launch on a host-bound batch-1 path)
         with _lib.on_device(x.device):
             rc = fn(*args)
     else:
-        def record():
-            b, ci, h, w, co, k, s, ho, wo, _ = shape
-            name, executed = describe()
-            return name, 2.0 * b * ho * wo * co * ci * k * k, shape, executed
-        rc = _timed(x.device, record, fn, *args)
+        b, ci, h, w, co, k, s, ho, wo, _ = shape
+        rc = _timed(x.device, 2.0 * b * ho * wo * co * ci * k * k, shape, fn, *args)
     if rc != 0 and (rc != _lib.ERR_UNSUPPORTED or not fallback):
         _lib.check(rc, entry)
     return rc
@@ -451,34 +449,13 @@ def _conv_pointwise(lib, x, wp, bias, residual, out, gate, strides, shape, slope
     b, ci, h, w, co = shape[:5]
     m = b * h * w
     dense = b == 1 or (isb == h * w * isp and osb == h * w * osp and (residual is None or rsb == h * w * rsp))
-    gflag = "true" if gate is not None else "false"
     if dense and (PW_TILED == "1" or (PW_TILED == "auto" and m >= PW_TILED_MIN_ROWS)):
         nbytes = _shape_query(lib, "sr_pw_conv_tiled_workspace_bytes", m, ci, co, dev=x.device.index)
         ws = _workspace(x.device, "pw_splitk", nbytes) if nbytes else None
-
-        def describe():
-            # the plan the LAUNCHER took: it splits K only with a usable workspace AND 16-byte aligned out / residual / bias
-            # rows (sr_pw_conv_tiled_nhwc_fwd's `can_split`), so ask with the same answer
-            a_, b_ = C.c_int(0), C.c_int(0)
-            can_split = ws is not None and ws.data_ptr() % 16 == 0 and co % 4 == 0 and _aligned16(out, 0, osp) and \
-                _aligned16(residual, 0, rsp) and (bias is None or bias.data_ptr() % 16 == 0)
-            lib.sr_pw_conv_tiled_plan(m, ci, co, int(can_split), C.byref(a_), C.byref(b_))
-            if b_.value > 1 and nbytes < b_.value * m * co * 4:
-                lib.sr_pw_conv_tiled_plan(m, ci, co, 0, C.byref(a_), C.byref(b_))
-            tile_m, tile_n = ((64, 128), (128, 160), (128, 64), (64, 64))[a_.value]
-            executed = 2.0 * (-(-m // tile_m) * tile_m) * (-(-co // tile_n) * tile_n) * (-(-ci // 32) * 32)
-            return f"sr_pw_tiled_kernel<{tile_m}x{tile_n}, ks {b_.value}, {gflag}>", executed
-        return _launch(x, shape, "sr_pw_conv_tiled_nhwc_fwd", gate is None, describe, lib.sr_pw_conv_tiled_nhwc_fwd,
+        return _launch(x, shape, "sr_pw_conv_tiled_nhwc_fwd", gate is None, lib.sr_pw_conv_tiled_nhwc_fwd,
                        _lib.ptr(x), isp, _lib.ptr(wp), _lib.ptr(bias), _lib.ptr(gate), _lib.ptr(residual), rsp, _lib.ptr(out),
                        osp, m, h * w, ci, co, slope, _lib.ptr(ws), nbytes, _lib.stream_ptr(x.device))
-
-    def describe():
-        a_, b_ = C.c_int(0), C.c_int(0)
-        lib.sr_pw_conv_plan(b, h * w, ci, co, C.byref(a_), C.byref(b_))
-        mt = b * ((h * w + 31) // 32)
-        executed = 2.0 * mt * 32 * ((co + 32 * a_.value - 1) // (32 * a_.value) * 32 * a_.value) * ((ci + 7) // 8 * 8)
-        return f"sr_pw_kernel<{a_.value}, {b_.value}, {gflag}>", executed
-    return _launch(x, shape, "sr_pw_conv_nhwc_fwd", gate is None, describe, lib.sr_pw_conv_nhwc_fwd, _lib.ptr(x), isb, isp,
+    return _launch(x, shape, "sr_pw_conv_nhwc_fwd", gate is None, lib.sr_pw_conv_nhwc_fwd, _lib.ptr(x), isb, isp,
                    _lib.ptr(wp), _lib.ptr(bias), _lib.ptr(gate), _lib.ptr(residual), rsb, rsp, _lib.ptr(out), osb, osp, b,
                    h * w, ci, co, slope, _lib.stream_ptr(x.device))
 
@@ -491,14 +468,9 @@ def _conv_wino4(lib, x, wp, bias, residual, out, strides, shape, slope, variant)
     if not (_aligned16(x, isb, isp) and _aligned16(out, osb, osp) and _aligned16(residual, rsb, rsp)
             and (bias is None or bias.data_ptr() % 16 == 0)):
         return _lib.ERR_UNSUPPORTED
-
-    def describe():
-        regions = ((h + 15) // 16) * ((w + 15) // 16)   # multiplies issued: 36 per 4x4 tile and (ci, co) pair, padded
-        executed = 2.0 * b * regions * 16 * 36 * ((ci + 15) // 16 * 16) * ((co + 63) // 64 * 64)
-        return "sr_wino4ws_kernel" if variant == 3 else "sr_wino4_kernel", executed
-    return _launch(x, shape, "sr_conv3x3_wino4_nhwc_fwd", True, describe, lib.sr_conv3x3_wino4_variant_nhwc_fwd, _lib.ptr(x),
-                   isb, isp, _lib.ptr(wp), _lib.ptr(bias), _lib.ptr(residual), rsb, rsp, _lib.ptr(out), osb, osp, b, h, w, ci,
-                   co, slope, variant, _lib.stream_ptr(x.device))
+    return _launch(x, shape, "sr_conv3x3_wino4_nhwc_fwd", True, lib.sr_conv3x3_wino4_variant_nhwc_fwd, _lib.ptr(x), isb, isp,
+                   _lib.ptr(wp), _lib.ptr(bias), _lib.ptr(residual), rsb, rsp, _lib.ptr(out), osb, osp, b, h, w, ci, co,
+                   slope, variant, _lib.stream_ptr(x.device))
 
 
 def _conv_wino(lib, x, wp, bias, residual, out, strides, shape, slope, workspace=True, fallback=True):
@@ -507,26 +479,10 @@ def _conv_wino(lib, x, wp, bias, residual, out, strides, shape, slope, workspace
     training path); fallback=False: SR_ERR_UNSUPPORTED raises like any other error (no direct-kernel launch stands behind)."""
     isb, isp, osb, osp, rsb, rsp = strides
     b, ci, h, w, co = shape[:5]
-    split = wino_split_mode()
     # 0 unless it splits K
     nbytes = _shape_query(lib, "sr_wino_splitk_workspace_bytes", b, h, w, ci, co, dev=x.device.index) if workspace else 0
     ws = _workspace(x.device, "wino_splitk", nbytes) if nbytes else None
-
-    def describe():
-        vin = bool(_aligned16(x, isb, isp) and ci % 4 == 0)
-        vout = vin and co % 4 == 0 and _aligned16(out, osb, osp) and _aligned16(residual, rsb, rsp) and \
-            (bias is None or bias.data_ptr() % 16 == 0)
-        # (without a workspace the launcher's plan is the one that may not split K: the name is asked with aligned_out = 0,
-        # which answers for that plan, and the vector epilogue's template argument is put back)
-        name = lib.sr_wino_kernel_name(b, h, w, ci, co, int(vin), int(vout and workspace)).decode()
-        if vout and not workspace:
-            name = name.replace(", true, false>", ", true, true>")
-        if split:   # (the fenced variant: sr_wino_split_kernel<NT, FMT>)
-            name = name.replace("sr_wino_kernel<", "sr_wino_split_kernel<").replace(
-                ", true, true>", f", {1 if split == 'bf16' else 2}>")
-        regions = ((h + 7) // 8) * ((w + 15) // 16)   # multiplies issued: 16 per 2x2 tile and (ci, co) pair, padded
-        return name, 2.0 * b * regions * 32 * 16 * ((ci + 15) // 16 * 16) * ((co + 31) // 32 * 32)
-    return _launch(x, shape, "sr_conv3x3_wino_nhwc_fwd", fallback and not split, describe, lib.sr_conv3x3_wino_splitk_nhwc_fwd,
+    return _launch(x, shape, "sr_conv3x3_wino_nhwc_fwd", fallback and not wino_split_mode(), lib.sr_conv3x3_wino_splitk_nhwc_fwd,
                    _lib.ptr(x), isb, isp, _lib.ptr(wp), _lib.ptr(bias), _lib.ptr(residual), rsb, rsp, _lib.ptr(out), osb, osp,
                    b, h, w, ci, co, slope, _lib.ptr(ws), nbytes, _lib.stream_ptr(x.device))
 
@@ -538,9 +494,7 @@ def _conv_direct(lib, x, wp, bias, residual, out, strides, shape, slope, pads, r
     b, ci, h, w, co, k, s = shape[:7]
     args = (_lib.ptr(x), isb, isp, _lib.ptr(wp), _lib.ptr(bias), _lib.ptr(residual), rsb, rsp, _lib.ptr(out), osb, osp,
             b, h, w, ci, co, k, s)
-    describe = lambda: (lib.sr_conv_kernel_name(b, h, w, ci, co, k, s, int(_aligned16(x, isb, isp))).decode(), None)
-    launch = lambda fn, *tail: _launch(x, shape, "sr_conv2d_nhwc_fwd", False, describe, fn, *args, *tail,
-                                       _lib.stream_ptr(x.device))
+    launch = lambda fn, *tail: _launch(x, shape, "sr_conv2d_nhwc_fwd", False, fn, *args, *tail, _lib.stream_ptr(x.device))
     if pads is not None:
         return launch(lib.sr_conv2d_padded_nhwc_fwd, *pads, slope)
     if replicate:
@@ -653,11 +607,9 @@ def stem7x7(image, conv: nn.Conv2d, bn=None, leaky=0.0, out=None):
         return out
     sb, sc, sy, sx = image.stride()
     osb, osp = _strides(out)
-    record = lambda: ("sr_stem_kernel", 2.0 * b * ho * wo * 64 * 147, (b, 3, h, w, 64, 7, 2),
-                      2.0 * b * ((ho + 15) // 16) * ((wo + 15) // 16) * 256 * 64 * 148)
-    rc = _timed(image.device, record, _lib.lib().sr_stem7x7_fwd, _lib.ptr(image), sb, sc, sy, sx, _lib.ptr(wp),
-                _lib.ptr(scale), _lib.ptr(shift), -1.0 if leaky is None else float(leaky), _lib.ptr(out), osb,
-                osp, b, h, w, 64, _lib.stream_ptr(image.device))
+    rc = _timed(image.device, 2.0 * b * ho * wo * 64 * 147, (b, 3, h, w, 64, 7, 2), _lib.lib().sr_stem7x7_fwd, _lib.ptr(image),
+                sb, sc, sy, sx, _lib.ptr(wp), _lib.ptr(scale), _lib.ptr(shift), -1.0 if leaky is None else float(leaky),
+                _lib.ptr(out), osb, osp, b, h, w, 64, _lib.stream_ptr(image.device))
     _lib.check(rc, "sr_stem7x7_fwd")
     return out
 
@@ -733,11 +685,9 @@ def conv1x1_stats(x, conv: nn.Conv2d, eps=1e-5):
     bias = conv.bias.detach() if conv.bias is not None else None
     isb, isp = _strides(x)
     osb, osp = _strides(out)
-    record = lambda: ("sr_conv1x1_stats_kernel", 2.0 * b * h * w * co * ci, (b, ci, h, w, co, 1, 1),
-                      2.0 * b * ((h * w + 63) // 64) * 64 * co * ci)
-    rc = _timed(x.device, record, lib.sr_conv1x1_stats_nhwc_fwd, _lib.ptr(x), isb, isp, _lib.ptr(weight), _lib.ptr(bias),
-                _lib.ptr(out), osb, osp, b, h, w, ci, co, eps, _lib.ptr(stats), _lib.ptr(ws), ws.numel() * 4,
-                _lib.stream_ptr(x.device))
+    rc = _timed(x.device, 2.0 * b * h * w * co * ci, (b, ci, h, w, co, 1, 1), lib.sr_conv1x1_stats_nhwc_fwd, _lib.ptr(x), isb,
+                isp, _lib.ptr(weight), _lib.ptr(bias), _lib.ptr(out), osb, osp, b, h, w, ci, co, eps, _lib.ptr(stats),
+                _lib.ptr(ws), ws.numel() * 4, _lib.stream_ptr(x.device))
     _lib.check(rc, "sr_conv1x1_stats_nhwc_fwd")
     return out, stats
 
@@ -765,11 +715,9 @@ def conv3x3_c16(x, conv: nn.Conv2d, in_stats=None, in_leaky=None, leaky=None):
         return out
     isb, isp = _strides(x)
     osb, osp = _strides(out)
-    record = lambda: ("sr_t16_kernel", 2.0 * b * h * w * co * ci * 9, (b, ci, h, w, co, 3, 1),
-                      2.0 * b * ((h + 7) // 8) * ((w + 15) // 16) * 128 * 16 * ci * 9)
-    rc = _timed(x.device, record, _lib.lib().sr_conv3x3_c16_nhwc_fwd, _lib.ptr(x), isb, isp, _lib.ptr(in_stats),
-                -1.0 if in_leaky is None else float(in_leaky), _lib.ptr(wp), _lib.ptr(bias), _lib.ptr(out), osb,
-                osp, b, h, w, ci, co, int(conv.padding_mode == "replicate"),
+    rc = _timed(x.device, 2.0 * b * h * w * co * ci * 9, (b, ci, h, w, co, 3, 1), _lib.lib().sr_conv3x3_c16_nhwc_fwd,
+                _lib.ptr(x), isb, isp, _lib.ptr(in_stats), -1.0 if in_leaky is None else float(in_leaky), _lib.ptr(wp),
+                _lib.ptr(bias), _lib.ptr(out), osb, osp, b, h, w, ci, co, int(conv.padding_mode == "replicate"),
                 -1.0 if leaky is None else float(leaky), _lib.stream_ptr(x.device))
     _lib.check(rc, "sr_conv3x3_c16_nhwc_fwd")
     return out

@@ -234,7 +234,7 @@ def test_winograd_f4(shape, variant, monkeypatch, sr_option):
     monkeypatch.setattr(ops, "WINO4_VARIANT", variant)
     ops._SHAPE_QUERIES.clear()
     try:
-        _conv_case(shape, expect="sr_wino4ws_kernel" if variant == 3 else "sr_wino4_kernel")
+        _conv_case(shape, expect={1: "sr_wino4_kernel", 2: "sr_wino4pp_kernel", 3: "sr_wino4ws_kernel"}[variant])
     finally:
         ops._SHAPE_QUERIES.clear()
 

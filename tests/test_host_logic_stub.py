@@ -71,14 +71,10 @@ def make_stub(monkeypatch):
                 return calls.prefer16_wgrad
             if self.name.endswith("_supported"):
                 return 1
-            if self.name in ("sr_pw_conv_plan", "sr_pw_conv_tiled_plan"):
-                # (tile variant, K split) through the two out-pointers; the tiled plan splits K only when it may
-                plan = (2, 1) if self.name == "sr_pw_conv_plan" else (1, 4) if args[3] else (3, 1)
-                args[-2]._obj.value, args[-1]._obj.value = plan
-            if self.name == "sr_wino_kernel_name":
-                return ("sr_wino_kernel<%d, %s, %s>" % (args[3], *("true" if a else "false" for a in args[5:]))).encode()
-            if self.name == "sr_conv_kernel_name":
-                return ("sr_conv_kernel<%s>" % ", ".join(map(str, args))).encode()
+            if self.name == "sr_last_launch":
+                # (kernel name, executed FLOPs) through the out-pointers: the launcher call before it, nothing executed
+                args[0]._obj.value = b"stub:" + calls[-2].encode()
+                args[2]._obj.value = -1.0
             if res is ctypes.c_char_p:
                 return b"stub_kernel"
             return 4096 if res is ctypes.c_size_t else calls.rc.get(self.name, 0)
@@ -710,9 +706,9 @@ def _dispatch_trace(stub, monkeypatch, case, rc):
                 trace["records"] = [[n, f, list(shape), ex] for n, f, _, _, shape, ex in prof]
         except (ValueError, _lib.HipLibraryError) as e:
             trace["raises"] = f"{type(e).__name__}: {e}"
-        # (profiled: without the queries behind a record's name and executed FLOPs -- the records pin what they answered)
+        # (profiled: without the query behind a record's name and executed FLOPs -- the records pin what it answered)
         trace["calls_profiled" if profiled else "calls"] = [
-            _pinned_call(n, a) for n, a in stub.args if not (profiled and n.endswith(("_kernel_name", "_plan")))]
+            _pinned_call(n, a) for n, a in stub.args if not (profiled and n == "sr_last_launch")]
     return trace
 
 
@@ -746,8 +742,9 @@ def _dispatch_traces(stub, monkeypatch):
 
 
 def test_conv2d_dispatch_matches_the_golden(stub, monkeypatch):
-    """ops.conv2d picks the same kernels, falls back in the same order and writes the same PROFILE records (name, algorithmic
-    and executed FLOPs, shape) as recorded in tests/golden/conv2d_dispatch.json.gz."""
+    """ops.conv2d calls the same entry points, falls back in the same order and writes the same PROFILE records (algorithmic
+    FLOPs and shape; the name and the executed FLOPs are the launcher's to report -- here the stub's "stub:<entry point>" and
+    None, on a GPU what tests/test_gpu_launch_records.py pins) as recorded in tests/golden/conv2d_dispatch.json.gz."""
     got = _dispatch_traces(stub, monkeypatch)
     with gzip.open(_GOLDEN_DISPATCH, "rt") as f:
         want = json.load(f)
