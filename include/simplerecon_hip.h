@@ -42,7 +42,12 @@ extern "C" {
  * that thread's next launch, and a HIP graph captured under a mode keeps the kernels of that mode.  Integer options take the
  * integer; the split modes take 0 = off (fp32 MFMA: the product path), 1 = bf16 pieces, 2 = f16 pieces (-1 = the unknown
  * string an environment variable held: the entry points that honour the mode return SR_ERR_INVALID_ARGUMENT); SR_MLP_TILE
- * takes the codes listed at sr_mlp_volume_tile_shape (environment: auto, flat, 2x32, 4x16, 8x8; -1 as above). */
+ * takes the codes listed at sr_mlp_volume_tile_shape (environment: auto, flat, 2x32, 4x16, 8x8; -1 as above).
+ * The two split modes differ in who reads them.  SR_OPT_MLP_SPLIT is read by the MLP entry points, once per call: the pack
+ * and the sweep inside one sr_mlp_volume_fwd see one value whatever another thread sets meanwhile.  SR_OPT_WINO_SPLIT is the
+ * switch a HOST reads to choose the `split_format` argument of sr_wino_pack_weights and sr_conv3x3_wino_splitk_nhwc_fwd: a
+ * packed Winograd weight outlives the call that made it, so its format travels with it as a value, and the library's
+ * Winograd launchers do not consult the option. */
 enum {
   SR_OPT_MLP_SPLIT = 0, SR_OPT_WINO_SPLIT, SR_OPT_WINO_XCD, SR_OPT_WINO_NT, SR_OPT_WINO_KSPLIT, SR_OPT_CONV_WINO,
   SR_OPT_CONV_TILE, SR_OPT_CONV_KSPLIT, SR_OPT_PW_NT, SR_OPT_PW_KS, SR_OPT_PT_CFG, SR_OPT_PT_KS, SR_OPT_DOT_LDS,
@@ -220,7 +225,8 @@ int sr_warp_features_fwd(const float* src, const float* K_src, const float* T_sr
 size_t sr_mlp_volume_workspace_bytes(int B, int K, int C, int h, int w, int hidden);
 
 /* Packs the MLP parameters into the k-step order of the sweep kernel (into `workspace`).
- * Experiment switch (off by default, read per call by the pack AND the sweep, which must agree): environment
+ * Experiment switch (off by default; read once per call -- sr_mlp_volume_fwd hands its one reading to the pack and the
+ * sweep inside it, a host that calls the pack and the sweep itself keeps the option still between the two): option
  * SR_MLP_SPLIT=bf16|f16 packs layers 1-2 as two 16-bit pieces per weight and selects the split-precision sweep kernel
  * (three exact 16-bit MFMA products per fp32 product, fp32 accumulate; K <= 7 source views, SR_ERR_UNSUPPORTED beyond;
  * unknown values: SR_ERR_INVALID_ARGUMENT).  Tensors handed in and results are fp32 either way. */
@@ -337,10 +343,12 @@ int sr_conv2d_splitk_nhwc_fwd(const float* in, int64_t in_batch_stride, int in_p
  * sr_wino_pack_weights (U = G g G^T in MFMA B-fragment order).  sr_conv_prefers_wino() tells whether this kernel
  * is expected to beat the direct one for a shape (enough 8x16-pixel regions, little padding). */
 size_t sr_wino_packed_weight_floats(int Cout, int Cin);
-/* Experiment switch (off by default; option SR_OPT_WINO_SPLIT, read by the pack AND the convolution, which must agree):
- * 1 = bf16 / 2 = f16 packs U as two 16-bit pieces (same buffer size) and selects the split-precision kernel (vector
- * instantiation and fp32 tensors only: SR_ERR_UNSUPPORTED otherwise; the value -1: SR_ERR_INVALID_ARGUMENT). */
-int sr_wino_pack_weights(const float* weight, int Cout, int Cin, float* packed, void* stream);
+/* `split_format` (fenced experiment): 0 = fp32 U, the product path; 1 = bf16 / 2 = f16 packs U as two 16-bit pieces (same
+ * buffer size) for the split-precision kernel; anything else: SR_ERR_INVALID_ARGUMENT.  The format is a property of the
+ * packed buffer: hand the same value to the sr_conv3x3_wino_splitk_nhwc_fwd calls that consume it.  Neither call reads
+ * SR_OPT_WINO_SPLIT -- that option is where a host keeps its choice.  sr_conv3x3_wino_nhwc_fwd (and the 16-bit I/O form) are
+ * the fp32-product entry points: they take format-0 weights and no longer follow the option. */
+int sr_wino_pack_weights(const float* weight, int Cout, int Cin, int split_format, float* packed, void* stream);
 int sr_conv_prefers_wino(int B, int H, int W, int Cin, int Cout, int ksize, int stride);
 int sr_conv3x3_wino_nhwc_fwd(const float* in, int64_t in_batch_stride, int in_pix_stride,
                              const float* packed_u, const float* bias, const float* residual,
@@ -378,15 +386,17 @@ int sr_conv3x3_wino4_variant_nhwc_fwd(const float* in, int64_t in_batch_stride, 
  * batch 1): work items cover Cin / ks input channels each and store raw partial outputs to `workspace`
  * ([ks][B, H*W, Cout] floats, 16-byte aligned); a second kernel adds them in index order (deterministic) and applies
  * bias + residual + LeakyReLU.  sr_wino_splitk_factor() = ks the launch plan picks for a shape (1: no split, no
- * workspace needed); with a NULL / too small workspace the call runs unsplit. */
+ * workspace needed); with a NULL / too small workspace the call runs unsplit.  `split_format` = the format `packed_u` was
+ * packed in (sr_wino_pack_weights); 1 / 2 select the split-precision kernel, which has the vector instantiation on fp32
+ * tensors only (SR_ERR_UNSUPPORTED otherwise). */
 int sr_wino_splitk_factor(int B, int H, int W, int Cin, int Cout);
 size_t sr_wino_splitk_workspace_bytes(int B, int H, int W, int Cin, int Cout);
 int sr_conv3x3_wino_splitk_nhwc_fwd(const float* in, int64_t in_batch_stride, int in_pix_stride,
                                     const float* packed_u, const float* bias, const float* residual,
                                     int64_t res_batch_stride, int res_pix_stride, float* out,
                                     int64_t out_batch_stride, int out_pix_stride, int B, int H, int W, int Cin,
-                                    int Cout, float leaky_slope, void* workspace, size_t workspace_bytes,
-                                    void* stream);
+                                    int Cout, float leaky_slope, int split_format, void* workspace,
+                                    size_t workspace_bytes, void* stream);
 
 /* The F(2x2) launch plan of a shape: output-channel block `nt` (32 nt channels per work item) and split-K factor `ks`
  * (either pointer may be NULL); `allow_split` = the launcher may split K (a usable workspace and the vector epilogue).  For

@@ -10,7 +10,7 @@ import torch
 
 _HERE = os.path.dirname(os.path.abspath(__file__))
 LIB_PATH = os.environ.get("SR_HIP_LIBRARY") or os.path.join(_HERE, "libsimplerecon_hip.so")   # override: ablation / trace builds
-ABI_VERSION = 4
+ABI_VERSION = 5
 
 _lib = None
 
@@ -132,12 +132,12 @@ SIGNATURES = {
     "sr_conv2d_splitk_nhwc_fwd": (_i, [_p, _i64, _i, _p, _p, _p, _i64, _i, _p, _i64, _i, _i, _i, _i, _i, _i, _i, _i,
                                        _f, _p, _sz, _p]),
     "sr_wino_packed_weight_floats": (_sz, [_i, _i]),
-    "sr_wino_pack_weights": (_i, [_p, _i, _i, _p, _p]),
+    "sr_wino_pack_weights": (_i, [_p, _i, _i, _i, _p, _p]),
     "sr_conv_prefers_wino": (_i, [_i, _i, _i, _i, _i, _i, _i]),
     "sr_wino_splitk_factor": (_i, [_i, _i, _i, _i, _i]),
     "sr_wino_splitk_workspace_bytes": (_sz, [_i, _i, _i, _i, _i]),
     "sr_conv3x3_wino_splitk_nhwc_fwd": (_i, [_p, _i64, _i, _p, _p, _p, _i64, _i, _p, _i64, _i, _i, _i, _i, _i, _i, _f,
-                                             _p, _sz, _p]),
+                                             _i, _p, _sz, _p]),
     "sr_wino_conv_plan": (_i, [_i, _i, _i, _i, _i, _i, _p, _p]),
     "sr_last_launch": (_i, [_p, _i, _p]),
     "sr_conv3x3_wino_nhwc_fwd": (_i, [_p, _i64, _i, _p, _p, _p, _i64, _i, _p, _i64, _i, _i, _i, _i, _i, _i, _f, _p]),
@@ -271,15 +271,11 @@ def check(rc, what):
 # the library never reads the environment again and hosts change a switch through these calls.  Process-wide.
 SPLIT_MODES = {"": 0, "0": 0, "off": 0, "fp32": 0, "bf16": 1, "f16": 2, "fp16": 2}
 _SPLIT_NAMES = {0: "", 1: "bf16", 2: "f16"}
-SPLIT_OPTION_NAMES = ("SR_MLP_SPLIT", "SR_WINO_SPLIT")   # the options that take a split-mode NAME
 TILE_MODES = {"auto": 0, "flat": 1, "2x32": 2, "4x16": 3, "8x8": 4}   # SR_MLP_TILE (sr_mlp_volume_tile_shape)
 _NAMED_VALUES = {"SR_MLP_SPLIT": SPLIT_MODES, "SR_WINO_SPLIT": SPLIT_MODES, "SR_MLP_TILE": TILE_MODES}   # every other option is
                                                                                                        # an integer
-# The split modes are read by the weight-packing AND by the launching entry points: a change between the two would feed one
-# format's packed weights to the other format's kernel.  Changing them and [pack + launch] hold this lock.
-import threading  # noqa: E402
-SPLIT_GUARD = threading.RLock()
-
+# A split mode is read ONCE per call and is a value from there on (ops.conv2d: cache key, pack and launch argument; the MLP
+# entry points: inside the library): a set_option from another thread or a listener changes the NEXT call, never one in flight.
 
 OPTION_LISTENERS = []   # callables (name, value) run after every set_option: caches of plan queries hang themselves in here
 
@@ -316,13 +312,10 @@ def set_option(name, value):
             raise ValueError(f"option {name} takes an integer, got {value!r}")   # (a typo used to become -1 silently)
         value = _NAMED_VALUES[name].get(value, -1)
     prev = C.c_int(0)
-    # a split mode's library value, mirror and listeners change together under the guard: a pack + launch in between would
-    # see the library in one mode and key its cache on the other
-    with SPLIT_GUARD if name in SPLIT_OPTION_NAMES else _NULL_CONTEXT:
-        check(lib().sr_option_set(_option_id(name), int(value), C.byref(prev)), "sr_option_set")
-        _OPTION_MIRROR[name] = int(value)
-        for fn in OPTION_LISTENERS:
-            fn(name, int(value))
+    check(lib().sr_option_set(_option_id(name), int(value), C.byref(prev)), "sr_option_set")
+    _OPTION_MIRROR[name] = int(value)
+    for fn in OPTION_LISTENERS:
+        fn(name, int(value))
     return prev.value
 
 

@@ -294,8 +294,10 @@ def _conv_raw_io(x, weight, bias, stride, residual, slope, pads, mfma16=None):
     if not ((wino or pw) and _rows_aligned(x, 8) and _rows_aligned(residual, 8)):
         y = _conv_raw(x.float(), weight, bias, stride, residual.float() if residual is not None else None, slope, pads)
         return y.to(dt)
+    if wino and _lib.get_option("SR_WINO_SPLIT") != 0:
+        raise _lib.HipLibraryError("the split-precision Winograd variant (SR_WINO_SPLIT) takes fp32 tensors: no 16-bit I/O")
     out = torch.empty((b, co, h, w), dtype=dt, device=x.device, memory_format=torch.channels_last)
-    wp = _pack("wino" if wino else "conv", weight.detach().float().contiguous())
+    wp = _pack("wino", weight.detach().float().contiguous(), 0) if wino else _pack("conv", weight.detach().float().contiguous())
     bd = bias.detach().float().contiguous() if bias is not None else None
     rsb, rsp = _strides(residual) if residual is not None else (0, 0)
     head = (x, *_strides(x), wp, bd, residual, rsb, rsp, out, *_strides(out), b)
@@ -324,7 +326,8 @@ def _conv_raw(x, weight, bias, stride, residual=None, slope=None, pads=None):
     if b == 0:
         return out
     use_wino = pads is None and stride == 1 and k == 3 and bool(lib.sr_conv_prefers_wino(b, h, w, ci, co, k, stride))
-    wp = _pack("wino" if use_wino else "conv", weight.detach().contiguous())
+    split = _lib.get_option("SR_WINO_SPLIT") if use_wino else 0   # read once: the pack and the launch take this value
+    wp = _pack("wino", weight.detach().contiguous(), split) if use_wino else _pack("conv", weight.detach().contiguous())
     if residual is not None:
         residual = as_nhwc(residual, "residual")
     bd = bias.detach().contiguous() if bias is not None else None
@@ -332,7 +335,7 @@ def _conv_raw(x, weight, bias, stride, residual=None, slope=None, pads=None):
     # (the shape also goes into ops.PROFILE with the kernel the launch ran: the data gradient's launches are told apart by it)
     shape = (b, ci, h, w, co, k, stride, ho, wo, residual is not None)
     if use_wino:
-        _conv_wino(lib, x, wp, bd, residual, out, strides, shape, _act_code(slope, None), workspace=False, fallback=False)
+        _conv_wino(lib, x, wp, bd, residual, out, strides, shape, _act_code(slope, None), split, workspace=False, fallback=False)
     else:
         _conv_direct(lib, x, wp, bd, residual, out, strides, shape, _act_code(slope, None), pads, False, workspace=False)
     return out

@@ -445,7 +445,7 @@ class FeatureVolumeManager(CostVolumeManager):
 
     def _launch_sweep(self, cur, src, Ks, T, Tp, invK, planes, params, return_mask, reserve_cus=0, in_place=False):
         """`in_place`: cur and src are dense channels-last views (dense_channels_last_pair) and go to
-        sr_mlp_volume_fwd_nhwc as they are; otherwise they are contiguous and go to sr_mlp_volume_fwd."""
+        sr_mlp_volume_fwd_nhwc as they are (under SR_MLP_SPLIT as copies); otherwise they are contiguous: sr_mlp_volume_fwd."""
         b, k, c, h, w = src.shape
         dev = src.device
         lib = _lib.lib()
@@ -460,10 +460,8 @@ class FeatureVolumeManager(CostVolumeManager):
         from . import ops   # (ops._timed: bench.py's in-step kernel table)
         cin, d = c * (k + 1) + 10 * k + 4, self.num_depth_bins
         flops = 2.0 * (cin * hidden + hidden * hidden + hidden) * b * d * h * w
-        with _lib.SPLIT_GUARD:   # (SR_MLP_SPLIT is read by the packing and by the sweep inside this one call)
-            if in_place and _lib.get_option("SR_MLP_SPLIT") != 0:   # the split-precision kernel reads cur planar
-                cur, src, in_place = cur.contiguous(), src.contiguous(), False
-            entry = "sr_mlp_volume_fwd_nhwc" if in_place else "sr_mlp_volume_fwd"
+
+        def launch(entry, cur, src, allow=()):   # (the library reads SR_MLP_SPLIT once per call, for its pack and its sweep)
             rc = ops._timed(
                 dev, flops, (), getattr(lib, entry),
                 _lib.ptr(cur), _lib.ptr(src), _lib.ptr(Ks), _lib.ptr(T), _lib.ptr(Tp), _lib.ptr(invK),
@@ -471,7 +469,14 @@ class FeatureVolumeManager(CostVolumeManager):
                 0.01,  # nn.LeakyReLU default slope (reference networks.py:139)
                 b, k, c, h, w, d, _lib.ptr(vol), sb, sd, sp, _lib.ptr(lowest),
                 _lib.ptr(mask), int(reserve_cus), _lib.ptr(ws), ws.numel(), _lib.stream_ptr(dev), name="sr_mlp_volume_fwd")
-        _lib.check(rc, entry)
+            if rc not in allow:
+                _lib.check(rc, entry)
+            return rc
+        # The split-precision kernel reads cur planar: under SR_MLP_SPLIT the in-place entry answers SR_ERR_UNSUPPORTED and the
+        # contiguous one serves the call.  (The mirror only spares the usual split call that refused attempt.)
+        if not (in_place and _lib.get_option("SR_MLP_SPLIT") == 0
+                and launch("sr_mlp_volume_fwd_nhwc", cur, src, allow=(_lib.ERR_UNSUPPORTED,)) == 0):
+            launch("sr_mlp_volume_fwd", cur.contiguous(), src.contiguous())
         return vol, lowest, mask
 
     def to_fast(self) -> "FastFeatureVolumeManager":

@@ -268,7 +268,7 @@ __global__ __launch_bounds__(1024) void sr_dot_volume_kernel16q(SrDotParams p) {
 
 // ------------------------------------------------------------------------ C ABI -------
 
-extern "C" int sr_abi_version(void) { return 4; }
+extern "C" int sr_abi_version(void) { return 5; }
 extern "C" const char* sr_target_arch(void) { return "gfx950"; }
 
 extern "C" size_t sr_volume_workspace_bytes(int B, int K, int C, int h, int w) {

@@ -997,8 +997,8 @@ __global__ __launch_bounds__(256, 1) void sr_mlp_volume_split_kernel(SrMlpParams
   }
 }
 
-// option SR_OPT_MLP_SPLIT: 0 = fp32 MFMA (the product path), 1 = bf16 pieces, 2 = f16 pieces, -1 = unknown (refused)
-static int sr_mlp_split_mode() { return sr_opt(SR_OPT_MLP_SPLIT); }
+// option SR_OPT_MLP_SPLIT: 0 = fp32 MFMA (the product path), 1 = bf16 pieces, 2 = f16 pieces, -1 = unknown (refused).  An
+// exported entry point reads it ONCE and hands the value (`split`) to the pack and the sweep it runs: both see one format.
 
 // lowest_cost = planes[argmax_d volume] (cost_volume.py:338-342, 374-378); first maximum wins
 __global__ void sr_argmax_planes_kernel(const float* __restrict__ cv, int64_t sb, int64_t sd, int64_t sp,
@@ -1067,7 +1067,7 @@ static float* sr_ws_packed(void* workspace, int B, int K, int C, int h, int w) {
 // planes it loses 2.4 ms of 46: the caller's decision, by batch size.  A reserve that would leave fewer than 8 CUs is ignored.
 // src_nhwc = null: cur is planar [B,16,h,w] and the source features are the workspace copy of sr_volume_prepare; else both are
 // the caller's channels-last buffers, cur [B, h*w, 16] and src_nhwc [B*K, h*w, 16], read where they lie.
-static int sr_mlp_volume_sweep_reserved(const float* cur, const float* src_nhwc, const float* invK_cur,
+static int sr_mlp_volume_sweep_reserved(int split, const float* cur, const float* src_nhwc, const float* invK_cur,
                                         const float* planes, int64_t ps_b,
                                         int64_t ps_d, int64_t ps_y, int64_t ps_x, float leaky_slope, int B, int K,
                                         int C, int h, int w, int D, float* out_cv, int64_t cv_sb, int64_t cv_sd,
@@ -1120,7 +1120,6 @@ static int sr_mlp_volume_sweep_reserved(const float* cur, const float* src_nhwc,
   const size_t w1_bytes = (size_t)sr_mlp_steps_var(K) * 1024;
   const size_t w2_bytes = (size_t)SR_MLP_STEPS2 * 1024;
   const size_t lds_max = 160 * 1024;
-  const int split = sr_mlp_split_mode();
   if (split < 0) return SR_ERR_INVALID_ARGUMENT;
   if (split) {   // fenced experiment: both weight blocks must fit the LDS (K <= 7); reads cur planar only
     if (p.cur_nhwc) return SR_ERR_UNSUPPORTED;
@@ -1156,8 +1155,9 @@ extern "C" int sr_mlp_volume_sweep(const float* cur, const float* invK_cur, cons
                                    int C, int h, int w, int D, float* out_cv, int64_t cv_sb, int64_t cv_sd,
                                    int64_t cv_sp, float* out_lowest, uint8_t* out_mask, void* workspace,
                                    size_t workspace_bytes, void* stream_) {
-  return sr_mlp_volume_sweep_reserved(cur, nullptr, invK_cur, planes, ps_b, ps_d, ps_y, ps_x, leaky_slope, B, K, C, h, w, D,
-                                      out_cv, cv_sb, cv_sd, cv_sp, out_lowest, out_mask, 0, workspace, workspace_bytes, stream_);
+  return sr_mlp_volume_sweep_reserved(sr_opt(SR_OPT_MLP_SPLIT), cur, nullptr, invK_cur, planes, ps_b, ps_d, ps_y, ps_x,
+                                      leaky_slope, B, K, C, h, w, D, out_cv, cv_sb, cv_sd, cv_sp, out_lowest, out_mask, 0,
+                                      workspace, workspace_bytes, stream_);
 }
 
 int sr_launch_argmax_planes(const float* cv, int64_t sb, int64_t sd, int64_t sp, SrPlanes planes, int B, int h, int w,
@@ -1167,19 +1167,25 @@ int sr_launch_argmax_planes(const float* cv, int64_t sb, int64_t sd, int64_t sp,
   return sr_hip_rc(hipGetLastError());
 }
 
-extern "C" int sr_mlp_pack_weights(const float* W1, const float* b1, const float* W2, const float* b2,
-                                   const float* W3, const float* b3, int hidden, int B, int K, int C, int h, int w,
-                                   void* workspace, size_t workspace_bytes, void* stream_) {
+static int sr_mlp_pack_split(int split, const float* W1, const float* b1, const float* W2, const float* b2,
+                             const float* W3, const float* b3, int hidden, int B, int K, int C, int h, int w,
+                             void* workspace, size_t workspace_bytes, void* stream_) {
   if (!W1 || !b1 || !W2 || !b2 || !W3 || !b3 || !workspace || K <= 0) return SR_ERR_INVALID_ARGUMENT;
   if (hidden != SR_HID || C != 16) return SR_ERR_UNSUPPORTED;
   if (workspace_bytes < sr_mlp_volume_workspace_bytes(B, K, C, h, w, hidden)) return SR_ERR_WORKSPACE_TOO_SMALL;
-  const int split = sr_mlp_split_mode();
   if (split < 0) return SR_ERR_INVALID_ARGUMENT;
   float* packed = sr_ws_packed(workspace, B, K, C, h, w);
   if (split == 1) hipLaunchKernelGGL((sr_mlp_pack_split_kernel<1>), dim3(64), dim3(256), 0, (hipStream_t)stream_, W1, b1, W2, b2, W3, b3, packed, K, C);
   else if (split == 2) hipLaunchKernelGGL((sr_mlp_pack_split_kernel<2>), dim3(64), dim3(256), 0, (hipStream_t)stream_, W1, b1, W2, b2, W3, b3, packed, K, C);
   else hipLaunchKernelGGL(sr_mlp_pack_kernel, dim3(64), dim3(256), 0, (hipStream_t)stream_, W1, b1, W2, b2, W3, b3, packed, K, C);
   return sr_hip_rc(hipGetLastError());
+}
+
+extern "C" int sr_mlp_pack_weights(const float* W1, const float* b1, const float* W2, const float* b2,
+                                   const float* W3, const float* b3, int hidden, int B, int K, int C, int h, int w,
+                                   void* workspace, size_t workspace_bytes, void* stream_) {
+  return sr_mlp_pack_split(sr_opt(SR_OPT_MLP_SPLIT), W1, b1, W2, b2, W3, b3, hidden, B, K, C, h, w, workspace, workspace_bytes,
+                           stream_);
 }
 
 // One body behind sr_mlp_volume_fwd and sr_mlp_volume_fwd_nhwc.  nhwc = false: cur is planar [B,16,h,w] and src [B*K,16,h,w]
@@ -1201,18 +1207,16 @@ static int sr_mlp_volume_run(bool nhwc, const float* cur, const float* src, cons
     if (((size_t)cur | (size_t)src) & 15) return SR_ERR_INVALID_ARGUMENT;   // a pixel is read as four 16-byte pieces
   }
   if (hidden != SR_HID || C != 16) return SR_ERR_UNSUPPORTED;
-  if (nhwc) {
-    const int split = sr_mlp_split_mode();
-    if (split < 0) return SR_ERR_INVALID_ARGUMENT;
-    if (split) return SR_ERR_UNSUPPORTED;   // the split-precision kernel reads cur planar: sr_mlp_volume_fwd serves it
-  }
+  const int split = sr_opt(SR_OPT_MLP_SPLIT);   // the one read of this call: the pack and the sweep below take the value
+  // the split-precision kernel reads cur planar: sr_mlp_volume_fwd serves it
+  if (nhwc && split) return split < 0 ? SR_ERR_INVALID_ARGUMENT : SR_ERR_UNSUPPORTED;
   if (workspace_bytes < sr_mlp_volume_workspace_bytes(B, K, C, h, w, hidden)) return SR_ERR_WORKSPACE_TOO_SMALL;
   int rc = nhwc ? sr_launch_geom(K_src, T_src_cur, T_cur_src, sr_ws_geom(workspace), B * K, (hipStream_t)stream_)
                 : sr_volume_prepare(src, K_src, T_src_cur, T_cur_src, B, K, C, h, w, workspace, workspace_bytes, stream_);
   if (rc) return rc;
-  rc = sr_mlp_pack_weights(W1, b1, W2, b2, W3, b3, hidden, B, K, C, h, w, workspace, workspace_bytes, stream_);
+  rc = sr_mlp_pack_split(split, W1, b1, W2, b2, W3, b3, hidden, B, K, C, h, w, workspace, workspace_bytes, stream_);
   if (rc) return rc;
-  return sr_mlp_volume_sweep_reserved(cur, nhwc ? src : nullptr, invK_cur, planes, ps_b, ps_d, ps_y, ps_x, leaky_slope, B, K,
+  return sr_mlp_volume_sweep_reserved(split, cur, nhwc ? src : nullptr, invK_cur, planes, ps_b, ps_d, ps_y, ps_x, leaky_slope, B, K,
                                       C, h, w, D, out_cv, cv_sb, cv_sd, cv_sp, out_lowest, out_mask, reserve_cus, workspace,
                                       workspace_bytes, stream_);
 }

@@ -160,7 +160,6 @@ __device__ __forceinline__ void wn_rv_row(const float4 (&w)[4], float4 (&a)[4]) 
   a[0] = f4sub(w[0], w[2]); a[1] = f4add(w[1], w[2]); a[2] = f4sub(w[2], w[1]); a[3] = f4sub(w[1], w[3]);
 }
 
-// ---- split-precision variant (sr_wino_split.hip; fenced experiment, SR_WINO_SPLIT=bf16|f16) ----
-int sr_wino_split_mode();   // 0 off, 1 bf16, 2 f16, -1 unknown value (read per call)
+// ---- split-precision variant (sr_wino_split.hip; fenced experiment).  mode: 1 bf16, 2 f16 -- the split_format argument ----
 int sr_wino_split_pack(const float* weight, int Cout, int Cin, float* packed, int mode, hipStream_t stream);
 int sr_wino_split_launch(const SrWinoParams& p, int nt, int blocks, int mode, hipStream_t stream);

@@ -557,12 +557,12 @@ extern "C" size_t sr_wino_packed_weight_floats(int Cout, int Cin) {
   return 16 * G * 2 * Co_pad * 4;
 }
 
-extern "C" int sr_wino_pack_weights(const float* weight, int Cout, int Cin, float* packed, void* stream_) {
+// split_format 1 / 2: the fenced experiment's 16-bit pieces (sr_wino_split.hip) in the same buffer; the launch is told the same
+extern "C" int sr_wino_pack_weights(const float* weight, int Cout, int Cin, int split_format, float* packed, void* stream_) {
   if (!weight || !packed || Cout <= 0 || Cin <= 0) return SR_ERR_INVALID_ARGUMENT;
   const int G = ((Cin + 15) / 16) * 2, Co_pad = ((Cout + 31) / 32) * 32;
-  const int split = sr_wino_split_mode();   // fenced experiment (sr_wino_split.hip): the same buffer, 16-bit pieces inside
-  if (split < 0) return SR_ERR_INVALID_ARGUMENT;
-  if (split) return sr_wino_split_pack(weight, Cout, Cin, packed, split, (hipStream_t)stream_);
+  if (split_format < 0 || split_format > 2) return SR_ERR_INVALID_ARGUMENT;
+  if (split_format) return sr_wino_split_pack(weight, Cout, Cin, packed, split_format, (hipStream_t)stream_);
   hipLaunchKernelGGL(sr_wino_pack_kernel, dim3(256), dim3(256), 0, (hipStream_t)stream_, weight, packed, Cout, Cin, G,
                      Co_pad);
   return sr_hip_rc(hipGetLastError());
@@ -638,7 +638,7 @@ extern "C" int sr_wino_conv_plan(int B, int H, int W, int Cin, int Cout, int all
 static int sr_wino_run(const float* in, int64_t in_batch_stride, int in_pix_stride, const float* packed_u,
                        const float* bias, const float* residual, int64_t res_batch_stride, int res_pix_stride,
                        float* out, int64_t out_batch_stride, int out_pix_stride, int B, int H, int W, int Cin, int Cout,
-                       float leaky_slope, void* workspace, size_t workspace_bytes, void* stream_, int io = 0) {
+                       float leaky_slope, int split, void* workspace, size_t workspace_bytes, void* stream_, int io = 0) {
   if (io < 0 || io > 2) return SR_ERR_INVALID_ARGUMENT;
   const uintptr_t amask = io ? 7 : 15;   // 4 channels = 16 bytes of fp32 or 8 bytes of fp16 / bf16
   if (B < 0 || H <= 0 || W <= 0 || Cin <= 0 || Cout <= 0) return SR_ERR_INVALID_ARGUMENT;
@@ -661,8 +661,7 @@ static int sr_wino_run(const float* in, int64_t in_batch_stride, int in_pix_stri
                     (!bias || sr_ptr_aligned(bias, 15)) &&
                     (!residual || sr_rows_aligned(residual, res_batch_stride, res_pix_stride, amask, 4));
   if (io && !vout) return SR_ERR_UNSUPPORTED;   // 16-bit I/O: the vector instantiation only
-  const int split = sr_wino_split_mode();
-  if (split < 0) return SR_ERR_INVALID_ARGUMENT;
+  if (split < 0 || split > 2) return SR_ERR_INVALID_ARGUMENT;   // the packed weight's format (sr_wino_pack_weights)
   if (split && (io || !vout)) return SR_ERR_UNSUPPORTED;   // split precision: fp32 tensors, the vector instantiation only
   // Per-image byte offsets are 32-bit (buffer addressing).  The input-side limit applies to the vector STAGING too --
   // sr_wino_kernel<NT, true, false> --, not only to the vector epilogue: its buffer descriptors carry 32-bit byte offsets
@@ -748,7 +747,7 @@ extern "C" int sr_conv3x3_wino_nhwc_fwd(const float* in, int64_t in_batch_stride
                                         int64_t out_batch_stride, int out_pix_stride, int B, int H, int W, int Cin,
                                         int Cout, float leaky_slope, void* stream_) {
   return sr_wino_run(in, in_batch_stride, in_pix_stride, packed_u, bias, residual, res_batch_stride, res_pix_stride, out,
-                     out_batch_stride, out_pix_stride, B, H, W, Cin, Cout, leaky_slope, nullptr, 0, stream_);
+                     out_batch_stride, out_pix_stride, B, H, W, Cin, Cout, leaky_slope, 0, nullptr, 0, stream_);
 }
 
 // The same operator on fp16 (io_dtype = 1) / bf16 (2) activation tensors: input, residual and output in HBM are 16-bit
@@ -759,16 +758,16 @@ extern "C" int sr_conv3x3_wino_io_nhwc_fwd(const void* in, int64_t in_batch_stri
                                            int H, int W, int Cin, int Cout, float leaky_slope, int io_dtype, void* stream_) {
   return sr_wino_run((const float*)in, in_batch_stride, in_pix_stride, packed_u, bias, (const float*)residual,
                      res_batch_stride, res_pix_stride, (float*)out, out_batch_stride, out_pix_stride, B, H, W, Cin, Cout,
-                     leaky_slope, nullptr, 0, stream_, io_dtype);
+                     leaky_slope, 0, nullptr, 0, stream_, io_dtype);
 }
 
 extern "C" int sr_conv3x3_wino_splitk_nhwc_fwd(const float* in, int64_t in_batch_stride, int in_pix_stride,
                                                const float* packed_u, const float* bias, const float* residual,
                                                int64_t res_batch_stride, int res_pix_stride, float* out,
                                                int64_t out_batch_stride, int out_pix_stride, int B, int H, int W,
-                                               int Cin, int Cout, float leaky_slope, void* workspace,
-                                               size_t workspace_bytes, void* stream_) {
+                                               int Cin, int Cout, float leaky_slope, int split_format,
+                                               void* workspace, size_t workspace_bytes, void* stream_) {
   return sr_wino_run(in, in_batch_stride, in_pix_stride, packed_u, bias, residual, res_batch_stride, res_pix_stride, out,
-                     out_batch_stride, out_pix_stride, B, H, W, Cin, Cout, leaky_slope, workspace, workspace_bytes,
-                     stream_);
+                     out_batch_stride, out_pix_stride, B, H, W, Cin, Cout, leaky_slope, split_format, workspace,
+                     workspace_bytes, stream_);
 }

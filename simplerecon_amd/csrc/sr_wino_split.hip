@@ -383,8 +383,6 @@ __global__ __launch_bounds__(256, NT == 1 ? SR_WS_NT1_WGS : 2) void sr_wino_spli
 
 // ------------------------------------------------------------------ host side (called from sr_wino.hip) -------------
 
-int sr_wino_split_mode() { return sr_opt(SR_OPT_WINO_SPLIT); }
-
 int sr_wino_split_pack(const float* weight, int Cout, int Cin, float* packed, int mode, hipStream_t stream) {
   const int G = ((Cin + 15) / 16) * 2, Co_pad = ((Cout + 31) / 32) * 32;
   unsigned* wu = reinterpret_cast<unsigned*>(packed);
@@ -397,7 +395,7 @@ int sr_wino_split_pack(const float* weight, int Cout, int Cin, float* packed, in
 int sr_wino_split_launch(const SrWinoParams& p, int nt, int blocks, int mode, hipStream_t stream) {
   const size_t lds = (size_t)WN_LDS_FLOATS(nt) * sizeof(float);
   if (nt == 1 && SR_WS_NT1_WGS != 2) {   // (tuning builds) the persistent grid follows the occupancy the kernel was compiled for
-    blocks = blocks / 2 * SR_WS_NT1_WGS;
+    blocks = sr_device_cus() * SR_WS_NT1_WGS;   // (not from the caller's count: clamped to p.total = 1 it scaled to no grid at all)
     if (blocks > p.total) blocks = p.total;
   }
 #define WS_LAUNCH(NTV, FMTV)                                                                                      \

@@ -6,9 +6,10 @@ every fp32 operand as two 16-bit pieces, three exact products, fp32 accumulate. 
 The modes are entries of the library's option table (`SR_MLP_SPLIT`, `SR_WINO_SPLIT`: include/simplerecon_hip.h), set
 through `_lib.set_option` -- the process environment is neither read nor written (r04 mutated os.environ, which the library
 re-read with getenv() on every launch: a data race against launches on other threads, and inherited by child processes).
-The table is process-wide: launches from OTHER threads inside the block run split as well, and a HIP graph captured inside
-the block keeps the split kernels after it.  The block must enclose the forward calls themselves; packed weights are
-re-packed when the mode changes (`ops.packed_wino_weight`'s cache key)."""
+The SWITCH is process-wide: calls that OTHER threads start inside the block run split as well, and a HIP graph captured inside
+the block keeps the split kernels after it.  A call in flight is not touched: each call reads its switch once and carries
+that value from its weight packing to its launch (the Winograd format is an argument of both library calls and the key of
+`ops.packed_wino_weight`'s cache; the sweep's entry point reads once).  The block must enclose the forward calls themselves."""
 import contextlib
 
 from . import _lib

@@ -92,11 +92,12 @@ def _await_pack(e):
 _PACK_DIMS = {"conv": 3, "wino": 2, "wino4": 2, "stem": 1, "conv3x3_c16": 2}
 
 
-def _pack(kind, w):
-    """The library's `kind` packing of the contiguous fp32 weight `w` ([Co, Ci, k, k]) into a new tensor (uncached)."""
+def _pack(kind, w, *fmt):
+    """The library's `kind` packing of the contiguous fp32 weight `w` ([Co, Ci, k, k]) into a new tensor (uncached).  `fmt`:
+    what the pack call takes behind the dimensions ("wino": the split format, which the launch is handed too)."""
     dims = w.shape[:_PACK_DIMS[kind]]
     packed = torch.empty(getattr(_lib.lib(), f"sr_{kind}_packed_weight_floats")(*dims), dtype=torch.float32, device=w.device)
-    _lib.call(f"sr_{kind}_pack_weights", w.device, w, *dims, packed)
+    _lib.call(f"sr_{kind}_pack_weights", w.device, w, *dims, *fmt, packed)
     return packed
 
 
@@ -209,12 +210,12 @@ def _check_conv(conv):
         raise _lib.HipLibraryError(f"unsupported Conv2d configuration for the HIP path: {conv}")
 
 
-def _pack_folded(kind, conv, bn):
-    """(the `kind` packing of conv's weight with `bn` folded in, bias)."""
+def _pack_folded(kind, conv, bn, *fmt):
+    """(the `kind` packing (_pack) of conv's weight with `bn` folded in, bias)."""
     _lib.require_device_f32("conv weight", conv.weight)
     _check_conv(conv)
     w, bias = _effective_weight(conv, bn)
-    return _pack(kind, w), bias
+    return _pack(kind, w, *fmt), bias
 
 
 def packed_weight(conv: nn.Conv2d, bn=None):
@@ -259,14 +260,15 @@ def linear(x, lin: nn.Linear, leaky=None):
 
 def wino_split_mode():
     """'' (off: fp32 MFMA, the product path), 'bf16' or 'f16': the fenced split-precision Winograd variant -- the library's
-    option SR_WINO_SPLIT (one atomic load; set with _lib.set_option / experimental.split_precision)."""
+    option SR_WINO_SPLIT (set with _lib.set_option / experimental.split_precision), which a call reads once (`split`)."""
     return _lib.split_mode_name("SR_WINO_SPLIT")
 
 
-def packed_wino_weight(conv: nn.Conv2d, bn=None):
-    """(Winograd-packed weight U = G g G^T, bias); cached until a parameter changes."""
-    key = (_state_key(conv, bn), wino_split_mode())   # (the fenced split-precision variant packs 16-bit pieces)
-    return _cached(conv, "wino", key, _pack_folded, "wino", conv, bn)
+def packed_wino_weight(conv: nn.Conv2d, bn=None, split=None):
+    """(Winograd-packed weight U = G g G^T, bias); cached until a parameter or the format changes.  `split`: the format, 0 /
+    1 / 2 = fp32 / bf16 pieces / f16 pieces (None: what SR_WINO_SPLIT says now) -- the launch on this weight takes the same."""
+    split = _lib.get_option("SR_WINO_SPLIT") if split is None else split
+    return _cached(conv, "wino", (_state_key(conv, bn), split), _pack_folded, "wino", conv, bn, split)
 
 
 # Which 3x3 / stride-1 layers take the F(4x4, 3x3) kernel (csrc/sr_wino4.hip): "1" (default) = the library's rule
@@ -349,12 +351,12 @@ def conv2d(x, conv: nn.Conv2d, residual=None, leaky=None, out=None, bn=None, act
     isb, isp = _strides(x)
     osb, osp = _strides(out)
     rsb, rsp = _strides(residual) if residual is not None else (0, 0)
-    split = use_wino and wino_split_mode()
+    split = _lib.get_option("SR_WINO_SPLIT") if use_wino else 0   # read ONCE: the cache key, the pack's and the launch's format
     if split and not (ci % 4 == 0 and co % 4 == 0 and _aligned16(x, isb, isp) and _aligned16(out, osb, osp)
                       and _aligned16(residual, rsb, rsp)):
         # the fenced split-precision Winograd (SR_WINO_SPLIT, csrc/sr_wino_split.hip) has the vector instantiation only:
         # unaligned tensors and channel counts that are no multiple of 4 take the direct fp32 kernel instead
-        use_wino = split = False
+        use_wino, split = False, 0
     if gate is not None:
         _lib.require_device_f32("gate", gate)
         if k != 1 or s != 1 or tuple(gate.shape) != (b, ci) or not gate.is_contiguous():
@@ -386,14 +388,8 @@ def conv2d(x, conv: nn.Conv2d, residual=None, leaky=None, out=None, bn=None, act
                                WINO4_VARIANT or w4_form) == 0:
         return out
     if use_wino:
-        # pack and launch must see ONE split mode.  A plain acquire / release -- a context manager object per call
-        # costs a microsecond on a launch path that is host-bound at batch 1
-        _lib.SPLIT_GUARD.acquire()
-        try:
-            if _conv_wino(lib, x, *packed_wino_weight(conv, bn), residual, out, strides, shape, slope) == 0:
-                return out
-        finally:
-            _lib.SPLIT_GUARD.release()
+        if _conv_wino(lib, x, *packed_wino_weight(conv, bn, split), residual, out, strides, shape, slope, split) == 0:
+            return out
         # SR_ERR_UNSUPPORTED from the Winograd entry point (a per-image byte range past 2^31: its buffer descriptors carry 32-bit
         # offsets): the implicit-GEMM kernel serves the shape with 64-bit addressing, as it did before r04
         wp, bias = packed_weight(conv, bn)
@@ -473,18 +469,18 @@ def _conv_wino4(lib, x, wp, bias, residual, out, strides, shape, slope, variant)
                    slope, variant, _lib.stream_ptr(x.device))
 
 
-def _conv_wino(lib, x, wp, bias, residual, out, strides, shape, slope, workspace=True, fallback=True):
-    """3x3 / stride 1: F(2x2, 3x3) Winograd (csrc/sr_wino.hip, or the fenced split-precision variant of SR_WINO_SPLIT) on the
-    Winograd-packed weight `wp`.  workspace=False: no split-K scratch is handed over, so the launcher never splits K (the
-    training path); fallback=False: SR_ERR_UNSUPPORTED raises like any other error (no direct-kernel launch stands behind)."""
+def _conv_wino(lib, x, wp, bias, residual, out, strides, shape, slope, split, workspace=True, fallback=True):
+    """3x3 / stride 1: F(2x2, 3x3) Winograd (csrc/sr_wino.hip; the fenced split-precision variant for `split` 1 / 2) on the
+    weight `wp`, Winograd-packed in format `split`.  workspace=False: no split-K scratch is handed over, so the launcher never
+    splits K (the training path); fallback=False: SR_ERR_UNSUPPORTED raises like any other error (no direct launch behind)."""
     isb, isp, osb, osp, rsb, rsp = strides
     b, ci, h, w, co = shape[:5]
     # 0 unless it splits K
     nbytes = _shape_query(lib, "sr_wino_splitk_workspace_bytes", b, h, w, ci, co, dev=x.device.index) if workspace else 0
     ws = _workspace(x.device, "wino_splitk", nbytes) if nbytes else None
-    return _launch(x, shape, "sr_conv3x3_wino_nhwc_fwd", fallback and not wino_split_mode(), lib.sr_conv3x3_wino_splitk_nhwc_fwd,
+    return _launch(x, shape, "sr_conv3x3_wino_nhwc_fwd", fallback and not split, lib.sr_conv3x3_wino_splitk_nhwc_fwd,
                    _lib.ptr(x), isb, isp, _lib.ptr(wp), _lib.ptr(bias), _lib.ptr(residual), rsb, rsp, _lib.ptr(out), osb, osp,
-                   b, h, w, ci, co, slope, _lib.ptr(ws), nbytes, _lib.stream_ptr(x.device))
+                   b, h, w, ci, co, slope, split, _lib.ptr(ws), nbytes, _lib.stream_ptr(x.device))
 
 
 def _conv_direct(lib, x, wp, bias, residual, out, strides, shape, slope, pads, replicate, workspace=True):

@@ -200,26 +200,23 @@ def test_option_table_is_explicit_and_seeded_once_from_the_environment():
     assert lib.sr_option_set(n, 0, None) == 1 and lib.sr_option_get(-1, C.byref(d)) == 1   # SR_ERR_INVALID_ARGUMENT
 
 
-def test_split_option_listeners_run_under_the_split_guard():
-    """A split mode's library value, Python mirror and listeners change together under SPLIT_GUARD: no pack + launch on
-    another thread sees them disagree (a listener probes the guard from a second thread)."""
-    import threading
+def test_set_option_updates_library_mirror_and_listeners_in_that_order():
+    """set_option: the library's value first, then the Python mirror, then the listeners -- a listener (the plan-query caches)
+    sees both already changed, for a split mode like for any other switch."""
     from simplerecon_amd import _lib
-    seen = {}
+    lib, seen = _lib.lib(), []
 
     def probe(name, value):
-        def try_guard():
-            got = _lib.SPLIT_GUARD.acquire(blocking=False)
-            if got:
-                _lib.SPLIT_GUARD.release()
-            seen[name] = got
-        t = threading.Thread(target=try_guard)
-        t.start()
-        t.join()
+        c = ctypes.c_int(-7)
+        assert lib.sr_option_get(lib.sr_option_id(name.encode()), ctypes.byref(c)) == 0
+        seen.append((name, value, c.value, _lib.get_option(name)))
+    saved = _lib.get_option("SR_WINO_SPLIT")
     _lib.OPTION_LISTENERS.append(probe)
     try:
-        for name in ("SR_MLP_SPLIT", "SR_WINO_SPLIT", "SR_PW_NT"):
-            _lib.set_option(name, _lib.get_option(name))
+        _lib.set_option("SR_WINO_SPLIT", "bf16")
+        _lib.set_option("SR_PW_NT", _lib.get_option("SR_PW_NT"))
     finally:
         _lib.OPTION_LISTENERS.remove(probe)
-    assert seen == {"SR_MLP_SPLIT": False, "SR_WINO_SPLIT": False, "SR_PW_NT": True}
+        _lib.set_option("SR_WINO_SPLIT", saved)
+    nt = _lib.get_option("SR_PW_NT")
+    assert seen == [("SR_WINO_SPLIT", 1, 1, 1), ("SR_PW_NT", nt, nt, nt)]

@@ -84,6 +84,31 @@ def test_wino_fp32_refuses_null_and_spans_only():
     assert call(B=1, H=16384, W=16384, Cin=8, Cout=8) == UNSUPPORTED
 
 
+@pytest.mark.parametrize("fmt", [1, 2])
+def test_wino_split_format_has_the_vector_instantiation_only(fmt, sr_option):
+    """split_format 1 / 2 on the split-K entry point selects the split-precision kernel: what the scalar instantiation would
+    take is refused, with the option that used to select the kernel off or on another mode -- the argument alone decides."""
+    for option in (0, 3 - fmt):
+        sr_option("SR_WINO_SPLIT", option)
+        for ws in ((None, 0), (WS, 1 << 20)):
+            call = _conv3x3("sr_conv3x3_wino_splitk_nhwc_fwd", (fmt, *ws))
+            for kw in (dict(in_=None), dict(wp=None), dict(out=None)):
+                assert call(**kw) == INVALID, kw
+            for kw in MISALIGNED:
+                assert call(**kw) == UNSUPPORTED, kw
+            for which in ("in", "out", "res"):
+                assert call(**_big(which)) == UNSUPPORTED, which
+
+
+def test_wino_split_format_is_checked_before_anything_is_launched(sr_option):
+    """A split_format outside 0..2 is an invalid argument of the pack and of the launch, whatever the option says."""
+    for option in (0, 2):
+        sr_option("SR_WINO_SPLIT", option)
+        for fmt in (3, -1):
+            assert _conv3x3("sr_conv3x3_wino_splitk_nhwc_fwd", (fmt, WS, 1 << 20))() == INVALID
+            assert _lib.lib().sr_wino_pack_weights(IN, 16, 16, fmt, WP, None) == INVALID
+
+
 def _pw(io):
     lib = _lib.lib()
 

@@ -28,7 +28,7 @@ def _wino_io(x, conv, res, slope, out):
     co = conv.out_channels
     wp = torch.empty(lib.sr_wino_packed_weight_floats(co, ci), dtype=torch.float32, device=DEV)
     st = _lib.stream_ptr(x.device)
-    _lib.check(lib.sr_wino_pack_weights(_lib.ptr(conv.weight.detach().contiguous()), co, ci, _lib.ptr(wp), st), "pack")
+    _lib.check(lib.sr_wino_pack_weights(_lib.ptr(conv.weight.detach().contiguous()), co, ci, 0, _lib.ptr(wp), st), "pack")
     isb, isp = ops._strides(x)
     osb, osp = ops._strides(out)
     rsb, rsp = ops._strides(res) if res is not None else (0, 0)

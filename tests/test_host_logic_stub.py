@@ -31,6 +31,7 @@ def make_stub(monkeypatch):
     calls.args = []          # (name, arguments) of every stubbed call
     calls.option_sets = []   # (id, value) of every sr_option_set, forwarded to the real library
     calls.rc = {}            # entry point -> the code it returns (default 0: success)
+    calls.hooks = {}         # entry point -> callable(*args) run inside the stubbed call
 
     class Stream:
         cuda_stream = 0
@@ -61,6 +62,8 @@ def make_stub(monkeypatch):
                     assert isinstance(v, int), (self.name, type(v), v)
             calls.append(self.name)
             calls.args.append((self.name, args))
+            if self.name in calls.hooks:
+                calls.hooks[self.name](*args)
             if self.name == "sr_conv_prefers_wino":
                 return int(calls.prefer_wino)
             if self.name == "sr_conv_prefers_wino4":
@@ -362,6 +365,69 @@ def test_split_precision_switch_repacks_the_cached_winograd_weight(stub, monkeyp
     sr_option("SR_WINO_SPLIT", "0")
     ops.packed_wino_weight(conv)
     assert stub.count("sr_wino_pack_weights") == n + 3        # and back to fp32 fragments
+
+
+def test_a_split_mode_set_during_the_pack_does_not_reach_the_launch(stub, monkeypatch, sr_option):
+    """The Winograd split format is read once per call and carried from the pack to the launch as a value (the C ABI's
+    `split_format`): here another thread sets SR_WINO_SPLIT to another mode from INSIDE sr_wino_pack_weights, during an
+    ops.conv2d and during an autograd_ops._ConvBiasAct forward.  The launch that follows carries the format the pack carried;
+    the next call, under the mode now set, packs again in that mode (the cache keys on the format); and the thread that
+    set the mode was never kept waiting.  This replaces test_split_option_listeners_run_under_the_split_guard of
+    tests/test_abi.py, which tested the lock that used to stand for the property.  Before the format became an argument the
+    training-path half failed -- _conv_raw held no lock and the launcher read the option table again after the pack, so the
+    fp16-piece weights met the bf16 kernel -- and in the conv2d half the setting thread hung on the lock instead."""
+    import threading
+
+    from torch import nn
+
+    from simplerecon_amd import autograd_ops, ops
+    monkeypatch.setattr(ops, "_PACKED", weakref.WeakKeyDictionary())
+    stub.prefer_wino = True
+    pack_fmt = _lib.SIGNATURES["sr_wino_pack_weights"][1].index(ctypes.c_int, 3)                # behind Cout, Cin
+    launch_fmt = _lib.SIGNATURES["sr_conv3x3_wino_splitk_nhwc_fwd"][1].index(ctypes.c_float) + 1   # behind leaky_slope
+    assert pack_fmt == 3 and launch_fmt == 17
+    kept_waiting = []
+
+    def set_another_mode(*args):
+        t = threading.Thread(target=_lib.set_option, args=("SR_WINO_SPLIT", {0: 2, 1: 2, 2: 1}[args[pack_fmt]]))
+        t.start()
+        t.join(10)   # (returns at once unless set_option blocks)
+        kept_waiting.append(t.is_alive())
+    stub.hooks["sr_wino_pack_weights"] = set_another_mode
+
+    def formats():
+        """[format of each pack, format of each Winograd launch] since the last look"""
+        got = [[a[pack_fmt] for n, a in stub.args if n == "sr_wino_pack_weights"],
+               [a[launch_fmt] for n, a in stub.args if n == "sr_conv3x3_wino_splitk_nhwc_fwd"]]
+        del stub[:], stub.args[:]
+        return got
+    conv = nn.Conv2d(16, 32, 3, padding=1)
+    x = torch.zeros(1, 16, 8, 16).contiguous(memory_format=torch.channels_last)
+    sr_option("SR_WINO_SPLIT", "f16")
+    del stub[:], stub.args[:]
+    with torch.no_grad():
+        ops.conv2d(x, conv)
+        assert formats() == [[2], [2]] and _lib.get_option("SR_WINO_SPLIT") == 1   # packed as f16 pieces, launched as such
+        ops.conv2d(x, conv)
+        assert formats() == [[1], [1]] and _lib.get_option("SR_WINO_SPLIT") == 2   # the mode set meanwhile: packed again
+        ops.conv2d(x, conv)
+        assert formats() == [[2], [2]]   # (the cache holds one format per layer)
+        del stub.hooks["sr_wino_pack_weights"]
+        ops.conv2d(x, conv)
+        assert formats() == [[1], [1]]
+        ops.conv2d(x, conv)
+        assert formats() == [[], [1]]    # nothing set in between: a cache hit
+    stub.hooks["sr_wino_pack_weights"] = set_another_mode
+    w, b = conv.weight.detach().requires_grad_(), conv.bias.detach()
+    _lib.set_option("SR_WINO_SPLIT", "f16")
+    autograd_ops._ConvBiasAct.apply(x, w, b, None, 1, 0.1, None)
+    assert formats() == [[2], [2]] and _lib.get_option("SR_WINO_SPLIT") == 1
+    autograd_ops._ConvBiasAct.apply(x, w, b, None, 1, 0.1, None)
+    assert formats() == [[1], [1]] and _lib.get_option("SR_WINO_SPLIT") == 2
+    _lib.set_option("SR_WINO_SPLIT", 0)
+    autograd_ops._ConvBiasAct.apply(x, w, b, None, 1, 0.1, None)
+    assert formats() == [[0], [0]]
+    assert kept_waiting == [False] * 6
 
 
 def _cached_entry_points():

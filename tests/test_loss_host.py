@@ -96,4 +96,4 @@ def test_header_states_the_filters_and_rules():
     for phrase in ("blur_pool2d(x, 3)", "spatial_gradient(x)", "gaussian_blur2d(x, (5,5), (2,2))", "zero-weight taps",
                    "round half to even", "nanmean", "#define SR_LOSS_MAX_SOURCES 15"):
         assert phrase in sec, phrase
-    assert "sr_abi_version" in _lib.SIGNATURES and _lib.ABI_VERSION == 4
+    assert "sr_abi_version" in _lib.SIGNATURES and _lib.ABI_VERSION == 5

@@ -184,7 +184,7 @@ def test_symbols_are_declared_bound_and_exported():
     for name in SYMBOLS:
         assert re.search(r"\b" + name + r"\s*\(", hdr), f"{name} is not declared in the header"
         assert name in _lib.SIGNATURES and hasattr(raw, name)
-    assert _lib.ABI_VERSION == 4 and raw.sr_abi_version() == 4
+    assert _lib.ABI_VERSION == 5 and raw.sr_abi_version() == 5
     for macro, value in (("SR_RASTER_CULL_NONE", 0), ("SR_RASTER_CULL_BACK", 1), ("SR_RASTER_MAX_SIDE", 32768),
                          ("SR_RASTER_RECORD_BYTES", 80), ("SR_RASTER_MASK_VIEWS", 64)):
         assert re.search(rf"#define {macro} {value}\b", hdr)

@@ -341,7 +341,7 @@ def test_symbols_are_declared_bound_and_exported():
         assert re.search(r"\b" + name + r"\s*\(", hdr), f"{name} is not declared in the header"
         assert name in _lib.SIGNATURES and hasattr(raw, name)
         getattr(raw, name).restype, getattr(raw, name).argtypes = _lib.SIGNATURES[name]
-    assert _lib.ABI_VERSION == 4 and raw.sr_abi_version() == 4
+    assert _lib.ABI_VERSION == 5 and raw.sr_abi_version() == 5
     for macro, value in (("SR_SHADE_UNLIT", 0), ("SR_SHADE_NORMALS", 1), ("SR_SHADE_LAMBERT", 2),
                          ("SR_SHADE_NORMAL_SMOOTH", 0), ("SR_SHADE_NORMAL_FLAT", 1), ("SR_SHADE_LIGHT_DIRECTIONAL", 0),
                          ("SR_SHADE_LIGHT_POINT", 1), ("SR_SHADE_LIGHT_HEAD", 2), ("SR_SHADE_MAX_LIGHTS", 32),
