@@ -503,6 +503,9 @@ int sr_conv3x3_c16_nhwc_fwd(const float* in, int64_t in_batch_stride, int in_pix
  *  depth [B,H,W] fp16, depth_mask [B,H,W] bool or NULL, K / T [B,4,4] fp16 row-major (intrinsics, cam_T_world)
  *  min_depth, max_depth, truncation (= truncation_size * voxel_size), maxW: the fuser's python scalars as fp32;
  *  depth_range = max_depth - min_depth evaluated in double, as fp32.
+ *  B <= 1024 per call (per-frame state in LDS: 48 B + 16 ceil(B / 16) bytes), else SR_ERR_UNSUPPORTED; the update is
+ *  sequential per voxel, so a longer batch is exactly consecutive calls over consecutive frames (TSDFFuser.integrate_depth
+ *  splits it that way).
  */
 int sr_tsdf_integrate_fwd(void* tsdf_values, void* tsdf_weights, const void* voxel_coords, int X, int Y, int Z,
                           float origin_x, float origin_y, float origin_z, float voxel_size, const void* depth,

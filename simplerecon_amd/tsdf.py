@@ -202,6 +202,7 @@ class TSDF:
 
 class TSDFFuser:
     """Fuses depth maps into a TSDF volume (reference tools/tsdf.py:176-320)."""
+    MAX_FRAMES_PER_CALL = 1024  # sr_tsdf_integrate_fwd refuses more; integrate_depth splits longer batches
 
     def __init__(self, tsdf, min_depth=0.5, max_depth=5.0, use_gpu=True):
         if not use_gpu:
@@ -276,9 +277,14 @@ class TSDFFuser:
             ox = oy = oz = 0.0
         if b == 0:
             return
-        _lib.call("sr_tsdf_integrate_fwd", dev, vol.tsdf_values, vol.tsdf_weights, coords, X, Y, Z, ox, oy, oz,
-                  float(vol.voxel_size), depth, mask, K, T, b, h, w, float(self.min_depth), float(self.max_depth),
-                  float(self.max_depth - self.min_depth), float(self.truncation), float(self.maxW))
+        # one launch takes at most MAX_FRAMES_PER_CALL frames (its per-frame state lives in LDS); the update is sequential
+        # per voxel, so consecutive calls over consecutive frames give exactly the result of one long batch
+        for b0 in range(0, b, self.MAX_FRAMES_PER_CALL):
+            b1 = min(b0 + self.MAX_FRAMES_PER_CALL, b)
+            _lib.call("sr_tsdf_integrate_fwd", dev, vol.tsdf_values, vol.tsdf_weights, coords, X, Y, Z, ox, oy, oz,
+                      float(vol.voxel_size), depth[b0:b1], None if mask is None else mask[b0:b1], K[b0:b1], T[b0:b1],
+                      b1 - b0, h, w, float(self.min_depth), float(self.max_depth),
+                      float(self.max_depth - self.min_depth), float(self.truncation), float(self.maxW))
 
 
 class OurFuser:

@@ -7,6 +7,7 @@ import pytest
 import torch
 
 import mesh_oracle as mo
+import tsdf_cases
 from simplerecon_amd import _lib
 from simplerecon_amd.tsdf import TSDF, OurFuser, marching_cubes
 
@@ -83,6 +84,16 @@ def test_mesh_matches_oracle(name):
     vol = CASES[name]()
     _, f, _ = _assert_matches_oracle(vol)
     assert len(f) > 0
+
+
+@pytest.mark.parametrize("shape, nbricks, chunk, busy", [((160, 168, 128), 1680, 2, 840), ((200, 200, 160), 3125, 4, 782)])
+def test_mesh_matches_oracle_past_1024_bricks(shape, nbricks, chunk, busy):
+    """More bricks than sr_mesh_scan_kernel has threads: every thread sums and offsets `chunk` > 1 bricks, and with chunk 4
+    the threads from 782 on have none (tsdf_cases.mesh_plan restates the arithmetic)."""
+    plan = tsdf_cases.mesh_plan(shape)
+    assert (plan["nbricks"], plan["chunk"], plan["busy_threads"]) == (nbricks, chunk, busy) and busy < 1024 < nbricks
+    _, f, _ = _assert_matches_oracle(noise(shape, 11, smooth=6))
+    assert len(f) > 1000
 
 
 def test_ambiguous_faces_are_exercised():
@@ -174,9 +185,9 @@ def test_scalar_path_matches_vector_path():
     assert torch.equal(a.vertices, b.vertices) and torch.equal(a.faces, b.faces) and torch.equal(a.normals, b.normals)
 
 
-def _room(fuser, frames=4, seed=3):
+def _room(fuser, frames=4, seed=3, near=1.0, span=1.5):
     g = torch.Generator(device="cpu").manual_seed(seed)
-    depth = (1.0 + 1.5 * torch.rand((frames, 1, 48, 64), generator=g))
+    depth = (near + span * torch.rand((frames, 1, 48, 64), generator=g))
     depth = torch.nn.functional.interpolate(depth, size=(480, 640), mode="bilinear", align_corners=False)
     K = torch.eye(4).repeat(frames, 1, 1)
     K[:, 0, 0] = K[:, 1, 1] = 577.87
@@ -210,9 +221,21 @@ def test_fused_room_mesh():
 
 
 def test_default_volume_mesh():
+    """The default 504^3 volume (62 512 bricks: every thread of the scan owns 62) against the oracle on a crop.
+
+    The fused surface is a close one (depths 0.2 .. 0.35 m), because the box of touched voxels is wide whatever the depth: the
+    voxel layers next to the camera plane are updated out to the volume's faces (their fp16 pixel coordinates overflow and the
+    fuser samples texel 0, as the reference does), so the box spans all of x and y and only its z extent -- the sheet's few
+    layers plus depth + truncation -- can be kept small enough for the oracle (at most 4 M voxels).  That sheet also puts
+    active bricks all along the brick order, which is what the scan's offsets need.
+
+    Outside the box every voxel is -1, so no edge out there crosses the level, and both sides walk voxels lexicographically:
+    the crop's mesh is the volume's mesh with vertex coordinates shifted by the crop's offset, vertex for vertex and face for
+    face.  Dilating the box by 2 voxels gives the normals' central differences the same neighbours on both sides."""
     fuser = OurFuser(max_fusion_depth=3.0, device=DEV)
     assert tuple(fuser.tsdf_fuser_pred.shape) == (504, 504, 504)
-    _room(fuser, frames=2)
+    assert tsdf_cases.mesh_plan((504, 504, 504))["chunk"] == 62
+    _room(fuser, frames=2, near=0.2, span=0.15)
     torch.cuda.synchronize()
     t0 = time.monotonic()
     m = fuser.get_mesh()
@@ -221,6 +244,36 @@ def test_default_volume_mesh():
     assert m.faces.shape[0] > 1000 and m.vertices.shape[0] > 1000
     assert int(m.faces.min()) >= 0 and int(m.faces.max()) < m.vertices.shape[0]
     assert dt < 30.0, f"504^3 extraction took {dt:.1f} s"
+
+    vol = fuser.tsdf_fuser_pred.tsdf
+    touched = vol.tsdf_weights > 0
+    lo, hi = [], []
+    for a in range(3):
+        idx = torch.nonzero(touched.any(dim=tuple(d for d in range(3) if d != a)))[:, 0]
+        lo.append(max(0, int(idx.min()) - 2))
+        hi.append(min(504, int(idx.max()) + 1 + 2))
+    size = (hi[0] - lo[0]) * (hi[1] - lo[1]) * (hi[2] - lo[2])
+    print(f"box of touched voxels, dilated by 2: {lo} .. {hi}, {size} voxels")
+    assert size <= 4_000_000, f"the dilated box {lo} .. {hi} is too large for the oracle"
+    unchanged = vol.tsdf_values == -1
+    unchanged[lo[0]:hi[0], lo[1]:hi[1], lo[2]:hi[2]] = True
+    assert bool(unchanged.all()), "a voxel outside the box is not -1"
+    del unchanged, touched
+    crop = vol.tsdf_values[lo[0]:hi[0], lo[1]:hi[1], lo[2]:hi[2]].cpu().numpy()
+    vo, fo, no, _ = mo.marching_cubes(crop)
+    u = vol.extract_mesh(scale_to_world=False)
+    v, f, n = u.vertices.cpu().numpy(), u.faces.cpu().numpy(), u.normals.cpu().numpy()
+    assert len(v) == len(vo) == m.vertices.shape[0] and f.shape == fo.shape == tuple(m.faces.shape)
+    assert np.array_equal(f, fo), "faces differ from the crop's, or come in another order"
+    assert np.abs(n - no).max(initial=0.0) < 1e-5
+    # A coordinate is index + t in fp32, t in [0, 1) the crossing's position on its edge.  Index + t < 512, where fp32 values are
+    # 2^-15 apart: the volume's mesh rounds it once (error <= 2^-16); the crop's mesh rounds (index - lo) + t, also below 512,
+    # once (<= 2^-16), and the offset is added here in float64 (exact).  t itself is the same fp32 expression on both sides,
+    # allowed one unit in its last place (2^-23, the spacing just below 1) as in _assert_matches_oracle.
+    bound = 2.0 ** -16 + 2.0 ** -16 + 2.0 ** -23
+    err = float(np.abs(v.astype(np.float64) - (vo.astype(np.float64) + np.asarray(lo, np.float64))).max())
+    print(f"vertex error {err:.3e}, bound {bound:.3e}")
+    assert err <= bound
 
 
 def test_save_and_export(tmp_path):
